@@ -3,7 +3,7 @@
 configs[1]); weak scaling over N GPUs (one process per GPU, RCCL all-gather of the [256,512] embeddings per step
 on a side stream = BASELINE.json configs[4] at N = 8).
 
-    python bench.py [--gpus N --steps K --warmup W]          # N > 1 without WORLD_SIZE: starts the N ranks itself
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # N > 1 without WORLD_SIZE: starts the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,12 @@ A step = one pass of ``encode_image`` over one batch of 256 synthetic N(0,1) cro
 Rank 0 prints ONE JSON line.  Weights are the seeded synthetic ViT-B/16 of hoigen_amd.synth (no checkpoint is
 reachable offline).  `value` is measured with every row of every block computed (option last_block_row0 = 0).
 
-Extra objects on the line:
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line (`value`, `ms_per_step` = milliseconds
+per timed step, `step_ms` = median / p10 / p90 of the individual timed steps from events on the compute stream, `config`).  --dump-outputs DIR then writes what the last timed step returned as
+DIR/embeddings.npy (float32, [N x 256, 512]); crops and weights are seeded, so equal arguments give equal inputs.
+
+Extra objects on the line, measured only with --full (--no-cpu-baseline / --no-extra-configs / --no-class-rows / --power
+narrow that down):
   roofline         the kernel with the largest share of the step (found by timing every GEMM / attention launch of
                    two untimed steps), timed live with hipEvent pairs on its launch stream during the first timed
                    steps: achieved = mean algorithmic FLOPs per launch / mean duration, vs the dense 16-bit MFMA peak
@@ -19,8 +24,8 @@ Extra objects on the line:
                    the 40 % target.
   kernels          per launch shape: launches per step, mean ms, FLOPs, fraction of MFMA peak, algorithmic HBM bytes
                    and fraction of 8 TB/s (from the two untimed, fully instrumented steps).
-  step_ms          median / p10 / p90 of the individual timed steps (events on the compute stream).
   class_rows_only  the library's default (last block on the class-token rows only), same protocol.
+  parity           encode_image of the reference fixture's 4 crops against its output, both last-block settings.
   power            (N = 1) package power / shader clock while the headline step runs (rocm-smi beside an untimed burst).
   variant_c        (N = 1) the detector's call `visual(x, prior)` with instance adapters on the same crops.
   config3/config4  (N = 1) encode_text over the 600 HICO prompts and the CoOp-VAE on 100 000 rows, each with its own
@@ -64,13 +69,23 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH, help="crops per GPU per step (metric is quoted at 256)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the embeddings of the last timed step as DIR/embeddings.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel table and roofline, class-rows-only region, parity, "
+                         "power, CPU baselines, variant C, configs 3 / 4, generation (a plain run times the headline steps only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the config3 / config4 objects")
     ap.add_argument("--no-class-rows", action="store_true",
                     help="skip the second timed region (the library's default last block); for kernel traces of the headline alone")
     ap.add_argument("--power", action="store_true",
-                    help="with --no-extra-configs: still sample package power / clock beside the headline step (A/B runs)")
-    return ap.parse_args()
+                    help="with --full --no-extra-configs: still sample package power / clock beside the headline step (A/B runs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.power and not args.full:
+        ap.error("--power is part of --full")
+    return args
 
 
 def self_launch(args) -> int:
@@ -92,6 +107,10 @@ def self_launch(args) -> int:
         cmd.append("--no-class-rows")
     if args.power:
         cmd.append("--power")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -472,6 +491,102 @@ def aggregate(recs, steps):
     return out
 
 
+def kernel_table(model, step, batch):
+    """(--full) The `kernels` table and the launches behind `roofline`, from instrumented steps run before the timed region."""
+    from hoigen_amd import _lib
+    global RLN_STREAM_BYTES
+    hilo = ctypes.c_int32(0)
+    _lib.lib().hg_get_option(model.visual._ctx.handle, b"stream_hilo", ctypes.byref(hilo))
+    if hilo.value and batch * 197 >= 512:
+        # 23 such launches per all-rows step, lo = b bytes (bf8: 1, the default build; fp16: 2): 21 read and write hi + lo (4 + 2b), the first
+        # reads fp32 and writes hi + lo (6 + b), the last reads hi + lo and writes fp32 + copy (8 + b)
+        lo_bits = ctypes.c_int32(16)
+        _lib.lib().hg_get_option(model.visual._ctx.handle, b"stream_lo_bits", ctypes.byref(lo_bits))
+        b = lo_bits.value / 8.0
+        RLN_STREAM_BYTES = (21 * (4 + 2 * b) + (6 + b) + (8 + b)) / 23
+    # two more untimed steps with every GEMM / attention launch bracketed by events: the per-kernel table, and which
+    # kernel the live `roofline` measurement of the timed region follows
+    PROF_STEPS = 4
+    _, all_recs = _lib.profile(model.visual._ctx.handle, _lib.HG_PROF_ALL, PROF_STEPS * 128,
+                               lambda: [step() for _ in range(PROF_STEPS)])
+    kernels = aggregate(all_recs, PROF_STEPS)
+    by_kind = {}
+    for k in kernels:
+        by_kind[k["kind"]] = by_kind.get(k["kind"], 0.0) + k["ms_per_step"]
+    dom_kind = max(by_kind, key=by_kind.get)
+    dom_launches = int(round(sum(k["launches_per_step"] for k in kernels if k["kind"] == dom_kind)))
+
+    # `roofline`: the dominant kernel's launches of those untimed steps (hipEvent pairs on the stream it is launched on, this process,
+    # right before the timed region) - the timed region itself carries no instrumentation (VERDICT r5 item 9)
+    live = [r for r in all_recs if r[0] == dom_kind]
+    return kernels, live, by_kind, dom_kind, dom_launches, PROF_STEPS
+
+
+def roofline(live, by_kind, dom_kind, dom_launches, prof_steps, crops_per_s_per_gpu):
+    """(--full) The `roofline` object: the dominant kernel's launches of the instrumented steps, and the whole step."""
+    flops_l = sum(kernel_row(*r[:4])[1] for r in live) / max(1, len(live))
+    bytes_l = sum(kernel_row(*r[:4])[2] for r in live) / max(1, len(live))
+    ms_l = sum(r[4] for r in live) / max(1, len(live))
+    ach = flops_l / ms_l / 1e9 if ms_l > 0 else 0.0
+    traffic = step_traffic = traffic_source = None
+    tpath = os.path.join(HERE, "profiles", "traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            traffic = tj.get(f"kind{dom_kind}_hbm_bytes_per_launch")
+            # HBM-side bytes of the whole step (FETCH_SIZE x 2 + WRITE_SIZE over every kernel of one all-rows step), from the
+            # same PMC passes (tools/gpu_energy_ab.sh); the default configuration's entry
+            st = tj.get("step_total_MB", {})
+            key = next((k for k in st if "(default)" in k and "stagger" in k), next((k for k in st if "(default)" in k), None))
+            step_traffic = int(st[key] * 1e6) if key else None
+            # these two are CONSTANTS read from the committed file (separate rocprofv3 --pmc passes), not counters of this run
+            traffic_source = (f"profiles/traffic.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round {tj.get('round', '?')}"
+                              f" on the library at commit {tj.get('commit', 'unrecorded')}; file constants, NOT counters of this run")
+        except Exception:
+            traffic = step_traffic = traffic_source = None
+    e2e = crops_per_s_per_gpu * FLOPS_PER_CROP / 1e12
+    shapes = sorted({(r[1], r[2], r[3]) for r in live})
+    return {"bound": "mfma",
+            "kernel": f"{KIND_NAMES.get(dom_kind, dom_kind)}: the kernel with the largest share of the step "
+                      f"({by_kind[dom_kind]:.3f} of {sum(by_kind.values()):.3f} ms of GEMM+attention time), "
+                      f"{dom_launches} launches per step, shapes (M,N,K) {shapes}",
+            "achieved": round(ach, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "step_traffic": step_traffic,
+            "traffic_source": traffic_source,
+            "avg_kernel_ms": round(ms_l, 4), "avg_gflop_per_launch": round(flops_l / 1e9, 2),
+            "launches_timed": len(live),
+            "how": f"hipEvent pairs around every launch of this kernel in {prof_steps} untimed steps run right before the "
+                   "timed region (same process, same stream); the timed region carries no events but one per step",
+            "algorithmic_hbm_bytes_per_launch": int(bytes_l),
+            "hbm_frac_algorithmic": round(bytes_l / ms_l / 1e6 / HBM_PEAK_GBS, 4) if ms_l > 0 else None,
+            "e2e_tflops": round(e2e, 2), "e2e_frac": round(e2e / MFMA_PEAK_TFLOPS, 4),
+            "target_e2e_frac": 0.40}
+
+
+def fixture_parity(model, dev):
+    """(--full) Parity beside the speed: the reference's own fixture (4 seeded crops, tests/golden/g2_vitb16_image.npz), whole
+    matrix and worst row, for both settings of last_block_row0; None when the fixture is absent."""
+    import torch
+    from hoigen_amd import synth
+    parity = None
+    g2p = os.path.join(HERE, "tests", "golden", "g2_vitb16_image.npz")
+    if os.path.exists(g2p):
+        import numpy as np
+        ref = torch.from_numpy(np.load(g2p)["encode_image"]).to(dev).float()
+        gold = torch.from_numpy(synth.crops(4, 224, seed=1234)).to(dev)
+        def _rel(o):
+            d = (o.float() - ref)
+            return {"rel_l2": float(f"{(d.norm() / ref.norm()).item():.3e}"),
+                    "worst_row_rel_l2": float(f"{(d.norm(dim=1) / ref.norm(dim=1)).max().item():.3e}")}
+        parity = {"what": "encode_image of the reference's 4 fixture crops vs the reference's CPU fp32 output (tolerance 1e-3)"}
+        cur = model.visual.get_option("last_block_row0")
+        for name, mode in (("all_rows", 0), ("class_rows_only", 1)):
+            model.visual.set_option("last_block_row0", mode)
+            parity[name] = _rel(model.visual.forward_trace(gold)[0])
+        model.visual.set_option("last_block_row0", cur)
+    return parity
+
+
 # ----------------------------------------------------------------------------------------------------------------
 def run(args):
     import torch
@@ -543,63 +658,27 @@ def run(args):
     model.visual.set_option("last_block_row0", 0)       # headline: every row of every block (hg_set_option on this context)
     for _ in range(args.warmup):
         step()
-    global RLN_STREAM_BYTES
-    hilo = ctypes.c_int32(0)
-    _lib.lib().hg_get_option(model.visual._ctx.handle, b"stream_hilo", ctypes.byref(hilo))
-    if hilo.value and args.batch * 197 >= 512:
-        # 23 such launches per all-rows step, lo = b bytes (bf8: 1, the default build; fp16: 2): 21 read and write hi + lo (4 + 2b), the first
-        # reads fp32 and writes hi + lo (6 + b), the last reads hi + lo and writes fp32 + copy (8 + b)
-        lo_bits = ctypes.c_int32(16)
-        _lib.lib().hg_get_option(model.visual._ctx.handle, b"stream_lo_bits", ctypes.byref(lo_bits))
-        b = lo_bits.value / 8.0
-        RLN_STREAM_BYTES = (21 * (4 + 2 * b) + (6 + b) + (8 + b)) / 23
-    # two more untimed steps with every GEMM / attention launch bracketed by events: the per-kernel table, and which
-    # kernel the live `roofline` measurement of the timed region follows
-    PROF_STEPS = 4
-    _, all_recs = _lib.profile(model.visual._ctx.handle, _lib.HG_PROF_ALL, PROF_STEPS * 128,
-                               lambda: [step() for _ in range(PROF_STEPS)])
-    kernels = aggregate(all_recs, PROF_STEPS)
-    by_kind = {}
-    for k in kernels:
-        by_kind[k["kind"]] = by_kind.get(k["kind"], 0.0) + k["ms_per_step"]
-    dom_kind = max(by_kind, key=by_kind.get)
-    dom_launches = int(round(sum(k["launches_per_step"] for k in kernels if k["kind"] == dom_kind)))
-
-    # `roofline`: the dominant kernel's launches of those untimed steps (hipEvent pairs on the stream it is launched on, this process,
-    # right before the timed region) - the timed region itself carries no instrumentation
-    live = [r for r in all_recs if r[0] == dom_kind]
+    if args.full:
+        kernels, live, by_kind, dom_kind, dom_launches, prof_steps = kernel_table(model, step, args.batch)
     dt, per_step, _, out = timed_region()
     assert torch.isfinite(out).all()
     out = out.clone()                                    # (the gather buffers are reused by the next steps)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "embeddings.npy"), out.float().cpu().numpy())
 
     # the library's default path (last block on the class-token rows only), same protocol
-    if args.no_class_rows:
-        dt2, rel = dt, 0.0
-    else:
+    dt2, rel, parity = dt, 0.0, None
+    if args.full and not args.no_class_rows:
         model.visual.set_option("last_block_row0", prev_row0 if prev_row0 is not None else 1)
         for _ in range(args.warmup):
             step()
         dt2, per_step2, _, out2 = timed_region()
         assert torch.isfinite(out2).all()
         rel = float(((out2.float() - out.float()).norm() / out.float().norm()).item())
-
-    # parity beside the speed: the reference's own fixture (4 seeded crops, tests/golden/g2_vitb16_image.npz), whole matrix and worst row
-    parity = None
-    g2p = os.path.join(HERE, "tests", "golden", "g2_vitb16_image.npz")
-    if rank == 0 and os.path.exists(g2p):
-        import numpy as np
-        ref = torch.from_numpy(np.load(g2p)["encode_image"]).to(dev).float()
-        gold = torch.from_numpy(synth.crops(4, 224, seed=1234)).to(dev)
-        def _rel(o):
-            d = (o.float() - ref)
-            return {"rel_l2": float(f"{(d.norm() / ref.norm()).item():.3e}"),
-                    "worst_row_rel_l2": float(f"{(d.norm(dim=1) / ref.norm(dim=1)).max().item():.3e}")}
-        parity = {"what": "encode_image of the reference's 4 fixture crops vs the reference's CPU fp32 output (tolerance 1e-3)"}
-        cur = model.visual.get_option("last_block_row0")
-        for name, mode in (("all_rows", 0), ("class_rows_only", 1)):
-            model.visual.set_option("last_block_row0", mode)
-            parity[name] = _rel(model.visual.forward_trace(gold)[0])
-        model.visual.set_option("last_block_row0", cur)
+    if args.full and rank == 0:
+        parity = fixture_parity(model, dev)
 
     t = torch.tensor([dt, dt2], device=dev, dtype=torch.float64)
     if world > 1 or force_comm:
@@ -609,30 +688,8 @@ def run(args):
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = world * args.batch * args.steps / dt
-        flops_l = sum(kernel_row(*r[:4])[1] for r in live) / max(1, len(live))
-        bytes_l = sum(kernel_row(*r[:4])[2] for r in live) / max(1, len(live))
-        ms_l = sum(r[4] for r in live) / max(1, len(live))
-        ach = flops_l / ms_l / 1e9 if ms_l > 0 else 0.0
-        traffic = step_traffic = traffic_source = None
-        tpath = os.path.join(HERE, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get(f"kind{dom_kind}_hbm_bytes_per_launch")
-                # HBM-side bytes of the whole step (FETCH_SIZE x 2 + WRITE_SIZE over every kernel of one all-rows step), from the
-                # same PMC passes (tools/gpu_energy_ab.sh); the default configuration's entry
-                st = tj.get("step_total_MB", {})
-                key = next((k for k in st if "(default)" in k and "stagger" in k), next((k for k in st if "(default)" in k), None))
-                step_traffic = int(st[key] * 1e6) if key else None
-                # these two are CONSTANTS read from the committed file (separate rocprofv3 --pmc passes), not counters of this run
-                traffic_source = (f"profiles/traffic.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round {tj.get('round', '?')}"
-                                  f" on the library at commit {tj.get('commit', 'unrecorded')}; file constants, NOT counters of this run")
-            except Exception:
-                traffic = step_traffic = traffic_source = None
         ps = sorted(per_step)
         pct = lambda q: round(ps[min(len(ps) - 1, int(q * len(ps)))], 4)
-        e2e = value / world * FLOPS_PER_CROP / 1e12
-        shapes = sorted({(r[1], r[2], r[3]) for r in live})
         line = {
             "metric": "union-crop embeddings/sec ViT-B/16 bs=256",
             "value": round(value, 2), "unit": "crops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -646,28 +703,15 @@ def run(args):
                        "batch_per_gpu": args.batch, "global_batch": world * args.batch,
                        "parallelism": f"dp{world}" + (f" + in-place all_gather[{world}x{args.batch}x512 f32] per step on a side stream" if (world > 1 or force_comm) else "")},
             "step_ms": {"median": pct(0.5), "p10": pct(0.1), "p90": pct(0.9), "how": "hipEvents on the compute stream around every timed step"},
-            "roofline": {"bound": "mfma",
-                         "kernel": f"{KIND_NAMES.get(dom_kind, dom_kind)}: the kernel with the largest share of the step "
-                                   f"({by_kind[dom_kind]:.3f} of {sum(by_kind.values()):.3f} ms of GEMM+attention time), "
-                                   f"{dom_launches} launches per step, shapes (M,N,K) {shapes}",
-                         "achieved": round(ach, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "step_traffic": step_traffic,
-                         "traffic_source": traffic_source,
-                         "avg_kernel_ms": round(ms_l, 4), "avg_gflop_per_launch": round(flops_l / 1e9, 2),
-                         "launches_timed": len(live),
-                         "how": f"hipEvent pairs around every launch of this kernel in {PROF_STEPS} untimed steps run right before the "
-                                "timed region (same process, same stream); the timed region carries no events but one per step",
-                         "algorithmic_hbm_bytes_per_launch": int(bytes_l),
-                         "hbm_frac_algorithmic": round(bytes_l / ms_l / 1e6 / HBM_PEAK_GBS, 4) if ms_l > 0 else None,
-                         "e2e_tflops": round(e2e, 2), "e2e_frac": round(e2e / MFMA_PEAK_TFLOPS, 4),
-                         "target_e2e_frac": 0.40},
-            "kernels": [{k: v for k, v in r.items() if k != "kind"} for r in kernels],
         }
+        if args.full:
+            line["roofline"] = roofline(live, by_kind, dom_kind, dom_launches, prof_steps, value / world)
+            line["kernels"] = [{k: v for k, v in r.items() if k != "kind"} for r in kernels]
         if parity is not None:
             line["parity"] = parity
         v2 = world * args.batch * args.steps / dt2
         f2 = FLOPS_PER_CROP - FLOPS_DEAD_ROWS
-        if not args.no_class_rows:
+        if args.full and not args.no_class_rows:
             line["class_rows_only"] = {
                 "what": "library default: last block = K/V for all rows, then attention / out-proj / MLP for the class-token "
                         "row only (rows that cannot reach the embedding are not computed)",
@@ -675,7 +719,7 @@ def run(args):
                 "flops_per_crop_executed": round(f2 / 1e9, 3),
                 "e2e_frac": round(v2 / world * f2 / 1e12 / MFMA_PEAK_TFLOPS, 4),
                 "rel_l2_vs_all_rows": float(f"{rel:.3e}")}
-        if world == 1:
+        if world == 1 and args.full:
             if (not args.no_extra_configs or args.power) and not force_comm:
                 model.visual.set_option("last_block_row0", 0)
                 try:

@@ -41,9 +41,9 @@ import pytest  # noqa: E402
 
 @pytest.mark.gpu
 def test_bench_line_schema_on_gpu():
-    """One short run of the real benchmark: the JSON line carries the contract's fields, the roofline of the dominant
+    """One short run of the real benchmark with --full: the JSON line carries the contract's fields, the roofline of the dominant
     kernel, the per-kernel table and the two extra configurations."""
-    r = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"], timeout=900)
+    r = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line"
@@ -66,6 +66,37 @@ def test_bench_line_schema_on_gpu():
     assert 0.8 * d["ms_per_step"] < sum(by_kernel.values()) < 1.12 * d["ms_per_step"]
     assert d["config4"]["ms"] > 0 and d["config3"]["truncated"]["ms"] < d["config3"]["full_77_tokens"]["ms"]
     assert 1.0 < d["variant_c"]["over_variant_a_all_rows"] < 1.3 and d["variant_c"]["crops_per_s"] > 0
+
+
+def test_power_needs_full_and_steps_must_be_positive():
+    """Checked by the argument parser, before anything touches the GPU runtime."""
+    r = _run(["--steps", "3", "--warmup", "1", "--power"])
+    assert r.returncode == 2 and "--power is part of --full" in r.stderr
+    r = _run(["--steps", "0", "--warmup", "1"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the contract's fields for exactly --steps timed steps, none of the objects that --full
+    adds, and --dump-outputs writes the last timed step's embeddings as float32."""
+    r = _run(["--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "exactly one JSON line"
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "step_ms"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "crops/s" and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    for k in ("roofline", "kernels", "class_rows_only", "parity", "power", "cpu_baseline", "variant_c", "config3", "config4",
+              "generation"):
+        assert k not in d, k
+    import numpy as np
+    assert sorted(os.listdir(tmp_path)) == ["embeddings.npy"]
+    e = np.load(tmp_path / "embeddings.npy")
+    assert e.shape == (256, 512) and e.dtype == np.float32 and np.isfinite(e).all()
+    assert np.abs(e[0] - e[1]).max() > 0
 
 
 @pytest.mark.gpu

@@ -1,11 +1,11 @@
 #!/bin/bash
 # FETCH_SIZE (x2, MB per launch) of the residual / QKV / c_fc GEMMs for several env settings: CONFIGS="name:ENV=V,ENV=V ..."
-R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/out}; export OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for cfg in $CONFIGS; do
   name=${cfg%%:*}; envs=${cfg#*:}
   if [ "$envs" != "-" ]; then for kv in ${envs//,/ }; do export $kv; done; fi
-  rm -rf $R/gpurun_out/pmc_x; rocprofv3 --kernel-trace --pmc ${PMC:-FETCH_SIZE} --output-format csv -d $R/gpurun_out/pmc_x -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-class-rows > $R/gpurun_out/pmc_x.log 2>&1
-  python3 - "$name" $R/gpurun_out/pmc_x <<'PY'
+  rm -rf $OUT/pmc_x; rocprofv3 --kernel-trace --pmc ${PMC:-FETCH_SIZE} --output-format csv -d $OUT/pmc_x -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-class-rows > $OUT/pmc_x.log 2>&1
+  python3 - "$name" $OUT/pmc_x <<'PY'
 import csv,glob,sys,collections,re
 fs=glob.glob(sys.argv[2]+'/**/*counter_collection.csv',recursive=True)
 if not fs: print(sys.argv[1],'no csv'); sys.exit()

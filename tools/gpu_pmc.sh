@@ -1,18 +1,18 @@
 #!/bin/bash
 # PMC counter passes over a short bench run (separate passes; --pmc only with --kernel-trace).
-R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/out}; export OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-run() { name=$1; shift; rm -rf $R/gpurun_out/pmc_$name; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $R/gpurun_out/pmc_$name -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $R/gpurun_out/pmc_$name.log 2>&1; }
+run() { name=$1; shift; rm -rf $OUT/pmc_$name; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$name -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/pmc_$name.log 2>&1; }
 run sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES
 run fetch FETCH_SIZE
 run write WRITE_SIZE
 run tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum
 cd $R
 python3 - <<'PY'
-import csv,glob,collections
+import csv,glob,collections,os
+OUT=os.environ["OUT"]
 for name in ['sq','fetch','write','tcc']:
-    fs=glob.glob(f'gpurun_out/pmc_{name}/**/*counter_collection.csv',recursive=True)
+    fs=glob.glob(f'{OUT}/pmc_{name}/**/*counter_collection.csv',recursive=True)
     if not fs: print(name,'no file'); continue
     agg=collections.defaultdict(lambda: collections.defaultdict(float)); cnt=collections.Counter()
     for row in csv.DictReader(open(fs[0])):

@@ -1,13 +1,14 @@
 #!/bin/bash
 # SQ counter pass over the all-rows headline step (own run: --pmc with --kernel-trace only): MFMA busy cycles, wave cycles, waits, LDS
-R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out; cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/pmc_sq
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $R/gpurun_out/pmc_sq -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-class-rows > $R/gpurun_out/pmc_sq.log 2>&1
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/out}; export OUT; mkdir -p $OUT; cd /tmp && export TMPDIR=/tmp
+rm -rf $OUT/pmc_sq
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-class-rows > $OUT/pmc_sq.log 2>&1
 cd $R
 python3 - <<'PY'
-import csv,glob,collections
-fs=glob.glob('gpurun_out/pmc_sq/**/*counter_collection.csv',recursive=True)
-tr=glob.glob('gpurun_out/pmc_sq/**/*kernel_trace.csv',recursive=True)
+import csv,glob,collections,os
+OUT=os.environ["OUT"]
+fs=glob.glob(OUT + '/pmc_sq/**/*counter_collection.csv',recursive=True)
+tr=glob.glob(OUT + '/pmc_sq/**/*kernel_trace.csv',recursive=True)
 dur=collections.defaultdict(list)
 if tr:
     for r in csv.DictReader(open(tr[0])): dur[r['Kernel_Name'][:70]].append(int(r['End_Timestamp'])-int(r['Start_Timestamp']))

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Copy the summaries of tools/gpu_r6_collect.sh (gpurun_out/r06/) into profiles/ as r06_<tag>_* and rewrite profiles/traffic.json from
+"""Copy the summaries of tools/gpu_r6_collect.sh ($OUT/r06/) into profiles/ as r06_<tag>_* and rewrite profiles/traffic.json from
 its FETCH_SIZE / WRITE_SIZE passes.  usage: r6_profiles.py <tag> (e.g. v1); the library's commit is read from git here."""
 import collections, csv, glob, json, os, re, shutil, subprocess, sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-O = os.path.join(R, "gpurun_out", "r06")
+O = os.path.join(os.environ.get("OUT") or os.path.join(R, "out"), "r06")
 tag = sys.argv[1] if len(sys.argv) > 1 else "v1"
 P = os.path.join(R, "profiles")
 for src, dst in (("headline_allrows_kernel_stats.csv", f"r06_{tag}_headline_allrows_kernel_stats.csv"),

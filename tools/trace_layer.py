@@ -1,6 +1,7 @@
-"""Print the per-dispatch durations of one transformer layer from the newest rocprofv3 kernel trace under gpurun_out/pm."""
+"""Print the per-dispatch durations of one transformer layer from the newest rocprofv3 kernel trace under $OUT/pm (tools/gpu_modes.sh)."""
 import csv, glob, os, sys
-f = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpurun_out", "pm", "*", "*_kernel_trace.csv")),
+OUT = os.environ.get("OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "out")
+f = sorted(glob.glob(os.path.join(OUT, "pm", "*", "*_kernel_trace.csv")),
            key=os.path.getmtime)[-1]
 rows = list(csv.DictReader(open(f)))
 seq = [(r["Kernel_Name"].replace("void hg::", "").replace("_ZN2hg", "")[:34], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3) for r in rows]
