@@ -8,8 +8,6 @@
 // of 32, FFN 64-128-64, two LayerNorms) is 1.7 % of a block's FLOPs and runs in fp32 on the VALU:
 // one lane per token, the token's activations in a private LDS row, weights fetched with wave-uniform
 // (scalar-cache) loads so every FMA takes an SGPR weight operand.
-#include <stdlib.h>
-
 #include "hg_kernels.h"
 
 namespace hg {
@@ -654,12 +652,8 @@ bool adapter_decoder_fused_down_ok(const AdapterDev& ad, bool priors, int L, int
     return adapter_decoder_mfma_ok(ad, priors, L, N) && 64 * ((L + 31) / 32) >= 384;
 }
 // the MFMA decoder serves sequences of at most NKMAX tokens and at most 32 prior tokens; anything else runs the fp32
-// one-lane-per-token kernels below (in -DHG_EXPERIMENTS builds HG_ADAPTER_MFMA=0 forces those for A/B timing)
+// one-lane-per-token kernels below
 bool adapter_decoder_mfma_ok(const AdapterDev& ad, bool priors, int L, int N) {
-#ifdef HG_EXPERIMENTS
-    static const bool on = []() { const char* e = getenv("HG_ADAPTER_MFMA"); return !(e && e[0] == '0'); }();
-    if (!on) return false;
-#endif
     return ad.w16[priors ? 0 : 1][0] && L <= NKMAX && (priors ? N <= 32 : true);
 }
 

@@ -46,8 +46,6 @@ struct BlockW {
     // MFMA fragments per head pair); null when the width does not qualify
     half_t* wp_qkv;
     float* bcs_qkv;
-    // c_fc / c_proj as the fragment stream of the one-kernel MLP block (hg_vae_fused.hip, mode 3): width 512 only (the text tower)
-    half_t* wp_mlp;
 };
 
 struct AdapterW {
@@ -157,15 +155,10 @@ struct hg_ctx {
                                  // the GEMMs keep the layer's own fp16 weights - closer to the reference than the separate kernels, 4 % faster);
                                  // 2 the weight folded into fp16(W * gamma) as in the vision tower (10 % faster, 7.6e-4 instead of 6.2e-4); 0 separate kernels
     int opt_qkv_attn_c = 1;      // ... also in the blocks that carry a folded adapter (variant C on the hi / lo stream: K = D + 64)
-    int opt_mlp_fused = 0;       // blocks of width 512 (text tower): 1 = c_fc -> QuickGELU -> c_proj -> residual as ONE kernel for the rows that
-                                 // fill whole rounds of 128-row items (hg_vae_fused.hip, mode 3), 2 = every row, 0 (default) = the two GEMMs:
-                                 // measured a tie (65 534-row pass: 331-335 us against 161 + 190; the generation pipeline -1.4 %) and a loss
-                                 // where a call leaves a remainder (600 prompts x 77 tokens: 5.47 -> 5.66 ms)
     int opt_vae_fused = 1;       // CoOp-VAE Encoder -> reparameterise -> Generator as ONE kernel (hg_vae_fused.hip) for the rows that fill
                                  // whole rounds of 128-row items over the CUs (the rest: the GEMM path); 2: every row; 0: GEMM path only
     int opt_mlp_pair = 1;        // c_fc -> QuickGELU -> c_proj of a LayerNorm-folded block as ONE persistent launch with per-row-panel ready
-                                 // counters between its tiles (hg_mlp_pair.hip; both towers, variant A); bit-identical to the two launches;
-                                 // 2: finalize_stats of the next LayerNorm in the launch's tail as well
+                                 // counters between its tiles (hg_mlp_pair.hip; both towers, variant A); bit-identical to the two launches
     int opt_mlp_pair_chunk = 32; // ... 256-row panels of an XCD per chunk
     int opt_mlp_pair_fc_slots = 32;  // ... workgroups per XCD that run c_fc tiles (the rest start with c_proj)
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
@@ -250,9 +243,6 @@ struct PairGateScope {      // around ONE pair launch on stream s of device dev 
     hipStream_t s;
     PairGateScope(int dev, hipStream_t s_) : g(&g_pair_gate[dev & 15]), s(s_) {
         g->mu.lock();
-#ifdef HG_NO_PAIR_GATE      // (experiment build: what two streams do to each other without the gate)
-        return;
-#endif
         if (!g->have_first) { g->first = s; g->have_first = true; }
         else if (!g->multi && s != g->first) {
             (void)hipDeviceSynchronize();      // (once: whatever the first stream has in flight carries no event)
@@ -355,21 +345,6 @@ int as_f32_T(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, int rows,
     return HG_OK;
 }
 
-// The MLP of a width-512 block as one kernel (option mlp_fused, hg_vae_fused.hip mode 3) reads its two weights as a packed fragment
-// stream: 4.3 MB per block, 52 MB for the text tower - packed when the option is on at load time or is switched on later, not for
-// every tower (the option defaults to 0: measured a tie).
-int pack_mlp_blocks(hg_ctx* c, std::vector<void*>& owned, std::vector<BlockW>& blocks, int D) {
-    if (!vae_fused_ok(D, 0, 4 * D)) return HG_OK;
-    for (BlockW& b : blocks) {
-        if (b.wp_mlp) continue;
-        int rc = 0;
-        keep_first(rc, dev_alloc(c, owned, vae_fused_pass_bytes(4 * D), (void**)&b.wp_mlp));
-        if (rc) return rc < 0 ? rc : HG_ERR_OOM;
-        HG_HIP(launch_pack_vae(nullptr, nullptr, 0, b.w_fc, b.w_proj, 4 * D, b.wp_mlp, 0));
-    }
-    return HG_OK;
-}
-
 int load_blocks(hg_ctx* c, std::vector<void*>& owned, const hg_block_weights* src, int layers, int D,
                 std::vector<BlockW>& dst, bool fold_ln) {
     if (!src) return fail(c, HG_ERR_INVALID, "blocks == NULL");
@@ -410,10 +385,6 @@ int load_blocks(hg_ctx* c, std::vector<void*>& owned, const hg_block_weights* sr
             HG_HIP(launch_pack_qkv(b.wf_qkv, b.bf_qkv, b.cs_qkv, b.wp_qkv, b.bcs_qkv, D, D / 64, 0));
         }
 
-    }
-    if (c->opt_mlp_fused) {
-        int rc = pack_mlp_blocks(c, owned, dst, D);
-        if (rc) return rc;
     }
     return HG_OK;
 }
@@ -794,7 +765,7 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
     }
     if (pre_w && trace) HG_HIP(launch_copy_rows(x, trace, n_seq, L, D, s));
     // Residual stream as centre + hi + lo between the LayerNorm-emitting residual GEMMs (GemmArgs::hl; option stream_hilo):
-    // hi IS the centred fp16 copy those GEMMs write anyway, lo its remainder as bf8 (HG_LO8; fp16 otherwise) - 6 (8) instead of 10
+    // hi IS the centred fp16 copy those GEMMs write anyway, lo its remainder as bf8 - 6 instead of 10
     // bytes per element through every such epilogue and a third fewer partial-line stores.  The first of them reads the fp32 stream (ln_pre wrote it),
     // the last one writes fp32 again (the plain last c_proj / the class-rows path / ln_post read it); nothing in between
     // touches x.  Variant A, and variant C when EVERY block's adapter is folded into its GEMMs (mode 2: nothing but the residual GEMMs
@@ -964,9 +935,8 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
         }
         g = GemmArgs{};
         g.A = h; g.lda = D; g.out = fc; g.ldc = 4 * D; g.M = M; g.N = 4 * D; g.K = D;
-        int mlp_done = 0;      // leading rows whose MLP ran as the one kernel (separate-LayerNorm path, width 512)
         GemmArgs pq{};         // option mlp_pair: the c_proj arguments, built ahead of c_fc (pq_built), and whether the pair kernel took both
-        bool pq_built = false, paired = false, pair_fin = false;
+        bool pq_built = false, paired = false;
         if (fuse) {
             g.W = b.wf_fc; g.bias = b.bf_fc; g.cs = b.cs_fc; g.mr = mr;
             if (hilo_c) { g.A = att; g.lda = D + 64; }
@@ -980,39 +950,19 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
                 if (mlp_pair_ok(g, pq, c->n_cu)) {
                     PairGateScope gate(c->device, s);
                     ProfScope ps(c, s, HG_PROF_MLP_PAIR, M, 4 * D, D);
-                    // (option mlp_pair = 2: the launch's tail also does finalize_stats' work - measured +10 us on the launch for the 5 us
-                    // launch it removes in the vision tower, a tie in the text tower (profiles/r06_mlp_pair.txt item 8); 1: its own launch)
-                    const bool fin = c->opt_mlp_pair == 2;
                     HG_HIP(launch_mlp_pair(g, pq, (unsigned*)c->pair_ready.p + i * (size_t)pair_panels, c->pair_err,
-                                           c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, fin ? mr : nullptr, mu, muc,
-                                           c->range_flag, c->opt_mlp_pair_fault));
+                                           c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, c->opt_mlp_pair_fault));
                     paired = true;
-                    pair_fin = fin;
                 }
             }
             if (!paired) HG_HIP(gemm(c, EPI_LN_BIAS_QGELU_F16, g, s));
         } else {
             HG_HIP(launch_layernorm_f16(x, b.ln2_w, b.ln2_b, h, M, D, nullptr, 0, 1, s));
-            // Width 512 (the text tower): x += W_proj quickgelu(W_fc h + b_fc) + b_proj as ONE kernel for the leading rows that fill
-            // whole rounds of its 128-row items (hg_vae_fused.hip mode 3: the [rows, 2048] activation stays on chip); the rest below
-            mlp_done = (b.wp_mlp && !trace) ? fused_item_rows(c, c->opt_mlp_fused, M) : 0;
-            if (mlp_done > 0) {
-                VaeFusedArgs a{};
-                a.x16 = h; a.bias = x; a.wp = b.wp_mlp; a.b0g = b.b_fc; a.b2g = b.b_proj;
-                a.R = mlp_done; a.eh = 0; a.gh = 4 * D; a.mode = 3; a.has_enc = false;
-                ProfScope ps(c, s, HG_PROF_VAE_FUSED, mlp_done, 1, 4 * D);
-                HG_HIP(launch_vae_fused(a, s));
-            }
-            if (mlp_done < M) {
-                g.A = h + (size_t)mlp_done * D; g.M = M - mlp_done;
-                g.W = b.w_fc; g.bias = b.b_fc;
-                HG_HIP(gemm(c, EPI_BIAS_QGELU_F16, g, s));
-            }
+            g.W = b.w_fc; g.bias = b.b_fc;
+            HG_HIP(gemm(c, EPI_BIAS_QGELU_F16, g, s));
         }
-        if (mlp_done >= M) continue;      // (only without a trace, on the separate-LayerNorm path: the stream is the fp32 x)
         g = GemmArgs{};
-        g.A = fc; g.lda = 4 * D; g.W = b.w_proj; g.bias = b.b_proj; g.out = x + (size_t)mlp_done * D; g.ldc = D; g.M = M - mlp_done; g.N = D;
-        g.K = 4 * D;
+        g.A = fc; g.lda = 4 * D; g.W = b.w_proj; g.bias = b.b_proj; g.out = x; g.ldc = D; g.M = M; g.N = D; g.K = 4 * D;
         if (fuse && i + 1 < blocks.size()) {      // the last block is followed by ln_post / ln_final on selected rows
             if (pq_built) {
                 g = pq;
@@ -1022,7 +972,7 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
                 gs_args(g, blocks[i + 1].ln1_w);
             }
             if (!paired) HG_HIP(gemm(c, EPI_RESID_LN_F32, g, s));
-            if (!pair_fin) HG_HIP(launch_finalize_stats(stats, mr, mu, M, sld, 64, s, muc, false, c->range_flag));
+            HG_HIP(launch_finalize_stats(stats, mr, mu, M, sld, 64, s, muc, false, c->range_flag));
         } else {
             HG_HIP(gemm(c, EPI_BIAS_RESID_F32, g, s));
         }
@@ -1158,7 +1108,7 @@ hg_ctx* hg_create(int device) {
                                                            {"HG_LN_FUSE", "ln_fuse"}, {"HG_ADAPTER_FUSE", "adapter_fuse"},
                                                            {"HG_ADAPTER_FOLD", "adapter_fold"}, {"HG_STREAM_HILO", "stream_hilo"},
                                                            {"HG_QKV_ATTN", "qkv_attn"}, {"HG_QKV_ATTN_MIN_SEQ", "qkv_attn_min_seq"},
-                                                           {"HG_QKV_ATTN_GSZ", "qkv_attn_gsz"}, {"HG_QKV_ATTN_C", "qkv_attn_c"}, {"HG_TEXT_LN_FOLD", "text_ln_fold"}, {"HG_VAE_FUSED", "vae_fused"}, {"HG_MLP_FUSED", "mlp_fused"},
+                                                           {"HG_QKV_ATTN_GSZ", "qkv_attn_gsz"}, {"HG_QKV_ATTN_C", "qkv_attn_c"}, {"HG_TEXT_LN_FOLD", "text_ln_fold"}, {"HG_VAE_FUSED", "vae_fused"},
                                                            {"HG_MLP_PAIR", "mlp_pair"},
                                                            {"HG_MLP_PAIR_CHUNK", "mlp_pair_chunk"}, {"HG_MLP_PAIR_FC_SLOTS", "mlp_pair_fc_slots"},
                                                            {"HG_MLP_PAIR_FAULT", "mlp_pair_fault"}};
@@ -1198,16 +1148,8 @@ int hg_set_option(hg_ctx* c, const char* key, int value) {
     else if (k == "vae_fused") {
         if (value < 0 || value > 2) return fail(c, HG_ERR_INVALID, "vae_fused must be 0, 1 or 2 (got %d)", value);
         c->opt_vae_fused = value;
-    } else if (k == "mlp_fused") {
-        if (value < 0 || value > 2) return fail(c, HG_ERR_INVALID, "mlp_fused must be 0, 1 or 2 (got %d)", value);
-        c->opt_mlp_fused = value;
-        if (value && c->text.loaded) {      // the packed operand of that kernel is made on demand
-            HG_ON_DEVICE(c);
-            int rc = pack_mlp_blocks(c, c->text.owned, c->text.blocks, c->text.D);
-            if (rc) return rc;
-        }
     } else if (k == "mlp_pair") {
-        if (value < 0 || value > 2) return fail(c, HG_ERR_INVALID, "mlp_pair must be 0, 1 or 2 (got %d)", value);
+        if (value < 0 || value > 1) return fail(c, HG_ERR_INVALID, "mlp_pair must be 0 or 1 (got %d)", value);
         c->opt_mlp_pair = value;
     } else if (k == "mlp_pair_chunk") {
         if (value < 1 || value > 64) return fail(c, HG_ERR_INVALID, "mlp_pair_chunk must be 1 .. 64 (got %d)", value);
@@ -1232,14 +1174,13 @@ int hg_get_option(hg_ctx* c, const char* key, int* value) {
     else if (k == "adapter_fuse") *value = c->opt_adapter_fuse;
     else if (k == "adapter_fold") *value = c->opt_adapter_fold;
     else if (k == "stream_hilo") *value = c->opt_stream_hilo;
-    else if (k == "stream_lo_bits") *value = HG_LO8 ? 8 : 16;      // read-only: how the build holds the low half
+    else if (k == "stream_lo_bits") *value = 8;      // read-only: the low half of the stream is bf8
     else if (k == "qkv_attn") *value = c->opt_qkv_attn;
     else if (k == "qkv_attn_min_seq") *value = c->opt_qkv_attn_min_seq;
     else if (k == "qkv_attn_gsz") *value = c->opt_qkv_attn_gsz;
     else if (k == "qkv_attn_c") *value = c->opt_qkv_attn_c;
     else if (k == "text_ln_fold") *value = c->opt_text_ln_fold;
     else if (k == "vae_fused") *value = c->opt_vae_fused;
-    else if (k == "mlp_fused") *value = c->opt_mlp_fused;
     else if (k == "mlp_pair") *value = c->opt_mlp_pair;
     else if (k == "mlp_pair_chunk") *value = c->opt_mlp_pair_chunk;
     else if (k == "mlp_pair_fc_slots") *value = c->opt_mlp_pair_fc_slots;

@@ -487,7 +487,7 @@ hipError_t launch_copy_rows(const float* x, float* out, int B, int row_stride, i
 }
 // row b * row_stride of a stream held as centre + hi + lo (GemmArgs::hl): hi row-major [*, D], lo in gemm_ring2's tile-fragment
 // order (tile 128 x 256; wave = (row % 64) / 32 * 4 + (col % 128) / 32; piece = (row / 64 % 2, col / 128 % 2, col / 16 % 2);
-// lane = (col % 16) / 4 * 16 + row % 16; inside the lane's 16 bytes: row tile (row % 32) / 16, then col % 4)
+// lane = (col % 16) / 4 * 16 + row % 16; inside the lane's 8 bytes: row tile (row % 32) / 16, then col % 4)
 __global__ void copy_rows_hilo_kernel(const half_t* __restrict__ hi, const half_t* __restrict__ lo, const float* __restrict__ muc,
                                       float* __restrict__ out, int B, int row_stride, int D) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -500,13 +500,8 @@ __global__ void copy_rows_hilo_kernel(const half_t* __restrict__ hi, const half_
     const int piece = (r >> 6) * 4 + (cc >> 7) * 2 + ((cc >> 4) & 1);
     const int lane = ((cc & 15) >> 2) * 16 + (r & 15);
     const size_t lo_i = (((tile * 8 + wave) * 8 + piece) * 64 + lane) * 8 + ((r & 31) >> 4) * 4 + (cc & 3);
-    float lof;
-    if constexpr (HG_LO8) {      // bf8 (e5m2) = the top byte of an fp16
-        const unsigned short b = reinterpret_cast<const unsigned char*>(lo)[lo_i];
-        lof = (float)__builtin_bit_cast(half_t, (unsigned short)(b << 8)) * (1.0f / HG_LO_SCALE);
-    } else {
-        lof = (float)lo[lo_i];
-    }
+    const unsigned short b8 = reinterpret_cast<const unsigned char*>(lo)[lo_i];      // bf8 (e5m2) = the top byte of an fp16
+    const float lof = (float)__builtin_bit_cast(half_t, (unsigned short)(b8 << 8)) * (1.0f / HG_LO_SCALE);
     out[i] = (muc[m] + (float)hi[m * D + n]) + lof;
 }
 hipError_t launch_copy_rows_hilo(const half_t* hi, const half_t* lo, const float* muc, float* out, int B, int row_stride, int D,

@@ -50,7 +50,7 @@ namespace hg {
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_duo(const GemmArgs p, const int tiles_n, const int n_tiles,
-                                                   const unsigned a_bytes, const int gsz, const int xm) {
+                                                   const unsigned a_bytes, const int gsz) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 128, BK = 64;
     constexpr int A_BYTES = 16384, W_BYTES = 32768;
@@ -89,11 +89,6 @@ __global__ __launch_bounds__(256, 2) void gemm_duo(const GemmArgs p, const int t
     };
     if (my_tiles <= 0) return;
     const int S = my_tiles * nk;                                   // K-tiles in this workgroup's stream
-#ifdef HG_EXPERIMENTS
-    const int xmode = xm;        // timing experiments (wrong results): 1 every tile streams A tile 0, 2 epilogue on tile 0's rows
-#else
-    constexpr int xmode = 0;
-#endif
 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW =
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo(const GemmArgs p, const int t
     {
         int tm, tn;
         tile_of(slot, tm, tn);
-        lA.org = (xmode & 1) ? 0 : tm * BM * p.lda * 2;
+        lA.org = tm * BM * p.lda * 2;
         lW.org = tn * 256 * p.K * 2;
     }
     auto ld_advance = [&](Ld& l, bool isA) {
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo(const GemmArgs p, const int t
             if (l.r < my_tiles) {
                 int tm, tn;
                 tile_of(slot + l.r * cpx, tm, tn);
-                l.org = isA ? ((xmode & 1) ? 0 : tm * BM * p.lda * 2) : tn * 256 * p.K * 2;
+                l.org = isA ? tm * BM * p.lda * 2 : tn * 256 * p.K * 2;
             }
         }
     };
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo(const GemmArgs p, const int t
     for (int r = 0; r < my_tiles; ++r) {
         int tm, tn;
         tile_of(slot + r * cpx, tm, tn);
-        const int m0 = (xmode & 2) ? 0 : tm * BM, n0 = tn * 256;
+        const int m0 = tm * BM, n0 = tn * 256;
 #pragma unroll
         for (int f = 0; f < 4; ++f)
 #pragma unroll
@@ -432,27 +427,14 @@ static hipError_t launch_duo_t(const GemmArgs& a, hipStream_t s) {
     const int tiles_m = (a.M + 127) / 128, tiles_n = a.N / 256;
     const int n_tiles = tiles_m * tiles_n;
     const size_t a_bytes = (size_t)tiles_m * 128 * a.lda * 2;
-#ifdef HG_EXPERIMENTS
-    static const int gsz_env = []() { const char* e = getenv("HG_RING_GSZ"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int gsz_env = 0;
-#endif
-    int gsz = gsz_env > 0 ? gsz_env : (int)((1536 * 1024) / ((size_t)512 * a.K));
+    int gsz = (int)((1536 * 1024) / ((size_t)512 * a.K));
     if (gsz < 3) gsz = 3;
     if (gsz > tiles_n) gsz = tiles_n;
-    if (gsz_env <= 0) {
+    {
         const int ngroups = (tiles_n + gsz - 1) / gsz;
         gsz = (tiles_n + ngroups - 1) / ngroups;
     }
-    // timing experiments: HG_DUO_LDS_CUT = bytes requested less (results wrong), HG_DUO_GRID = workgroups per CU
-#ifdef HG_EXPERIMENTS
-    static const int xm_env = []() { const char* e = getenv("HG_DUO_XMODE"); return e ? atoi(e) : 0; }();
-    static const int lds_cut = []() { const char* e = getenv("HG_DUO_LDS_CUT"); return e ? atoi(e) : 0; }();
-    static const int per_cu = []() { const char* e = getenv("HG_DUO_GRID"); const int v = e ? atoi(e) : 2; return v >= 1 ? v : 2; }();
-#else
-    constexpr int xm_env = 0, lds_cut = 0, per_cu = 2;
-#endif
-    const int grid2 = n_tiles < per_cu * n_cu ? n_tiles : per_cu * n_cu;
+    const int grid2 = n_tiles < 2 * n_cu ? n_tiles : 2 * n_cu;      // two workgroups per CU
 #ifdef HG_STAMPS
     if (getenv("HG_STAMPS")) {
         const size_t n = (size_t)grid2 * 4 * 16;
@@ -461,7 +443,7 @@ static hipError_t launch_duo_t(const GemmArgs& a, hipStream_t s) {
         hipMemsetAsync(d, 0, n * 8, s);
         GemmArgs b = a;
         b.dbg = d;
-        hipLaunchKernelGGL((gemm_duo<EPI>), dim3(grid2), dim3(256), LDS - lds_cut, s, b, tiles_n, n_tiles, (unsigned)a_bytes, gsz, xm_env);
+        hipLaunchKernelGGL((gemm_duo<EPI>), dim3(grid2), dim3(256), LDS, s, b, tiles_n, n_tiles, (unsigned)a_bytes, gsz);
         hipStreamSynchronize(s);
         unsigned long long* h = (unsigned long long*)malloc(n * 8);
         hipMemcpy(h, d, n * 8, hipMemcpyDeviceToHost);
@@ -480,7 +462,7 @@ static hipError_t launch_duo_t(const GemmArgs& a, hipStream_t s) {
         return hipGetLastError();
     }
 #endif
-    hipLaunchKernelGGL((gemm_duo<EPI>), dim3(grid2), dim3(256), LDS - lds_cut, s, a, tiles_n, n_tiles, (unsigned)a_bytes, gsz, xm_env);
+    hipLaunchKernelGGL((gemm_duo<EPI>), dim3(grid2), dim3(256), LDS, s, a, tiles_n, n_tiles, (unsigned)a_bytes, gsz);
     return hipGetLastError();
 }
 

@@ -88,68 +88,25 @@ static hipError_t launch_ring_t(const GemmArgs& a_in, hipStream_t s) {
     // Even rounds: the tiles take `rounds` passes over the CUs whatever the grid, so use only as many workgroups as fill every
     // round (a multiple of 8: the XCD-chunked tile order needs it).  c_fc at batch 256: 2364 tiles = 10 rounds on 240
     // workgroups instead of 9.23 on 256 - the same number of rounds with fewer CUs contending for L2 / HBM: 236-239 -> 230 us
-    // (round 3, one box; QKV's 1773 tiles stay on 256).  (HG_RING_GRID overrides in -DHG_EXPERIMENTS builds.)
+    // (round 3, one box; QKV's 1773 tiles stay on 256).
     if (MF == 4 && n_tiles > n_cu) {
         const int rounds = (n_tiles + n_cu - 1) / n_cu;
         const int g8 = (((n_tiles + rounds - 1) / rounds) + 7) & ~7;
         if (g8 < grid) grid = g8;
     }
-#ifdef HG_EXPERIMENTS
-    if (const char* e = getenv("HG_RING_GRID")) { const int v = atoi(e); if (v >= 8 && v <= n_cu && v <= n_tiles) grid = v; }
-#endif
     const size_t a_bytes = (size_t)tiles_m * BM * a.lda * 2;      // A is allocated with rows padded to 256
-    // start stagger: estimated cycles per K-tile (a deliberate under-estimate).  The timing-experiment switches HG_RING_MODE,
-    // HG_RING_DELAY (0 = no stagger) and HG_RING_GSZ are read in -DHG_EXPERIMENTS builds only
-#ifdef HG_EXPERIMENTS
-    static const int mode = []() {
-        const char* e = getenv("HG_RING_MODE");
-        const char* d = getenv("HG_RING_DELAY");
-        return (e ? atoi(e) & 0xFF : 0) | ((d ? atoi(d) : (MF == 4 ? 3000 : 1800)) << 8);
-    }();
-    static const int gsz_env = []() { const char* e = getenv("HG_RING_GSZ"); return e ? atoi(e) : 0; }();
-#else
+    // start stagger: estimated cycles per K-tile (a deliberate under-estimate), in the kernel's `mode` >> 8
     constexpr int mode = (MF == 4 ? 3000 : 1800) << 8;
-    constexpr int gsz_env = 0;
-#endif
     // column tiles per L2 group: W slices of one group (gsz * 256 rows * K * 2 B) should fit ~1.5 MiB, but
     // never fewer than 3: an A panel that is not shared by neighbouring column tiles is re-read from HBM once
     // per column tile (c_proj, K = 3072: 310 MB of activations x 3)
-    int gsz = gsz_env > 0 ? gsz_env : (int)((1536 * 1024) / ((size_t)512 * a.K));
+    int gsz = (int)((1536 * 1024) / ((size_t)512 * a.K));
     if (gsz < 3) gsz = 3;
     if (gsz > tiles_n) gsz = tiles_n;
-    if (gsz_env <= 0) {                                  // equal groups: 9 column tiles -> 3 + 3 + 3, not 4 + 4 + 1
+    {                                                    // equal groups: 9 column tiles -> 3 + 3 + 3, not 4 + 4 + 1
         const int ngroups = (tiles_n + gsz - 1) / gsz;
         gsz = (tiles_n + ngroups - 1) / ngroups;
     }
-#ifdef HG_TRACE
-    if (getenv("HG_TRACE")) {
-        const size_t n = (size_t)grid * 8 * 16;
-        unsigned long long* d = nullptr;
-        if (hipMalloc(&d, n * 8) != hipSuccess) return hipErrorOutOfMemory;
-        hipMemsetAsync(d, 0, n * 8, s);
-        GemmArgs b = a;
-        b.dbg = d;
-        hipLaunchKernelGGL((gemm_ring<MF, EPI, PH2>), dim3(grid), dim3(512), LDS, s, b, tiles_n, n_tiles, (unsigned)a_bytes, mode, gsz);
-        hipStreamSynchronize(s);
-        unsigned long long* h = (unsigned long long*)malloc(n * 8);
-        hipMemcpy(h, d, n * 8, hipMemcpyDeviceToHost);
-        for (int blk : {0, 9, 130}) {
-            if (blk >= grid) continue;
-            const unsigned long long t0 = h[(size_t)(blk * 8) * 16];
-            for (int w : {0, 4}) {
-                fprintf(stderr, "[trace] ring<%d,%d> N=%d K=%d block %d wave %d:", MF, EPI, a.N, a.K, blk, w);
-                for (int k = 0; k < 16; ++k) {
-                    const unsigned long long t = h[(size_t)(blk * 8 + w) * 16 + k];
-                    if (t) fprintf(stderr, " %lld", (long long)(t - t0));
-                }
-                fprintf(stderr, "\n");
-            }
-        }
-        free(h);
-        hipFree(d);
-        return hipGetLastError();
-    }
-#endif
 #ifdef HG_STAMPS
     if (getenv("HG_STAMPS")) {
         const size_t n = (size_t)grid * 8 * 16;
@@ -200,10 +157,9 @@ bool gemm_ln_ok(int epi, const GemmArgs& a) {
 // 256x256 tiles: two phases per K-tile, except with the residual epilogues (their rolling window does not fit beside the
 // two-phase loop's fragment registers: those instantiations would spill and are never built)
 template <int E>
-static hipError_t launch_big(const GemmArgs& a, hipStream_t s, bool ph2) {
+static hipError_t launch_big(const GemmArgs& a, hipStream_t s) {
     constexpr bool resid = (E == EPI_BIAS_RESID_F32 || E == EPI_SCALE_RESID_F32 || E == EPI_RESID_LN_F32);
-    if constexpr (resid) return launch_ring_t<4, E, false>(a, s);
-    else return ph2 ? launch_ring_t<4, E, true>(a, s) : launch_ring_t<4, E, false>(a, s);
+    return launch_ring_t<4, E, !resid>(a, s);
 }
 
 hipError_t launch_gemm_ring(int epi, const GemmArgs& a, hipStream_t s) {
@@ -215,13 +171,6 @@ hipError_t launch_gemm_ring(int epi, const GemmArgs& a, hipStream_t s) {
     // as rounds(256) <= 0.8 * rounds(128): N = 768, M = 50432: 3 vs 5 * 0.8.
     const int t256 = ((a.M + 255) / 256) * (a.N / 256), t128 = ((a.M + 127) / 128) * (a.N / 256);
     const int rounds = (t256 + 255) / 256, rounds128 = (t128 + 255) / 256;
-#ifdef HG_EXPERIMENTS
-    static const int force_big = []() { const char* e = getenv("HG_RING_BIG"); return e ? atoi(e) : 0; }();
-    static const bool ph2 = []() { const char* e = getenv("HG_RING_PH2"); return e ? atoi(e) != 0 : true; }();
-#else
-    constexpr int force_big = 0;
-    constexpr bool ph2 = true;
-#endif
     bool big = t256 >= 256 && (double)t256 / (rounds * 256.0) >= 0.9;
     // ... or when its whole passes (even rounds: launch_ring_t uses only as many workgroups as fill them) still beat the
     // 128-row kernel's: text-tower QKV, M = 46 200, N = 1536: 5 passes of 256x256 against 8.5 of 128x256 at ~0.8 of the time
@@ -231,16 +180,14 @@ hipError_t launch_gemm_ring(int epi, const GemmArgs& a, hipStream_t s) {
     // (fp16 copy + statistics: 387 MB per launch) the epilogue is an HBM burst of every CU at once, and three big
     // bursts overlap worse than five small ones (K = 768: 154 vs 127 us; K = 3072: 300 vs 303): keep 128 rows.
     if (resid && epi != EPI_RESID_LN_F32 && t256 >= 256 && (double)rounds <= 0.8 * rounds128 + 1e-9) big = true;
-    if (force_big == 1) big = true;
-    if (force_big == 2 || force_big == 3) big = false;
     if (epi == EPI_RESID_LN_F32 && (!big || a.hl || a.gamma)) return launch_gemm_ring2(epi, a, s);     // no 128-row variant in this kernel; the hi / lo stream lives in ring2's tile order
-    if (!big && force_big != 3 && !lnc && gemm_ring2_ok(a)) return launch_gemm_ring2(epi, a, s);   // 128x256, two-phase
-    // 256x256 tiles run two phases per K-tile (32 MFMAs per segment): -4..8 % vs four phases (HG_RING_PH2=0 in experiments builds)
+    if (!big && !lnc && gemm_ring2_ok(a)) return launch_gemm_ring2(epi, a, s);   // 128x256, two-phase
+    // 256x256 tiles run two phases per K-tile (32 MFMAs per segment): -4..8 % vs four phases
     // ... except with the residual epilogues: their rolling window does not fit beside the two-phase loop's fragment
     // registers (9-21 spilled VGPRs, 4-10 % slower than four phases)
 #define HG_RING(E)                                                         \
     case E:                                                                \
-        return big ? launch_big<E>(a, s, ph2) : launch_ring_t<2, E, false>(a, s)
+        return big ? launch_big<E>(a, s) : launch_ring_t<2, E, false>(a, s)
     switch (epi) {
         HG_RING(EPI_BIAS_F16);
         HG_RING(EPI_BIAS_QGELU_F16);

@@ -25,9 +25,9 @@ namespace hg {
 // HL (EPI_RESID_LN_F32 only): how the residual stream is held on the way in / out (GemmArgs::hl): 0 fp32 / fp32, 1 fp32 /
 // hi + lo, 2 hi + lo / hi + lo, 3 hi + lo / fp32.  hi = the centred fp16 copy (row-major: the next GEMM's operand), lo = the
 // remainder (x - centre) - hi in tile-fragment order: piece (ha, hb, g2) of a wave = this lane's two row tiles f = 0, 1 side by
-// side, 64 lanes contiguous - whole lines in, whole lines out.  lo is bf8 (HG_LO8, hg_kernels.h: 2 x 4 B per lane; 6 bytes per
-// element through the epilogue) or fp16 (2 x 8 B; 8 bytes) instead of the fp32 stream's 10, and 16 instead of 24 partial-line
-// store instructions per wave and tile.
+// side, 64 lanes contiguous - whole lines in, whole lines out.  lo is bf8 (hg_kernels.h: 2 x 4 B per lane; 6 bytes per
+// element through the epilogue) instead of the fp32 stream's 10, and 16 instead of 24 partial-line store instructions per wave
+// and tile.
 // GS (EPI_RESID_LN_F32 only; GemmArgs::gamma): the copy the next GEMM reads is fp16((x' - mu) * gamma[n]) - the next LayerNorm's weight
 // rides in the ACTIVATION copy, so that the consuming GEMM multiplies by the layer's own fp16 weights (as the reference does) and not by
 // a re-rounded fp16(W * gamma): the folded text tower's excess error against the reference was that second rounding
@@ -38,15 +38,8 @@ template <int EPI, int HL, bool GS, class SCHED>
 __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int tiles_n, const unsigned a_bytes, const int mode,
                                                 const SCHED& sc) {
 #if defined(__HIP_DEVICE_COMPILE__)   // device-only builtins (buffer resources, LDS DMA): host sees just the stub
-    // timing-experiment switches (HG_RING_MODE bits 1 locality, 2 no MFMA, 4 no epilogue, 8 no stagger, 64 no operand DMA)
-    // exist only in a -DHG_EXPERIMENTS build: run-time branches in the K loop cost several per cent.  (Round 2's store
-    // experiments - lane-linear stores, a tile's read-modify-write trickled under the next tile's K loop as junk accesses -
-    // are in the history; results in DESIGN.md 4.)
-#ifdef HG_EXPERIMENTS
-    const int xmode = mode;
-#else
-    constexpr int xmode = 0;
-#endif
+    // mode >> 8: the start stagger's estimated cycles per K-tile (0 = off).  (Round 2's store experiments - lane-linear stores, a
+    // tile's read-modify-write trickled under the next tile's K loop as junk accesses - are in the history; results in DESIGN.md 4.)
     constexpr int BM = 128, BK = 64;
     constexpr int AB = 16384, WH = 16384;              // bytes: A tile (both halves), one W half
     constexpr int STAGE = AB + 2 * WH;                 // 48 KiB
@@ -98,13 +91,10 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
         const int dunit = mode >> 8;                               // estimated cycles per K-tile, 0 = off
         const int slack = sc.slack();
         if (dunit > 0 && slack > 0) {
-#ifndef HG_R2_DELAY_HASH
-#define HG_R2_DELAY_HASH 1
-#endif
-            // what the pseudo-random fraction is drawn from: 1 (default) the workgroup's XCD - the slack workgroups of an XCD stay in
-            // step with each other, they share activation panels through its L2: 583 instead of 670 MB fetched per launch, step
-            // -0.8 % (profiles/r04_energy_ab5_stagger.txt); 0 the workgroup itself (rounds 1-3)
-            const unsigned hkey = HG_R2_DELAY_HASH == 1 ? (unsigned)(bid & 7) * 37u + 11u : (unsigned)bid;
+            // the pseudo-random fraction is drawn from the workgroup's XCD - the slack workgroups of an XCD stay in step with each
+            // other, they share activation panels through its L2: 583 instead of 670 MB fetched per launch, step -0.8 % against
+            // drawing it from the workgroup itself, as rounds 1-3 did (profiles/r04_energy_ab5_stagger.txt)
+            const unsigned hkey = (unsigned)(bid & 7) * 37u + 11u;
             const unsigned h = (hkey * 2654435761u) >> 24;   // 0..255
             const long long d = ((long long)slack * nk * dunit * h) >> 8;
             const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -145,7 +135,7 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
             ++l.r;
             int tm, tn;
             tile_of(l.r, tm, tn);
-            l.soff = (xmode & 1) ? 0 : (isA ? tm * BM * p.lda * 2 : tn * 256 * p.K * 2);   // mode 1: every tile reads tile 0
+            l.soff = isA ? tm * BM * p.lda * 2 : tn * 256 * p.K * 2;
         }
         l.st = l.st == (NST - 1) * STAGE ? 0 : l.st + STAGE;      // stage of stream position g is g % NST
     };
@@ -153,13 +143,11 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
     // which the hardware also adds to the global address, so voff*[i] carry -1024 * i
     auto dma_A = [&](auto I) {
         constexpr int i = decltype(I)::value;
-        if (xmode & 64) return;   // timing experiment: no operand DMA
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (HG_LDS void*)(smem + lA.st + wave * GA * 1024), 16, voffA[i],
                                                  lA.soff + lA.kt * (BK * 2), i * 1024, CON ? 16 /* sc1 */ : 0);
     };
     auto dma_W = [&](auto I) {
         constexpr int i = decltype(I)::value;
-        if (xmode & 64) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + lW.st + AB + wave * GW * 1024), 16, voffW[i],
                                                  lW.soff + lW.kt * (BK * 2), i * 1024, 0);
     };
@@ -206,18 +194,6 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
     f32x4 acc[2][2][2][2];
     auto mma = [&](auto HA) {
         constexpr int ha = decltype(HA)::value;
-        if (xmode & 2) {   // timing experiment: no MFMAs (operands kept live)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int f = 0; f < 2; ++f) asm volatile("" ::"v"(xa[f][ks]));
-#pragma unroll
-                for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-                    for (int g2 = 0; g2 < 2; ++g2) asm volatile("" ::"v"(wb[hb][g2][ks]));
-            }
-            return;
-        }
         SEG_B(3);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -273,7 +249,7 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
     else if (S > 1) wait_vm<GW + GA>();
     else wait_vm<0>();
     barrier_raw();
-    const bool late = (wave >= 4) && !(xmode & 8);
+    const bool late = wave >= 4;
     if (late) barrier_raw();
 
 #ifdef HG_STAMPS
@@ -306,8 +282,7 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
         float mucv[IN_HL ? 2 : 1][IN_HL ? 2 : 1];     // centre the hi / lo being read were written with
         // lo piece (ha, hb, g2) of this wave and tile: 64 lanes x 16 B
         auto lo_ptr = [&](int tm_, int tn_, int ha, int hb, int g2) {
-            return p.lo + ((((size_t)tm_ * tiles_n + tn_) * 8 + wave) * 8 + (ha * 4 + hb * 2 + g2)) * (HG_LO8 ? 256 : 512) +
-                   lane * (HG_LO8 ? 4 : 8);
+            return p.lo + ((((size_t)tm_ * tiles_n + tn_) * 8 + wave) * 8 + (ha * 4 + hb * 2 + g2)) * 256 + lane * 4;
         };
         // One K-tile.  KIND: 0 middle, 1 first of a tile (the previous epilogue's stores may be pending), 2 / 3 / 4 the
         // third-to-last, second-to-last and last K-tile of a tile: only there the refills (A at distance 2, W at
@@ -342,13 +317,9 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
                             for (int g2 = 0; g2 < 2; ++g2) {
                                 xhi[ha][hb][g2] = *reinterpret_cast<const u32x4_hl*>(
                                     p.out2 + (size_t)mp * p.ld2 + n0 + hb * 128 + wn * 32 + g2 * 16 + 4 * (qq & ~1));
-                                if constexpr (HG_LO8) {
-                                    typedef unsigned u32x2_hl __attribute__((ext_vector_type(2)));
-                                    const u32x2_hl l8 = *reinterpret_cast<const u32x2_hl*>(lo_ptr(tm, tn, ha, hb, g2));
-                                    xlo[ha][hb][g2] = u32x4_hl{l8[0], l8[1], 0u, 0u};
-                                } else {
-                                    xlo[ha][hb][g2] = *reinterpret_cast<const u32x4_hl*>(lo_ptr(tm, tn, ha, hb, g2));
-                                }
+                                typedef unsigned u32x2_hl __attribute__((ext_vector_type(2)));
+                                const u32x2_hl l8 = *reinterpret_cast<const u32x2_hl*>(lo_ptr(tm, tn, ha, hb, g2));
+                                xlo[ha][hb][g2] = u32x4_hl{l8[0], l8[1], 0u, 0u};
                             }
 #pragma unroll
                         for (int f = 0; f < 2; ++f) {
@@ -418,17 +389,6 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
         }
         // ---------------- epilogue
         SEG_B(7);
-        if (xmode & 4) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int f = 0; f < 2; ++f)
-#pragma unroll
-                        for (int g2 = 0; g2 < 2; ++g2) asm volatile("" ::"v"(acc[a][b][f][g2]));
-            continue;
-        }
         const int q = lane >> 4;
         // tiles entirely inside M (all of them at M = 197 * 256) skip the per-store row masks
         auto epilogue = [&](auto INTERIOR_T) {
@@ -479,8 +439,7 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
             for (int ha = 0; ha < 2; ++ha) {
                 half4 h16[2][2][2];                         // [f][hb][g2]: the new copy (hi)
                 half4 g16[GS && OUT_HL ? 2 : 1][GS && OUT_HL ? 2 : 1][GS && OUT_HL ? 2 : 1];      // ... times gamma, where hi must stay unscaled
-                half4 l16[OUT_HL ? 2 : 1][OUT_HL ? 2 : 1][OUT_HL ? 2 : 1];
-                unsigned l8[OUT_HL ? 2 : 1][OUT_HL ? 2 : 1][OUT_HL ? 2 : 1];      // HG_LO8: the remainder as four bf8 (e5m2)
+                unsigned l8[OUT_HL ? 2 : 1][OUT_HL ? 2 : 1][OUT_HL ? 2 : 1];      // the remainder as four bf8 (e5m2)
                 half4 hin[IN_HL ? 2 : 1][IN_HL ? 2 : 1][IN_HL ? 2 : 1];
                 f32x4 lin[IN_HL ? 2 : 1][IN_HL ? 2 : 1][IN_HL ? 2 : 1];
                 if constexpr (IN_HL) {
@@ -495,19 +454,11 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
                             const auto s1 = __builtin_amdgcn_permlane16_swap(o[1], o[3], false, false);
                             hin[0][hb][g2] = __builtin_bit_cast(half4, u32x2{(unsigned)s0[0], (unsigned)s1[0]});
                             hin[1][hb][g2] = __builtin_bit_cast(half4, u32x2{(unsigned)s0[1], (unsigned)s1[1]});
-                            if constexpr (HG_LO8) {
 #pragma unroll
-                                for (int f = 0; f < 2; ++f) {
-                                    const auto a = __builtin_amdgcn_cvt_pk_f32_bf8((int)l[f], false);
-                                    const auto b = __builtin_amdgcn_cvt_pk_f32_bf8((int)l[f], true);
-                                    lin[f][hb][g2] = f32x4{a[0], a[1], b[0], b[1]};
-                                }
-                            } else {
-#pragma unroll
-                                for (int f = 0; f < 2; ++f) {
-                                    const half4 lh = __builtin_bit_cast(half4, u32x2{l[2 * f], l[2 * f + 1]});
-                                    lin[f][hb][g2] = f32x4{(float)lh[0], (float)lh[1], (float)lh[2], (float)lh[3]};
-                                }
+                            for (int f = 0; f < 2; ++f) {
+                                const auto a = __builtin_amdgcn_cvt_pk_f32_bf8((int)l[f], false);
+                                const auto b = __builtin_amdgcn_cvt_pk_f32_bf8((int)l[f], true);
+                                lin[f][hb][g2] = f32x4{a[0], a[1], b[0], b[1]};
                             }
                         }
                 }
@@ -528,8 +479,8 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
 #pragma unroll
                                 for (int e2 = 0; e2 < 2; ++e2) {
                                     const half2v h2 = {hin[f][hb][g2][2 * e2], hin[f][hb][g2][2 * e2 + 1]};
-                                    // (lo is stored scaled by HG_LO_SCALE when it is bf8: one packed fma instead of the add)
-                                    const f32x2 ls2 = {HG_LO8 ? 1.0f / HG_LO_SCALE : 1.0f, HG_LO8 ? 1.0f / HG_LO_SCALE : 1.0f};
+                                    // (lo is stored scaled by HG_LO_SCALE: one packed fma instead of the add)
+                                    const f32x2 ls2 = {1.0f / HG_LO_SCALE, 1.0f / HG_LO_SCALE};
                                     const f32x2 x2 = f32x2{lin[f][hb][g2][2 * e2], lin[f][hb][g2][2 * e2 + 1]} * ls2 +
                                                      (mc2 + __builtin_convertvector(h2, f32x2));
                                     xin[2 * e2] = x2[0];
@@ -569,16 +520,12 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
                                 h16[f][hb][g2][2 * e2 + 1] = hh[1];
                                 if constexpr (OUT_HL) {
                                     const f32x2 r = d - __builtin_convertvector(hh, f32x2);
-                                    const f32x2 rs = HG_LO8 ? r * f32x2{HG_LO_SCALE, HG_LO_SCALE} : r;
+                                    const f32x2 rs = r * f32x2{HG_LO_SCALE, HG_LO_SCALE};
                                     rem[2 * e2] = rs[0];
                                     rem[2 * e2 + 1] = rs[1];
-                                    if constexpr (!HG_LO8) {
-                                        l16[f][hb][g2][2 * e2] = (half_t)r[0];
-                                        l16[f][hb][g2][2 * e2 + 1] = (half_t)r[1];
-                                    }
                                 }
                             }
-                            if constexpr (OUT_HL && HG_LO8) {
+                            if constexpr (OUT_HL) {
                                 int w8 = __builtin_amdgcn_cvt_pk_bf8_f32(rem[0], rem[1], 0, false);
                                 w8 = __builtin_amdgcn_cvt_pk_bf8_f32(rem[2], rem[3], w8, true);
                                 l8[f][hb][g2] = (unsigned)w8;
@@ -625,12 +572,7 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
                             if (INTERIOR || m < p.M) *reinterpret_cast<u32x4*>(p.out3 + (size_t)m * p.ld3 + nb + 4 * (q & ~1)) = og;
                         }
                         if constexpr (OUT_HL) {      // the remainder: this lane's two row tiles side by side, the wave's piece contiguous
-                            if constexpr (HG_LO8) {
-                                *reinterpret_cast<u32x2*>(lo_ptr(tm, tn, ha, hb, g2)) = u32x2{l8[0][hb][g2], l8[1][hb][g2]};
-                            } else {
-                                const u32x2 lx = __builtin_bit_cast(u32x2, l16[0][hb][g2]), ly = __builtin_bit_cast(u32x2, l16[1][hb][g2]);
-                                *reinterpret_cast<u32x4*>(lo_ptr(tm, tn, ha, hb, g2)) = u32x4{lx[0], lx[1], ly[0], ly[1]};
-                            }
+                            *reinterpret_cast<u32x2*>(lo_ptr(tm, tn, ha, hb, g2)) = u32x2{l8[0][hb][g2], l8[1][hb][g2]};
                         }
                     }
             }

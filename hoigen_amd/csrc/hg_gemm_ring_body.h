@@ -25,15 +25,7 @@ namespace hg {
 template <int MF, int EPI, bool PH2, class SCHED>
 __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned a_bytes, const int mode, const SCHED& sc) {
 #if defined(__HIP_DEVICE_COMPILE__)   // device-only builtins (buffer resources, LDS DMA): host sees just the stub
-    // timing-experiment switches (HG_RING_MODE bits 1 locality, 2 no MFMA, 4 no epilogue, 8 no stagger, 32 no fragment
-    // reads, 64 no operand DMA) exist only in a -DHG_EXPERIMENTS build: run-time branches in the K loop cost several per
-    // cent.  (The store experiments of round 2 - junk stores trickled under the next tile, epilogue without stores - are in
-    // the history: commits "Ring2 junk-trickle experiment", "experiment: phase-shifted half tiles"; results in DESIGN.md 4.)
-#ifdef HG_EXPERIMENTS
-    const int xmode = mode;
-#else
-    constexpr int xmode = 0;
-#endif
+    // mode >> 8: the start stagger's estimated cycles per K-tile (0 = off)
     constexpr int BM = 64 * MF, BK = 64;
     constexpr int AH = MF * 4096, BH = 16384;          // bytes per A / W half-tile slot
     constexpr int STAGE = 2 * AH + 2 * BH;
@@ -76,16 +68,6 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
 #ifdef HG_STAMPS
     unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_beg = 0, t_all = 0;
 #endif
-    // HG_TRACE build: time stamps (s_memtime) of one wave around the boundary between its second and third tile: after
-    // the last K-tiles of tile 1, after its epilogue, after the first K-tiles of tile 2 (tools/gpu_ring_trace.sh)
-#ifdef HG_TRACE
-    unsigned long long ttr[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int ttn = 0;
-#define HG_TR(cond) do { if ((cond) && ttn < 16) { ttr[ttn] = __builtin_amdgcn_s_memtime(); ++ttn; } } while (0)
-#else
-#define HG_TR(cond) do {} while (0)
-#endif
-
     // (the MLP pair kernel's schedules rebuild the thread id from the wave index and v_mbcnt, behind an opaque move: threadIdx.x itself
     // would have to stay in v0 across the other body, and with v0 / v1 taken every register tuple of this body - accumulators, fragments -
     // starts at 2 (mod 4) instead of 0: the same K loop then runs 6 % slower (profiles/r06_mlp_pair.txt))
@@ -163,8 +145,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             ++ld_r;
             int tm, tn;
             item_get(ld_r, tm, tn, ld_kt, ld_ke);
-            ld_sA = (xmode & 1) ? 0 : tm * BM * p.lda * 2;     // mode 1 (timing experiment): every tile reads tile 0
-            ld_sW = (xmode & 1) ? 0 : tn * 256 * p.K * 2;
+            ld_sA = tm * BM * p.lda * 2;
+            ld_sW = tn * 256 * p.K * 2;
         }
         ld_buf = (ld_g & 1) * STAGE;
     };
@@ -176,13 +158,11 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     using P1 = std::integral_constant<int, 1>;
     auto dma_A = [&](int h, auto I) {
         constexpr int i = decltype(I)::value;
-        if (xmode & 64) return;   // timing experiment: no operand DMA
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (HG_LDS void*)(smem + ld_buf + h * AH + wave * GA * 1024), 16,
                                                  voffA[h][i], ld_sA + ld_kt * (BK * 2), i * 1024, 0);
     };
     auto dma_W = [&](int h, auto I) {
         constexpr int i = decltype(I)::value;
-        if (xmode & 64) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + ld_buf + 2 * AH + h * BH + wave * GB * 1024),
                                                  16, voffW[h][i], ld_sW + ld_kt * (BK * 2), i * 1024, 0);
     };
@@ -207,21 +187,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
 
     // Fragment registers: one A set (half 0 in P1-P2, half 1 in P3-P4) and both W halves.
     half8 xa[MF][2], wb[2][2][2];
-#ifdef HG_EXPERIMENTS
-    if (xmode & 32) {   // defined (opaque) fragment values for the no-read experiment
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int f = 0; f < MF; ++f) asm volatile("v_mov_b32 %0, 0\n v_mov_b32 %1, 0\n v_mov_b32 %2, 0\n v_mov_b32 %3, 0" : "=v"(((int*)&xa[f][ks])[0]), "=v"(((int*)&xa[f][ks])[1]), "=v"(((int*)&xa[f][ks])[2]), "=v"(((int*)&xa[f][ks])[3]));
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int g2 = 0; g2 < 2; ++g2) asm volatile("v_mov_b32 %0, 0\n v_mov_b32 %1, 0\n v_mov_b32 %2, 0\n v_mov_b32 %3, 0" : "=v"(((int*)&wb[h][g2][ks])[0]), "=v"(((int*)&wb[h][g2][ks])[1]), "=v"(((int*)&wb[h][g2][ks])[2]), "=v"(((int*)&wb[h][g2][ks])[3]));
-        }
-    }
-#endif
     auto read_A = [&](int h, int buf) {
-        if (xmode & 32) return;   // timing experiment: no fragment reads
 #pragma unroll
         for (int f = 0; f < MF; ++f)
 #pragma unroll
@@ -230,7 +196,6 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     };
     auto read_W = [&](auto H, int buf) {
         constexpr int h = decltype(H)::value;
-        if (xmode & 32) return;
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
@@ -251,7 +216,11 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     };
     auto mma = [&](auto HA, auto HB) {
         constexpr int ha = decltype(HA)::value, hb = decltype(HB)::value;
-        if (xmode & 2) {   // timing experiment: no MFMAs (operands kept live)
+        // (A branch that is never taken, kept on purpose: without it clang allocates the two-phase 256 x 256 instances' registers
+        // differently, and the MLP pair kernel, which holds this body, spills 2 VGPRs to scratch.  It is the last trace of a timing
+        // experiment that ran without MFMAs; leave it until the pair kernel no longer depends on it.)
+        constexpr int no_mfma = 0;
+        if (no_mfma) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
@@ -322,7 +291,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     barrier_raw();
     // Stagger: waves 4-7 (the second wave of every SIMD) run one barrier interval behind waves 0-3, so a
     // SIMD always has one wave in a fetch segment (LDS reads, DMA issue, waits) and one in an MFMA segment.
-    const bool late = (wave >= 4) && !(xmode & 8);
+    const bool late = wave >= 4;
     if (late) barrier_raw();
 
 #ifdef HG_STAMPS
@@ -446,19 +415,15 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             using K2 = std::integral_constant<int, 2>;
             using K3 = std::integral_constant<int, 3>;
             ph2_ktile(K1{});
-            HG_TR(r == 2);
             if constexpr (PUB) {
                 ph2_ktile(std::integral_constant<int, 4>{});
                 ph2_ktile(std::integral_constant<int, 5>{});
             }
             for (int kt = PUB ? 3 : 1; kt < klen - 2; ++kt) {
                 ph2_ktile(K0{});
-                HG_TR((r == 1 && kt >= nk - 5) || (r == 2 && kt <= 4));
             }
             ph2_ktile(K2{});
-            HG_TR(r == 1);
             ph2_ktile(K3{});
-            HG_TR(r == 1);
         } else {
         for (int kt = 0; kt < klen; ++kt, ++g) {
             const int buf = (g & 1) * STAGE;
@@ -546,17 +511,6 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
         }
         // ---------------- epilogue of tile r (the ring keeps prefetching the next tile meanwhile)
         SEG_B(7);
-        if (xmode & 4) {   // timing experiment: no epilogue
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int f = 0; f < MF; ++f)
-#pragma unroll
-                        for (int g2 = 0; g2 < 2; ++g2) asm volatile("" ::"v"(acc[a][b][f][g2]));
-            continue;
-        }
         constexpr bool F16OUT = (EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_QGELU_F16 || EPI == EPI_BIAS_RELU_F16 || LNC);
         if constexpr (F16OUT) {
             // fp16 outputs: a lane holds 4 consecutive columns (8 B) of one row.  v_permlane16_swap pairs the
@@ -732,20 +686,12 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             }
         }
         SEG_E(7);
-        HG_TR(r == 1);
         if constexpr (PUB) tm_prev = tm;
     }
     if constexpr (PUB) {      // the last tile: every wave drains its stores and meets the others before wave 0 publishes
         wait_vm<0>();
         barrier_raw();
     }
-#ifdef HG_TRACE
-    if (p.dbg && lane == 0) {
-        unsigned long long* d = p.dbg + (size_t)(blockIdx.x * 8 + wave) * 16;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) d[k] = ttr[k];
-    }
-#endif
 #ifdef HG_STAMPS
     if (p.dbg && lane == 0) {
         unsigned long long* d = p.dbg + (size_t)(blockIdx.x * 8 + wave) * 16;

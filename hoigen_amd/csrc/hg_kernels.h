@@ -33,12 +33,8 @@ enum Epilogue : int {
     EPI_SCALE_RESID_LN_F32 = 12
 };
 
-// Low half of a residual stream held as centre + hi + lo (GemmArgs::hl): 1 = bf8 (e5m2: the top byte of the fp16 remainder, rounded to
-// nearest even by v_cvt_pk_bf8_f32; 13-14 bits of x - centre, 6 bytes per element through a residual epilogue), 0 = fp16 (22 bits,
-// 8 bytes).  One of the two is built; hg_get_option("stream_lo_bits") reports which.
-#ifndef HG_LO8
-#define HG_LO8 1
-#endif
+// Low half of a residual stream held as centre + hi + lo (GemmArgs::hl): bf8 (e5m2: the top byte of the fp16 remainder, rounded to
+// nearest even by v_cvt_pk_bf8_f32; 13-14 bits of x - centre, 6 bytes per element through a residual epilogue).
 // The bf8 low half holds the remainder TIMES 2^10: the remainder of an fp16 rounding is <= 2^-11 of the element, so unscaled it sits
 // 11 binades below hi and - e5m2 has fp16's exponent range - flushes to zero once the element is below ~0.25 (a stream whose rows
 // spread by 0.02 would travel as fp16 alone); scaled it is normal wherever |x - centre| >= 2.4e-4 (hi: 6.1e-5) and cannot overflow
@@ -106,10 +102,7 @@ hipError_t launch_gemm_simple(int epi, const GemmArgs& a, hipStream_t s);
 // that run c_fc tiles (of n_cu / 8)
 bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu);
 size_t mlp_pair_ready_words(int M);
-// fin_mr (optional): the launch also does finalize_stats' work for the rows c_proj updates - mr / mu / muc / range_flag as in
-// launch_finalize_stats (mu must be proj.mu) - in its tail; null: the caller launches finalize_stats
 hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int fc_slots, int n_cu, hipStream_t s,
-                           float* fin_mr = nullptr, float* fin_mu = nullptr, float* fin_muc = nullptr, int* range_flag = nullptr,
                            int grid_short = 0);      // grid_short (fault injection: hg_api.hip option mlp_pair_fault): workgroups NOT launched
 // two 4-wave workgroups per CU, 128x256 tiles, free-running (hg_gemm_duo.hip): residual GEMMs and fp16/fp32 outputs
 bool gemm_duo_ok(int epi, const GemmArgs& a);

@@ -61,11 +61,7 @@ __device__ __forceinline__ int mlp_thread_id(int wave) {
 // number of slots leaves the other workgroups of the XCD idle (polling, asleep) until the first panels are complete: as in the
 // stand-alone kernel, 2364 tiles take ten rounds on 240 or on 256 workgroups, and the idle CUs' power buys clock for the others.
 struct MlpFcSched {
-#ifdef HG_PAIR_NOPUB      // (timing experiment: c_fc without the hand-off's atomics and K-tile kinds; only meaningful with HG_PAIR_ONLY=1)
-    static constexpr bool PUBLISH = false, CONSUME = false;
-#else
     static constexpr bool PUBLISH = true, CONSUME = false;
-#endif
     int x, cu, fcs, ch, tn, cg, wave;   // XCD, slot, slots that run c_fc, panels per chunk, column tiles, column tiles per group
     int npx, nfc, last_pc, total;       // panels of this XCD, full chunks, panels of the partial chunk, items of this slot
     int e0, n;
@@ -73,11 +69,7 @@ struct MlpFcSched {
     __device__ __forceinline__ MlpFcSched(const MlpGeom& g, int M, int N, unsigned* ready_) {
         x = g.xcd; cu = g.cu; fcs = g.fcs; ch = g.ch; wave = g.wave; ready = ready_;
         tn = N / 256;
-#ifdef HG_FC_CG      // (experiment: column tiles per group of the c_fc order)
-        cg = tn % HG_FC_CG == 0 ? HG_FC_CG : tn;
-#else
         cg = tn % 4 == 0 ? 4 : (tn % 3 == 0 ? 3 : tn);
-#endif
         const int pf = (M + 255) / 256;
         npx = pf > x ? (pf - x + MLP_NX - 1) / MLP_NX : 0;
         nfc = npx / ch;
@@ -190,26 +182,16 @@ struct MlpProjArgs {
     half_t* out3;
     int ld3;
 };
-// the launch's tail: what finalize_stats would do in a launch of its own (read from the kernel-argument segment where it is needed)
-struct MlpFinArgs {
-    float* mr;            // [M][2]; null = the tail is off (the caller launches finalize_stats)
-    float* mu;            // [M]
-    float* muc;           // [M] or null
-    int* range_flag;      // host-mapped, or null
-};
 struct MlpPairArgs {
     MlpFcArgs fc;
     MlpProjArgs proj;
-    MlpFinArgs fin;
     unsigned* ready;      // [mlp_pair_ready_words(M)] zeroed before the launch: the census words, a counter per 256-row panel (c_fc tiles
-                          // stored), a counter per 128-row half (c_proj tiles stored: the tail)
+                          // stored)
     int* err;             // host-mapped
     int ch;               // 256-row panels of an XCD per chunk
     int fc_slots;         // slots per XCD that run c_fc tiles (the others start with c_proj, i.e. wait)
     int census_off;       // byte offset in dynamic LDS of the word through which a workgroup's waves learn their slot
-    unsigned long long* dbg;   // timing experiments (-DHG_PAIR_EXP builds, HG_PAIR_DBG): s_memtime stamps per workgroup
-    int only;             // timing experiments (-DHG_PAIR_EXP builds, HG_PAIR_ONLY): 1 = the c_fc tiles alone, 2 = the c_proj tiles alone
-                          // (waiting for nothing); wrong results
+    unsigned long long* dbg;   // diagnostics (HG_STAMPS build): s_memtime stamps per workgroup, normally null
 };
 
 // Scalar registers are the scarce resource of this kernel.  With a whole GemmArgs per body as kernel arguments (2 x 47 dwords) the
@@ -259,22 +241,19 @@ __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in
     __syncthreads();
     geo.cu = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + P.census_off));
     if (geo.cu >= geo.cpx) return;      // more workgroups on this XCD than it has slots: the others own all of its work
-#ifdef HG_PAIR_EXP
+#ifdef HG_STAMPS
     unsigned long long t_stamp[4] = {__builtin_amdgcn_s_memtime(), 0, 0, 0};
 #endif
     {
         MlpFcSched sf(geo, P.fc.M, P.fc.N, P.ready + MLP_CENSUS);
         sf.e0 = 0; sf.n = sf.total;
-#ifdef HG_PAIR_EXP
-        if (P.only == 2) sf.n = 0;
-#endif
         if (sf.n > 0) {
             GemmArgs a{};
             a.A = P.fc.A; a.W = P.fc.W; a.bias = P.fc.bias; a.out = P.fc.out; a.cs = P.fc.cs; a.mr = P.fc.mr;
             a.lda = P.fc.lda; a.ldc = P.fc.ldc; a.M = P.fc.M; a.N = P.fc.N; a.K = P.fc.K;
             gemm_ring_body<4, EPI_LN_BIAS_QGELU_F16, true>(a, P.fc.a_bytes, 3000 << 8, sf);
         }
-#ifdef HG_PAIR_EXP
+#ifdef HG_STAMPS
         t_stamp[1] = __builtin_amdgcn_s_memtime();
         t_stamp[3] = (unsigned long long)sf.n;
 #endif
@@ -283,10 +262,6 @@ __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in
         const MlpProjArgs Q = load_kernarg<MlpProjArgs>((unsigned)__builtin_offsetof(MlpPairArgs, proj));      // (here, not at the kernel's entry)
         MlpProjSched sp(geo, Q.M, Q.N, Q.K, P.ready + MLP_CENSUS, P.err);
         sp.e0 = 0; sp.n = sp.total;
-#ifdef HG_PAIR_EXP
-        if (P.only == 2) sp.target = 0u;
-        if (P.only == 1) sp.n = 0;
-#endif
         if (sp.n > 0) {
             GemmArgs a{};
             a.A = global_bits(Q.A); a.W = global_bits(Q.W); a.bias = global_bits(Q.bias); a.out = global_bits(Q.out); a.mu = global_bits(Q.mu);
@@ -298,39 +273,7 @@ __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in
             barrier_raw();      // every wave has left the c_fc body (its LDS image is dead)
             gemm_ring2_body<EPI_RESID_LN_F32, HL, GS>(a, a.N / 256, Q.a_bytes, 0, sp);
         }
-        // ---- tail: the LayerNorm statistics of the updated rows (what finalize_stats does in a launch of its own).  The column tiles of
-        // a 128-row half ran on workgroups of THIS XCD; each of them, with its tile's partial sums in the XCD's L2 (every wave has drained
-        // its stores), adds 1 to the half's counter, and the one whose add comes last combines the rows' partial sums - the same
-        // function, the same bits.  Nothing here touches the K loops: a workgroup does it once, behind its last tile.
-        const MlpFinArgs F = load_kernarg<MlpFinArgs>((unsigned)__builtin_offsetof(MlpPairArgs, fin));
-        if (F.mr != nullptr) {
-            wait_vm<0>();
-            __syncthreads();
-            const int tid = mlp_thread_id(geo.wave);      // (not threadIdx.x: see thread_id())
-            const int M = Q.M, nt = Q.stats_ld, tn = Q.N / 256;
-            unsigned* const done = P.ready + MLP_CENSUS + (M + 255) / 256;
-            int* const slot_word = reinterpret_cast<int*>(smem + P.census_off);
-            float* const stats = global_bits(Q.stats);
-            float* const f_mr = global_bits(F.mr);
-            float* const f_mu = global_bits(F.mu);
-            float* const f_muc = global_bits(F.muc);
-            // all of this workgroup's counter adds at once (lane e of wave 0: tile e), their answers through LDS: one atomic round trip
-            int* const lastw = reinterpret_cast<int*>(smem);      // (the ring's first bytes: the bodies are done)
-            if (tid < sp.n) {
-                int tm, t2;
-                sp.tile(tid, tm, t2);
-                lastw[tid] = (int)__hip_atomic_fetch_add(done + tm, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tn - 1 ? tm : -1;
-            }
-            __syncthreads();
-            (void)slot_word;
-            for (int e = 0; e < sp.n; ++e) {
-                const int tm = lastw[e];      // the row half this workgroup finalises, or -1
-                const int m = tm * 128 + (tid & 127);
-                if (tm >= 0 && tid < 128 && m < M)
-                    finalize_stats_row<true>(stats + (size_t)m * nt * 2, f_mr, f_mu, f_muc, m, nt, 64, 0, global_bits(F.range_flag));
-            }
-        }
-#ifdef HG_PAIR_EXP
+#ifdef HG_STAMPS
         t_stamp[2] = __builtin_amdgcn_s_memtime();
         if (P.dbg && threadIdx.x == 0) {
             unsigned long long* d = P.dbg + (size_t)blockIdx.x * 8;
@@ -365,20 +308,30 @@ static hipError_t launch_pair_t(const MlpPairArgs& a, int grid, int lds, hipStre
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-#ifdef HG_PAIR_COOP      // (experiment: a cooperative launch - the runtime's co-residency guarantee - and what it costs per launch)
-    MlpPairArgs a2 = a;
-    void* args[] = {&a2};
-    return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&mlp_pair_kernel<HL, GS>), dim3(grid), dim3(512), args, (unsigned)lds, s);
-#else
     hipLaunchKernelGGL((mlp_pair_kernel<HL, GS>), dim3(grid), dim3(512), lds, s, a);
     return hipGetLastError();
-#endif
 }
 
-size_t mlp_pair_ready_words(int M) { return (size_t)MLP_CENSUS + (size_t)((M + 255) / 256) + (size_t)((M + 127) / 128); }
+static hipError_t launch_pair_hl(const MlpPairArgs& a, int hl, bool gs, int grid, int lds, hipStream_t s) {
+    if (gs) {
+        switch (hl) {
+            case 2: return launch_pair_t<2, true>(a, grid, lds, s);
+            case 3: return launch_pair_t<3, true>(a, grid, lds, s);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (hl) {
+        case 0: return launch_pair_t<0>(a, grid, lds, s);
+        case 2: return launch_pair_t<2>(a, grid, lds, s);
+        case 3: return launch_pair_t<3>(a, grid, lds, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+size_t mlp_pair_ready_words(int M) { return (size_t)MLP_CENSUS + (size_t)((M + 255) / 256); }
 
 hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj_in, unsigned* ready, int* err, int ch, int fc_slots, int n_cu,
-                           hipStream_t s, float* fin_mr, float* fin_mu, float* fin_muc, int* range_flag, int grid_short) {
+                           hipStream_t s, int grid_short) {
     GemmArgs proj = proj_in;
     if (!proj.ld2) proj.ld2 = proj.ldc;
     if (!mlp_pair_ok(fc, proj, n_cu) || !ready || !err || proj.ld2 % 8) return hipErrorInvalidValue;
@@ -389,30 +342,22 @@ hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj_in, unsigned
     a.proj = MlpProjArgs{proj.A, proj.W, proj.bias, (float*)proj.out, proj.mu, proj.out2, proj.stats, proj.lo, proj.muc,
                          proj.lda, proj.ldc, proj.ld2, proj.M, proj.N, proj.K, proj.stats_ld,
                          (unsigned)((size_t)((proj.M + 127) / 128) * 128 * proj.lda * 2), proj.gamma, proj.out3, proj.ld3};
-    a.fin = MlpFinArgs{fin_mr, fin_mu, fin_muc, range_flag};
-    if (fin_mr && (!fin_mu || fin_mu != proj.mu)) return hipErrorInvalidValue;      // (the centre the copy is written with IS the previous mean)
     a.ready = ready; a.err = err;
     a.ch = ch < 1 ? 1 : (ch > 64 ? 64 : ch);
     a.fc_slots = fc_slots < 1 ? 1 : fc_slots;
-#ifdef HG_PAIR_EXP
-    static const int only_env = []() { const char* e = getenv("HG_PAIR_ONLY"); return e ? atoi(e) : 0; }();
-    a.only = only_env;
-#endif
     const int lds_fc = 2 * (2 * 4 * 4096 + 2 * 16384) + fc.N * 4 * 2 + 256 * 8;
     const int lds_proj = 3 * 49152 + proj.N * 4 * (proj.gamma ? 2 : 1);
     a.census_off = lds_fc > lds_proj ? lds_fc : lds_proj;      // (behind both bodies' LDS images: never overwritten)
     const int lds = a.census_off + 16;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int grid = n_cu - (grid_short > 0 && grid_short < MLP_NX ? grid_short : 0);
-#ifdef HG_PAIR_EXP
-    static int dbg_left = []() { const char* e = getenv("HG_PAIR_DBG"); return e ? atoi(e) : 0; }();
-    if (dbg_left > 0 && proj.hl == 2) {
-        --dbg_left;
+#ifdef HG_STAMPS
+    if (getenv("HG_STAMPS")) {
         unsigned long long* d = nullptr;
         if (hipMalloc(&d, (size_t)grid * 64) != hipSuccess) return hipErrorOutOfMemory;
         hipMemsetAsync(d, 0, (size_t)grid * 64, s);
         a.dbg = d;
-        hipError_t e = launch_pair_t<2>(a, grid, lds, s);
+        hipError_t e = launch_pair_hl(a, proj.hl, proj.gamma != nullptr, grid, lds, s);
         hipStreamSynchronize(s);
         unsigned long long* h = (unsigned long long*)malloc((size_t)grid * 64);
         hipMemcpy(h, d, (size_t)grid * 64, hipMemcpyDeviceToHost);
@@ -434,19 +379,7 @@ hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj_in, unsigned
         return e;
     }
 #endif
-    if (proj.gamma) {
-        switch (proj.hl) {
-            case 2: return launch_pair_t<2, true>(a, grid, lds, s);
-            case 3: return launch_pair_t<3, true>(a, grid, lds, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (proj.hl) {
-        case 0: return launch_pair_t<0>(a, grid, lds, s);
-        case 2: return launch_pair_t<2>(a, grid, lds, s);
-        case 3: return launch_pair_t<3>(a, grid, lds, s);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_pair_hl(a, proj.hl, proj.gamma != nullptr, grid, lds, s);
 }
 
 }  // namespace hg

@@ -159,13 +159,8 @@ hipError_t launch_qkv_attn(const QkvAttnArgs& a_in, hipStream_t s) {
     if (grid < 8) grid = n_cu_d[dev_i];
     if (n_items < grid) grid = n_items;            // (not a multiple of 8: plain dealing)
     if (!a.a_bytes) a.a_bytes = (unsigned)((size_t)(((size_t)a.n_seq * a.L + 255) / 256) * 256 * a.lda * 2);
-#ifdef HG_EXPERIMENTS
-    static const int mode = []() { const char* e = getenv("HG_QA_MODE"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int mode = 0;
-#endif
-    if ((a.K / 64) % 3 == 0) hipLaunchKernelGGL(qkv_attn_kernel, dim3(grid), dim3(512), QA_LDS, s, a, mode);
-    else hipLaunchKernelGGL(qkv_attn_kernel_k1, dim3(grid), dim3(512), QA_LDS, s, a, mode);      // (K = 64 (3 m + 1): the adapter folded in)
+    if ((a.K / 64) % 3 == 0) hipLaunchKernelGGL(qkv_attn_kernel, dim3(grid), dim3(512), QA_LDS, s, a);
+    else hipLaunchKernelGGL(qkv_attn_kernel_k1, dim3(grid), dim3(512), QA_LDS, s, a);      // (K = 64 (3 m + 1): the adapter folded in)
     return hipGetLastError();
 }
 

@@ -1,14 +1,7 @@
 // The fused in_proj + attention kernel (hg_qkv_attn.hip), included once per K-tile schedule: QA_KERNEL = the kernel's name,
 // SQ_NKMOD = (K / 64) % 3 of the instance (0: K = D, the product kernel of variant A; 1: K = D + 64, variant C's in_proj on [x16 | e]).
-__global__ __launch_bounds__(512, 2) void QA_KERNEL(const QkvAttnArgs p, const int mode) {
+__global__ __launch_bounds__(512, 2) void QA_KERNEL(const QkvAttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    // timing-experiment switches (HG_QA_MODE bits: 1 no attention phases, 2 no MFMA in the K loop, 4 no epilogue at all,
-    // 8 no operand DMA; wrong results) exist only in a -DHG_EXPERIMENTS build
-#ifdef HG_EXPERIMENTS
-    const int xmode = mode;
-#else
-    constexpr int xmode = 0;
-#endif
     constexpr int RB = QA_RB, NCB = QA_NCB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -102,12 +95,7 @@ __global__ __launch_bounds__(512, 2) void QA_KERNEL(const QkvAttnArgs p, const i
         issue_A(seq_n * p.L, 0, SQ_A0);
 #endif
 
-        if (xmode & 4) {
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int c = 0; c < NCB; ++c) asm volatile("" ::"v"(acc[rb][c]));
-        } else {
+        {
             // ---------------- epilogue: LayerNorm fold, fp16 (the expressions of hg_gemm_ring.hip's EPI_LN_BIAS_F16 epilogue)
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -170,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void QA_KERNEL(const QkvAttnArgs p, const i
             // S^T MFMAs of tile kt+1 and the K fragments of tile kt+2 are issued before the softmax of tile kt, the V fragments
             // of tile kt before its softmax arithmetic (sequence length is fixed here: 7 tiles, the last one masked and half empty).
             auto attend = [&](const int head, const bool pre_store_wait) {
-                if ((xmode & 1) || wave >= 7) {
+                if (wave >= 7) {
                     if (pre_store_wait) wait_vm<0>();
                     return;
                 }

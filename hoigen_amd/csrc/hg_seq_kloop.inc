@@ -1,5 +1,5 @@
 // K loop of the sequence-tile GEMMs (hg_seq_dev.h), expanded inside a kernel body.  Expects in scope: `smem` (THE extern
-// __shared__ array), `lane`, `wave`, `nk` (K / 64, a multiple of 3), `xmode` (experiment bits or constexpr 0), and the macros
+// __shared__ array), `lane`, `wave`, `nk` (K / 64, a multiple of 3), and the macros
 // SQ_A_PTR / SQ_A_BYTES / SQ_LDA (fp16 activations [rows, lda], bytes readable), SQ_W_PTR / SQ_W_BYTES (packed weight).
 // Defines: seq_prologue(row0, pn), stage_base(st), and what hg_seq_kloop_run.inc (the loop itself, expanded inside the item loop) needs.
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(SQ_A_PTR), 0, (SQ_A_BYTES), 0x00020000);
@@ -19,7 +19,6 @@
     // all pieces of one K-tile of the rows row0 .. row0 + 207 (26 pieces: waves 0 and 1 issue a fourth - an operation more
     // only makes the counted waits below stricter, never looser)
     auto issue_A = [&](int row0, int kt, int sbase) {
-        if (xmode & 8) return;
         const int soff = (row0 * sq_lda + kt * 64) * 2;
         const int ln = lane_now();
         const int voffA = ((wave * 8 + (ln >> 3)) * sq_lda + (((ln & 7) ^ ((ln >> 4) & 3) ^ ((wave & 1) << 2)) << 3)) * 2;
@@ -36,7 +35,6 @@
     char* wring = smem + wave * SQ_WSLOT;
     // fragment slot (ks, c) of K-tile kt of panel pn: Wp[pn][2 kt + ks][wave][c][lane][8]
     auto issue_W = [&](int pn, int kt, const int slot) {
-        if (xmode & 8) return;
         const int ks = slot / SQ_NCB, c = slot % SQ_NCB;
         const int soff = ((((pn * 2 * nk + kt * 2 + ks) * 8 + wave) * SQ_NCB) + c) * 1024;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(wring + slot * 1024), 16, lane_now() * 16, soff, 0, 0);

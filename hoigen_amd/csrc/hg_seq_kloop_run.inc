@@ -27,7 +27,6 @@
         const int row0 = sq_row0, pn = sq_pn, row0_n = sq_row0_n, pn_n = sq_pn_n;
         constexpr int RB = SQ_RB, NCB = SQ_NCB;
         issue_A(row0, 1, stage_base(1));
-        const bool sq_half = wave >= 4;
         constexpr int AR = SQ_AR, NPOS = 2 * RB, PUB = NPOS - (AR - 1);
         half8 wc[NCB], wn[NCB], afr[AR];
         int af_off[2], w_off;      // lane parts of the fragment addresses, recomputed per K-tile (hg_seq_kloop.inc: lane_now)
@@ -55,11 +54,9 @@
 #pragma unroll
                 for (int c = 0; c < NCB; ++c) wc[c] = read_W(c);
             }
-            // Priority of the MFMA stream (SQ_PRIO: 0 both waves of a SIMD raised, as measured best; 1 none; 2 only the younger
-            // wave w + 4 raised; taking turns position by position was measured 15-20 % slower: profiles/r04_qkv_attn.txt)
-            if (!(xmode & 2)) {
-                if (SQ_PRIO == 0 || (SQ_PRIO == 2 && sq_half)) __builtin_amdgcn_s_setprio(1);
-            }
+            // Priority of the MFMA stream: both waves of a SIMD raised, as measured best against none and against only the younger wave
+            // w + 4 raised; taking turns position by position was measured 15-20 % slower: profiles/r04_qkv_attn.txt
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
@@ -92,14 +89,9 @@
 #pragma unroll
                         for (int c = 0; c < NCB; ++c) wn[c] = read_W((1 - ks) * NCB + c);
                     }
-                    if (xmode & 2) {
 #pragma unroll
-                        for (int c = 0; c < NCB; ++c) asm volatile("" ::"v"(afr[(S0 + pos) % AR]), "v"(wc[c]));
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < NCB; ++c)
-                            acc[rb][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[c], afr[(S0 + pos) % AR], acc[rb][c], 0, 0, 0);
-                    }
+                    for (int c = 0; c < NCB; ++c)
+                        acc[rb][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[c], afr[(S0 + pos) % AR], acc[rb][c], 0, 0, 0);
                     if (rb == 0) {
                         // the step's W fragments are in registers (the MFMAs above waited for them): refill their slots
                         asm volatile("" ::"v"(wc[0]), "v"(wc[1]), "v"(wc[2]) : "memory");

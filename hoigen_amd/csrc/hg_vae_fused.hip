@@ -35,9 +35,6 @@
 //           wave-private scratch, E1's half straight into the registers x leaves);
 //   G       the generator on those fragments; epilogue: + bias, fp32 output.
 // Generator-only calls (hg_generator) run pass G alone with z read like x.
-//   M       (mode 3) the MLP of a transformer block of width 512 (the CLIP text tower: clipnet/model.py:173-177,187): the same pass with
-//           QuickGELU in place of relu and the residual update as its epilogue:  x += W_proj quickgelu(W_fc h + b_fc) + b_proj,  h = the
-//           fp16 LayerNorm output (row-major), x the fp32 stream in place.  c_fc's [rows, 2048] activation never reaches HBM.
 //
 // Arithmetic: fp16 operands (x, h, z, g, weights), fp32 accumulate and fp32 bias / relu / reparameterisation - the same roundings as the
 // GEMM path of hg_api.hip (which stores h and g as fp16 in HBM), in a different summation order.
@@ -56,22 +53,15 @@ namespace {
 constexpr int VF_DIM = 512;                  // feature width (x, mean, log_var, z, bias)
 constexpr int VF_KS = VF_DIM / 16;           // k-steps of a row = B fragments per wave
 constexpr int VF_ROWS = 128;                 // rows per item (4 waves x 32)
-#ifndef VF_STAGE_KB
-#define VF_STAGE_KB 16
-#endif
-constexpr int VF_STAGE = VF_STAGE_KB * 1024; // one ring stage = 16 (32) fragments: one s_barrier per stage
-constexpr int VF_NS = 128 / VF_STAGE_KB;     // ring slots (128 KiB)
+constexpr int VF_STAGE = 16 * 1024;         // one ring stage = 16 fragments: one s_barrier per stage
+constexpr int VF_NS = 128 * 1024 / VF_STAGE; // ring slots (128 KiB)
 constexpr int VF_WPIECES = VF_STAGE / 4096;  // 1-KiB pieces of a stage per wave
 constexpr int VF_ITER_BYTES = 64 * 1024;     // one iteration = 64 fragments = 4 stages = half the ring
 constexpr int VF_RING = 0;
 constexpr int VF_TAB = VF_NS * VF_STAGE;     // first-layer bias of the pass: (nb + 2) x 32 floats
 constexpr int VF_MAX_NB = 128;               // hidden <= 4096
 constexpr int VF_LDS = VF_TAB + (VF_MAX_NB + 2) * 32 * 4;
-#ifdef VF_AHEAD_OVERRIDE
-constexpr int VF_AHEAD = VF_AHEAD_OVERRIDE;
-#else
 constexpr int VF_AHEAD = 4;                  // weight fragments read ahead of the MFMA that uses them
-#endif
 static_assert(VF_LDS <= 160 * 1024, "LDS budget");
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -100,15 +90,15 @@ struct VaeFusedDev {
     const float* b2g;        // [512]
     half_t* zpark;           // [items][4 waves][16 fragments][64 lanes][8] fp16
     int R, nbe, nbg;         // hidden blocks of 32
-    int mode;                // 0 Encoder + Generator, 1 Encoder, 2 Generator, 3 MLP block (QuickGELU, bias = the fp32 stream, updated in place)
+    int mode;                // 0 Encoder + Generator, 1 Encoder, 2 Generator
     int stages_per_item;
     int n_items;
     unsigned long long* dbg;
 };
 
-// MSET: the passes this instantiation holds - 0 = Encoder (+ Generator): modes 0 and 1, 2 = Generator only, 3 = MLP block.  One kernel
-// with every pass kind carried the Encoder epilogues' 36 spilled dwords (and their 68 bytes of private segment per lane) into the
-// Generator-only and MLP launches, which are the ones the default dispatch uses.
+// MSET: the passes this instantiation holds - 0 = Encoder (+ Generator): modes 0 and 1, 2 = Generator only.  One kernel with every
+// pass kind carried the Encoder epilogues' 36 spilled dwords (and their 68 bytes of private segment per lane) into the Generator-only
+// launches, which are the ones the default dispatch uses.
 template <int MSET>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void vae_fused_kernel(const VaeFusedDev p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -124,13 +114,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
     };
 
-    // timing-experiment switches (compile-time: -DVF_XMODE=bits; 1 no operand DMA, 2 every stage fetched from stream offset 0, 4 no
-    // MFMA, 8 no fragment reads; wrong results) - run-time switches would put a branch at every MFMA
-#ifdef VF_XMODE
-    constexpr int xmode = VF_XMODE;
-#else
-    constexpr int xmode = 0;
-#endif
 #ifdef HG_STAMPS
     unsigned long long tk_vm = 0, tk_bar = 0, tk_b = 0, tk_all0 = __builtin_amdgcn_s_memtime(), tk_epi = 0, tk_x = 0;
 #define VF_STAMP_B() do { tk_b = __builtin_amdgcn_s_memtime(); } while (0)
@@ -149,16 +132,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     int d_off = wave * (VF_STAGE / 4);
     int d_lds = VF_RING + wave * (VF_STAGE / 4);
     auto issue_stage = [&]() {
-        if (!(xmode & 1)) {
-            const int lane16 = lane_now() * 16;
-            const int off = (xmode & 2) ? wave * (VF_STAGE / 4) : d_off;
+        const int lane16 = lane_now() * 16;
+        const int off = d_off;
 #pragma unroll
-            for (int g4 = 0; g4 < VF_WPIECES / 4; ++g4) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 1024, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 2048, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 3072, 0);
-            }
+        for (int g4 = 0; g4 < VF_WPIECES / 4; ++g4) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 1024, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 2048, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (HG_LDS void*)(smem + d_lds + g4 * 4096), 16, lane16, off + g4 * 4096, 3072, 0);
         }
         d_off += VF_STAGE;
         if (d_off >= stream_bytes) d_off -= stream_bytes;
@@ -168,7 +149,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // is past the stage two back: refill its slot
     auto boundary = [&]() {
         VF_STAMP_B();
-        if (!(xmode & 1)) wait_vm<(VF_NS - 3) * VF_WPIECES>();
+        wait_vm<(VF_NS - 3) * VF_WPIECES>();
         VF_STAMP_E(tk_vm);
         VF_STAMP_B();
         barrier_raw();
@@ -237,24 +218,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int pos = 0; pos < 64; ++pos) {
                 const int q = pos + VF_AHEAD;
                 if ((q & (VF_STAGE / 1024 - 1)) == 0) boundary();
-                if (!(xmode & 8)) wr[q & 7] = q < 64 ? rd(base_cur, q) : rd(base_nxt, q - 64);
+                wr[q & 7] = q < 64 ? rd(base_cur, q) : rd(base_nxt, q - 64);
                 if (pos < 32) {
                     // layer 1 of block t: H^T += W0frag x x^T frag
                     // (inline asm: the VGPR form.  The builtin takes the AGPR form for every MFMA of the kernel, and the 256 AGPRs are
                     // the sixteen output blocks: with these accumulators there as well the allocator parks two output blocks in
                     // VGPRs and moves them in and out around each of their MFMAs - 4 x (16 writes, s_nop 11, 16 reads) per iteration)
-                    if (xmode & 4) asm volatile("" ::"v"(wr[pos & 7]));
-                    else if (pos == 0)
+                    if (pos == 0)
                         asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(hacc[C]) : "v"(wr[pos & 7]), "v"(bf[pos]), "v"(bias16));
                     else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(hacc[C]) : "v"(wr[pos & 7]), "v"(bf[pos]));
-                    // under it: block t - 1 -> fp16.  QuickGELU (KIND 3): one element every other MFMA gap (two quarter-rate
-                    // transcendentals each); relu: fp16 pairs (positions 2..9), then a packed fp16 max (10..17)
-                    if constexpr (KIND == 3) {
-                        if ((pos & 1) == 0) {
-                            const int r = pos >> 1;
-                            hf[r >> 3][r & 7] = (half_t)quick_gelu_r(hacc[1 - C][r]);
-                        }
-                    } else if (pos >= 2 && pos < 10) {
+                    // under it: block t - 1 -> fp16 and relu: fp16 pairs (positions 2..9), then a packed fp16 max (10..17)
+                    if (pos >= 2 && pos < 10) {
                         const int r = 2 * (pos - 2);
                         hp2[pos - 2] = __builtin_convertvector(f32x2t{hacc[1 - C][r], hacc[1 - C][r + 1]}, half2t);
                     } else if (pos >= 10 && pos < 18) {
@@ -267,8 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 } else {
                     // layer 2 of block t - 1: out^T[ob] += W2frag x H^T frag (k-step s2)
                     const int s2 = (pos - 32) >> 4, ob = (pos - 32) & 15;
-                    if (xmode & 4) asm volatile("" ::"v"(wr[pos & 7]));
-                    else oacc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[pos & 7], hf[s2], oacc[ob], 0, 0, 0);
+                    oacc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[pos & 7], hf[s2], oacc[ob], 0, 0, 0);
                 }
                 // (pins the order: left alone the scheduler gathers the 64 ds_reads in front of the MFMAs - 256 registers of
                 // fragments in flight, the x fragments spilled)
@@ -304,9 +277,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     for (int g = 0; g < 4; ++g) {
                         const int cb = (32 * ob + 8 * g) * 4;
                         const f32x4 b2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, boff + cb, 0, 0));
-                        f32x4 v = f32x4{oacc[ob][4 * g], oacc[ob][4 * g + 1], oacc[ob][4 * g + 2], oacc[ob][4 * g + 3]} + b2;
-                        if constexpr (KIND == 3)      // the residual update: x += (acc + bias), this lane's own four columns in place
-                            v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsO, voff + cb, 0, 0)) + v;
+                        const f32x4 v = f32x4{oacc[ob][4 * g], oacc[ob][4 * g + 1], oacc[ob][4 * g + 2], oacc[ob][4 * g + 3]} + b2;
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO, voff + cb, 0, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -373,7 +344,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
     using K2 = std::integral_constant<int, 2>;
-    using K3 = std::integral_constant<int, 3>;
 
     for (item = blockIdx.x; item < p.n_items; item += gridDim.x) {
         // ---- the wave's rows as B fragments: element j of lane (n, h) in k-step s = x[row n][vf_kidx(s, h, j)]  (rows beyond R: zeros)
@@ -406,8 +376,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
         VF_STAMP_E(tk_x);
-        if constexpr (MSET == 3) run_pass(K3{}, p.nbg, p.b0g);
-        else if constexpr (MSET == 2) run_pass(K2{}, p.nbg, p.b0g);
+        if constexpr (MSET == 2) run_pass(K2{}, p.nbg, p.b0g);
         else {
             run_pass(K0{}, p.nbe, p.b0e);
             run_pass(K1{}, p.nbe, p.b0e);
@@ -512,11 +481,11 @@ hipError_t launch_vae_fused(const VaeFusedArgs& a, hipStream_t s) {
 }
 
 static hipError_t launch_vae_fused_slice(const VaeFusedArgs& a, hipStream_t s) {
-    if (a.R <= 0 || (!a.x && !(a.mode >= 2 && a.x16)) || !a.wp || a.mode < 0 || a.mode > 3) return hipErrorInvalidValue;
+    if (a.R <= 0 || (!a.x && !(a.mode == 2 && a.x16)) || !a.wp || a.mode < 0 || a.mode > 2) return hipErrorInvalidValue;
     if (a.mode < 2 && (!a.eps || !a.b0e || !a.bml || !a.zpark)) return hipErrorInvalidValue;
     if (a.mode != 1 && (!a.b0g || !a.b2g || !a.bias)) return hipErrorInvalidValue;
     VaeFusedDev d{};
-    d.x = a.x; d.x16 = a.mode >= 2 ? a.x16 : nullptr; d.eps = a.eps; d.mean = a.mean; d.logvar = a.logvar; d.z = a.z; d.bias = a.bias;
+    d.x = a.x; d.x16 = a.mode == 2 ? a.x16 : nullptr; d.eps = a.eps; d.mean = a.mean; d.logvar = a.logvar; d.z = a.z; d.bias = a.bias;
     d.b0e = a.b0e; d.bml = a.bml; d.b0g = a.b0g; d.b2g = a.b2g; d.zpark = a.zpark;
     d.R = a.R; d.nbe = a.eh / 32; d.nbg = a.gh / 32;
     const size_t enc_bytes = 2 * vae_fused_pass_bytes(a.eh), gen_bytes = vae_fused_pass_bytes(a.gh);
@@ -525,8 +494,7 @@ static hipError_t launch_vae_fused_slice(const VaeFusedArgs& a, hipStream_t s) {
     d.mode = a.mode;
     if (a.mode == 0) bytes = enc_bytes + gen_bytes;
     else if (a.mode == 1) bytes = enc_bytes;
-    else if (a.mode == 2) { d.wp = a.wp + (a.has_enc ? enc_bytes / 2 : 0); bytes = gen_bytes; }
-    else bytes = gen_bytes;      // mode 3: wp is the one pass of this block's MLP
+    else { d.wp = a.wp + (a.has_enc ? enc_bytes / 2 : 0); bytes = gen_bytes; }
     if (bytes >= (1ull << 31) || a.R > (1 << 20)) return hipErrorInvalidValue;      // (32-bit byte offsets into the [R, 512] fp32 tensors)
     d.stages_per_item = (int)(bytes / VF_STAGE);
     d.n_items = (a.R + VF_ROWS - 1) / VF_ROWS;
@@ -535,8 +503,7 @@ static hipError_t launch_vae_fused_slice(const VaeFusedArgs& a, hipStream_t s) {
     const int dev_i = current_device_index();
     if (!attr_set_d[dev_i]) {
         n_cu_d[dev_i] = 256;
-        for (const void* f : {reinterpret_cast<const void*>(&vae_fused_kernel<0>), reinterpret_cast<const void*>(&vae_fused_kernel<2>),
-                              reinterpret_cast<const void*>(&vae_fused_kernel<3>)}) {
+        for (const void* f : {reinterpret_cast<const void*>(&vae_fused_kernel<0>), reinterpret_cast<const void*>(&vae_fused_kernel<2>)}) {
             hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
         }
@@ -553,8 +520,7 @@ static hipError_t launch_vae_fused_slice(const VaeFusedArgs& a, hipStream_t s) {
     d.dbg = dbg;
     if (dbg) (void)hipMemsetAsync(dbg, 0, (size_t)1024 * 4 * 8 * 8, s);
 #endif
-    if (a.mode == 3) hipLaunchKernelGGL(vae_fused_kernel<3>, dim3(grid), dim3(256), VF_LDS, s, d);
-    else if (a.mode == 2) hipLaunchKernelGGL(vae_fused_kernel<2>, dim3(grid), dim3(256), VF_LDS, s, d);
+    if (a.mode == 2) hipLaunchKernelGGL(vae_fused_kernel<2>, dim3(grid), dim3(256), VF_LDS, s, d);
     else hipLaunchKernelGGL(vae_fused_kernel<0>, dim3(grid), dim3(256), VF_LDS, s, d);
 #ifdef HG_STAMPS
     if (dbg && getenv("HG_VF_STAMPS")) {

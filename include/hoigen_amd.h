@@ -241,8 +241,8 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *   "adapter_fold"    [HG_ADAPTER_FOLD]    1: adapter update folded into the block's own GEMMs; 0: separate up_proj GEMM
  *   "stream_hilo"     [HG_STREAM_HILO]     1: between the LayerNorm-folded blocks of variant A, of the text tower (and of variant C when every
  *                      block's adapter is folded into its GEMMs) the residual stream is held as
- *                      centre + hi + lo (the centred fp16 copy the GEMMs read + its remainder as bf8; fp16 in a -DHG_LO8=0 build:
- *                      read-only option "stream_lo_bits" = 8 / 16); 0: as fp32 throughout
+ *                      centre + hi + lo (the centred fp16 copy the GEMMs read + its remainder as bf8: read-only option
+ *                      "stream_lo_bits" = 8); 0: as fp32 throughout
  *   "qkv_attn"        [HG_QKV_ATTN]        1: in the LayerNorm-folded blocks of the vision tower in_proj and attention run as ONE kernel
  *                      (hoigen_amd/csrc/hg_qkv_attn.hip: q, k, v stay in LDS; 192 < tokens <= 208, i.e. ViT-B/16); 0: two kernels with the
  *                      qkv matrix in HBM between them; 2: the one kernel wherever the shapes allow (1 also asks that the last round
@@ -264,18 +264,13 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      up to 4096) for the leading rows that fill whole rounds of its 128-row work items over the CUs, the GEMM path for
  *                      the rest (and for calls too small to fill 70 % of one round); 2: the one kernel for every row; 0: GEMM path only.
  *                      Same fp16 operand roundings on both paths; results differ by fp32 summation order.
- *   "mlp_fused"       [HG_MLP_FUSED]       blocks of width 512 (the text tower, separate-LayerNorm path): 1 = c_fc -> QuickGELU -> c_proj ->
- *                      residual as ONE kernel (hg_vae_fused.hip mode 3: the [rows, 2048] activation stays on chip) for the leading rows that
- *                      fill whole rounds of 128-row items, 2 = every row, 0 (default: measured a tie) = the two GEMMs
  *   "mlp_pair"        [HG_MLP_PAIR]        1 (default): in the LayerNorm-folded blocks of both towers (variant A; every form of the residual stream and
  *                      of the LayerNorm weight) c_fc -> QuickGELU -> c_proj run as ONE persistent launch (hoigen_amd/csrc/hg_mlp_pair.hip: the c_fc
  *                      tiles publish per-256-row-panel ready counters, the c_proj tiles of a panel - on the same XCD by its hardware id -
  *                      wait for them; results do not depend on workgroup placement; a wait that times out makes the NEXT call return
  *                      HG_ERR_HIP; devices with 8 x 32 CUs, otherwise the two launches run; the launch's workgroups wait for each other: the library
  *                      orders such launches across the streams of one process; PROCESSES that share a GPU and both run it can hold each other up
- *                      until that bound - set 0 there); 2: as 1, and the last workgroup of a row half also
- *                      combines that half's LayerNorm partial sums (no finalize_stats launch between the blocks; measured slower in the
- *                      vision tower, a tie in the text tower); 0: two launches.  Bit-identical results in all three.
+ *                      until that bound - set 0 there); 0: two launches.  Bit-identical results in both.
  *   "mlp_pair_chunk"  [HG_MLP_PAIR_CHUNK]  1 .. 64: 256-row panels of an XCD per chunk of that launch's c_fc tile order (default 32: the XCD's whole list
  *                      column group by column group, as in the stand-alone kernel; speed only)
  *   "mlp_pair_fc_slots" [HG_MLP_PAIR_FC_SLOTS] 1 .. 64: workgroups per XCD (of 32) that run c_fc tiles in that launch (default 32); the others start with

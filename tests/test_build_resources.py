@@ -41,9 +41,7 @@ def test_no_kernel_spills_registers_or_uses_scratch():
     assert len(kernels) >= 60, f"only {len(kernels)} kernels seen: the remarks were not parsed"
     # SGPR "spills" are v_writelane moves into spare VGPR lanes, not memory: tolerated only in the two fp32 fallback kernels of
     # the adapter (weights held in scalar registers by design: hg_adapter.hip), which no batch-256 path runs
-    sgpr_ok = ("adapter_kv_kernel", "adapter_decoder_kernel", "qkv_attn_kernel", "vae_fused_kernelILi0E", "mlp_pair_kernelILi2ELb1E")
-    # (mlp_pair_kernel<2, gamma>, hg_mlp_pair.hip - the text tower's instance: two GEMM bodies in one kernel, three scalars are parked in
-    # VGPR lanes around its tail; what must not happen inside the bodies is pinned by test_mlp_pair_kernel_codegen below)
+    sgpr_ok = ("adapter_kv_kernel", "adapter_decoder_kernel", "qkv_attn_kernel", "vae_fused_kernelILi0E")
     # (qkv_attn_kernel, hg_qkv_attn.hip, runs its K loop on 156 accumulator + 48 fragment registers and its attention phases beside
     # 78 registers of parked fp16 results: it used to park a handful of per-item values in scratch across the K loop; values the
     # allocator would keep live across the loop - a hoisted lane id of __shfl_xor, a hoisted `wave < 2`, a constant pair, the zero high
@@ -51,8 +49,8 @@ def test_no_kernel_spills_registers_or_uses_scratch():
     # vae_fused_kernel<0> (hg_vae_fused.hip: the instance that holds the Encoder passes, options vae_fused = 2 only) keeps 256 accumulator
     # + 128 operand registers through its pass loops; at the joins between its three pass epilogues the allocator parks one accumulator
     # block in scratch for the duration of an epilogue (three per 128-row item of ~0.3 ms; 30 dwords).  Its pass LOOPS must be free
-    # of scratch and vmcnt(0): test_vae_fused_pass_loops_are_scratch_free.  The Generator-only and MLP-block instances (<2>, <3>: what the
-    # default dispatch launches) spill nothing and fall under the rule for every other kernel.
+    # of scratch and vmcnt(0): test_vae_fused_four_pass_loops_are_scratch_free.  The Generator-only instance (<2>: what the default dispatch
+    # launches) spills nothing and falls under the rule for every other kernel.
     few_ok = {"vae_fused_kernelILi0E": 40}
     def tolerated(r):
         f, n, k, v = r
@@ -90,8 +88,8 @@ def test_fused_kernel_k_loop_is_scratch_free():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_vae_fused_pass_loops_are_scratch_free():
-    """The pass loops of the three vae_fused_kernel instances (two iterations of 64 MFMAs per trip) keep six ring stages of LDS-DMA in flight behind
+def test_vae_fused_four_pass_loops_are_scratch_free():
+    """The pass loops of the two vae_fused_kernel instances (two iterations of 64 MFMAs per trip) keep six ring stages of LDS-DMA in flight behind
     counted s_waitcnt vmcnt(20): a scratch reload inside them waits for vmcnt(0) and drains the ring once per iteration (measured:
     4 750 instead of 2 100 cycles per iteration).  Every innermost loop that holds MFMAs must hold exactly 128 of them, 8 barriers,
     no scratch access, no vmcnt(0), and no AGPR<->VGPR copies (the layer-1 accumulators are VGPR-form inline asm for that reason)."""
@@ -110,7 +108,7 @@ def test_vae_fused_pass_loops_are_scratch_free():
     with_128 = [(a, b) for a, b in loops if sum("v_mfma" in x for x in lines[a:b + 1]) == 128]
     # (the item loop of a one-pass instance holds the same 128 MFMAs as its pass loop: innermost loops only)
     inner = [(a, b) for a, b in with_128 if not any((a2, b2) != (a, b) and a <= a2 and b2 <= b for a2, b2 in with_128)]
-    assert len(inner) == 5, f"expected five pass loops (instance <0>: Encoder x 2 + Generator, <2>: Generator, <3>: MLP block), found {len(inner)}"
+    assert len(inner) == 4, f"expected four pass loops (instance <0>: Encoder x 2 + Generator, <2>: Generator), found {len(inner)}"
     for a, b in inner:
         body = lines[a:b + 1]
         assert sum("s_barrier" in x for x in body) == 8

@@ -266,10 +266,10 @@ def test_residual_stream_as_centre_hi_lo(ctx, M, N, K):
     err = ((hl[0] - f32[0]).abs() / spread).max().item()
     print(f"\\nhi/lo stream vs fp32 stream after 5 updates: max |diff| / row spread = {err:.2e}")
     bits = C.c_int32(0)
-    assert _lib.lib().hg_get_option(ctx, b"stream_lo_bits", C.byref(bits)) == 0
-    # lo as fp16: 22 bits of x - centre.  lo as bf8 (the default build, HG_LO8): the remainder (<= 2^-11 of the element) keeps two
-    # mantissa bits, <= 2^-14 of the element per update, and the updates' errors add: 5 x 6.1e-5 of the row spread at most
-    assert err <= (4e-6 if bits.value == 16 else 5 * 2.0 ** -14 * 1.02)
+    assert _lib.lib().hg_get_option(ctx, b"stream_lo_bits", C.byref(bits)) == 0 and bits.value == 8
+    # lo as bf8: the remainder (<= 2^-11 of the element) keeps two mantissa bits, <= 2^-14 of the element per update, and the
+    # updates' errors add: 5 x 6.1e-5 of the row spread at most
+    assert err <= 5 * 2.0 ** -14 * 1.02
     assert (hl[1] - f32[1]).abs().max().item() <= 1e-5 * scale                      # mean
     assert ((hl[3][:, 1] - f32[3][:, 1]).abs() / f32[3][:, 1]).max().item() <= 1e-4   # rstd
     assert (hl[2] - f32[2]).abs().max().item() <= 2e-3 * spread.max().item()          # last centred copy (fp16 grid)

@@ -81,10 +81,9 @@ def test_fused_in_proj_attention_is_bit_identical_inside_encode_image(fullA):
         fullA.visual.set_option("qkv_attn", 1)
         fullA.visual.set_option("last_block_row0", 1)
 
-def test_mlp_pair_one_launch_is_bit_identical_inside_encode_image(fullA):
+def test_mlp_pair_launch_is_bit_identical_inside_encode_image(fullA):
     """Option mlp_pair (hg_mlp_pair.hip: c_fc -> QuickGELU -> c_proj of a block as ONE persistent launch, the c_fc tiles publishing
-    per-row-panel ready counters their c_proj tiles wait for; with value 2 the LayerNorm statistics of the updated rows are combined in the
-    launch's tail by the last of a row half's column-tile workgroups): the same tiles, K loops, epilogues and statistics in another order and on other
+    per-row-panel ready counters their c_proj tiles wait for): the same tiles, K loops, epilogues and statistics in another order and on other
     workgroups, so encode_image gives the SAME bits as the two launches + finalize_stats - at batch 256, 171 (ragged last panels) and 40 (fewer
     c_proj tiles than two rounds), with several chunk sizes of the c_fc tile order and with 30 or 24 of an XCD's 32 workgroups running
     c_fc tiles (the others really wait for their first panels), every row of the last block or the class rows only; repeated launches
@@ -100,13 +99,13 @@ def test_mlp_pair_one_launch_is_bit_identical_inside_encode_image(fullA):
             for n in (256, 171, 40):
                 fullA.visual.set_option("mlp_pair", 0)
                 want = fullA.encode_image(crops[:n])
-                for pair, chunk, slots in ((1, 32, 32), (2, 32, 32), (1, 8, 30), (1, 3, 24), (2, 25, 30)):
-                    fullA.visual.set_option("mlp_pair", pair)      # (1: finalize_stats in a launch of its own; 2: its work in the pair launch's tail)
+                fullA.visual.set_option("mlp_pair", 1)
+                for chunk, slots in ((32, 32), (8, 30), (3, 24)):
                     fullA.visual.set_option("mlp_pair_chunk", chunk)
                     fullA.visual.set_option("mlp_pair_fc_slots", slots)
                     for rep in range(3 if n == 256 else 1):
                         got = fullA.encode_image(crops[:n])
-                        assert torch.equal(got, want), (row0, n, pair, chunk, slots, rep, float((got - want).abs().max()))
+                        assert torch.equal(got, want), (row0, n, chunk, slots, rep, float((got - want).abs().max()))
         got = fullA.encode_image(crops)[60:64].float().cpu().numpy()
         assert np.linalg.norm(got - ref) / np.linalg.norm(ref) < 1e-3
     finally:
@@ -212,7 +211,7 @@ def test_mlp_pair_launches_from_two_streams_do_not_wait_for_each_other(fullA, g0
     torch.cuda.synchronize()
 
 
-def test_mlp_pair_in_the_text_tower_is_bit_identical(fullA):
+def test_mlp_pair_launch_in_the_text_tower_is_bit_identical(fullA):
     """The same one-launch MLP in the text tower (width 512: c_fc 8 column tiles, c_proj 2; the next LayerNorm's weight rides in the
     activation copy - the kernel's gamma instances; 46 200 rows at 77 tokens: a ragged last panel with one 128-row half) and in the
     truncated tower the generation pipeline runs (13-16 tokens): encode_text equals the two launches bit for bit, for all three
@@ -232,10 +231,9 @@ def test_mlp_pair_in_the_text_tower_is_bit_identical(fullA):
                 fullA.truncate_text = trunc
                 fullA.set_option("mlp_pair", 0)
                 want = fullA.encode_text(ids)
-                for pair in (1, 2):
-                    fullA.set_option("mlp_pair", pair)
-                    got = fullA.encode_text(ids)
-                    assert torch.equal(got, want), (fold, trunc, pair, float((got.float() - want.float()).abs().max()))
+                fullA.set_option("mlp_pair", 1)
+                got = fullA.encode_text(ids)
+                assert torch.equal(got, want), (fold, trunc, float((got.float() - want.float()).abs().max()))
     finally:
         fullA.set_option("mlp_pair", 1)
         fullA.set_option("text_ln_fold", prev_fold)
@@ -321,7 +319,7 @@ def test_variant_c_600_crops_with_priors_equals_chunks():
     assert not torch.equal(g3, glob[256:260])
 
 
-def test_text_700_prompts_equals_chunks(fullA, g0):
+def test_text_pass_boundary_prompts_equal_chunks(fullA, g0):
     """encode_text across a pass boundary of the text tower (65 536 rows per pass, equal passes): 1 000 prompts x 77 tokens = two passes
     of 500 (the 600 HOI + 81 object + 117 verb + 202 CoOp prompts); truncated to their 13-16 tokens they are one pass.  A prompt's bits
     depend on the PATH its call takes, never on its neighbours: with the LayerNorms folded (text_ln_fold 1, the default, and 2) every
@@ -343,35 +341,24 @@ def test_text_700_prompts_equals_chunks(fullA, g0):
             sel = torch.cat([sel, torch.tensor([longest], device=ids.device)])
         return fullA.encode_text(ids[sel])[: hi - lo]
 
-    # (option mlp_fused lives in the separate-LayerNorm path: a row's MLP runs as the one kernel or as two GEMMs depending on where it
-    # falls in its pass - each path is held to bit-equality on its own, the default against both)
     wholes = {}
     try:
-        for fold, mlp in ((0, 0), (0, 2), (0, 1), (1, 0), (2, 0)):
+        for fold in (0, 1, 2):
             fullA.set_option("text_ln_fold", fold)
-            fullA.set_option("mlp_fused", mlp)
             for trunc in (False, True):
                 fullA.truncate_text = trunc
-                whole = wholes[fold, mlp, trunc] = fullA.encode_text(ids)
-                if (fold, mlp) == (0, 1):
-                    for other in (0, 2):
-                        ref = wholes[0, other, trunc].float()
-                        err = float((whole.float() - ref).norm() / ref.norm())
-                        assert err < 9e-4, f"mlp_fused=1 vs {other}, truncate={trunc}: {err:.2e}"      # (two realisations of 12 blocks of fp16 roundings, each ~6.5e-4 from the reference)
-                    continue
+                whole = wholes[fold, trunc] = fullA.encode_text(ids)
                 for lo, hi in ((0, 500), (500, 1000), (480, 530), (0, 640)):      # (50 prompts x 13 tokens = 650 rows: the folded path)
-                    assert torch.equal(piece(lo, hi, trunc), whole[lo:hi]), f"prompts [{lo},{hi}) truncate={trunc} text_ln_fold={fold} mlp_fused={mlp}"
+                    assert torch.equal(piece(lo, hi, trunc), whole[lo:hi]), f"prompts [{lo},{hi}) truncate={trunc} text_ln_fold={fold}"
                 small = piece(490, 510, trunc)      # 20 prompts: 273 rows truncated (the separate kernels whatever the option), 1 540 at 77 tokens
                 if fold == 0 or not trunc:
-                    assert torch.equal(small, whole[490:510]), f"prompts [490,510) truncate={trunc} text_ln_fold={fold} mlp_fused={mlp}"
+                    assert torch.equal(small, whole[490:510]), f"prompts [490,510) truncate={trunc} text_ln_fold={fold}"
                 else:
-                    assert torch.equal(small, wholes[0, 0, trunc][490:510]), "a call below 512 rows must take the separate-LayerNorm path"
+                    assert torch.equal(small, wholes[0, trunc][490:510]), "a call below 512 rows must take the separate-LayerNorm path"
                     err = float((small.float() - whole[490:510].float()).norm() / whole[490:510].float().norm())
                     assert err < 1e-3, f"small call vs folded whole call: {err:.2e}"
-        assert not torch.equal(wholes[0, 0, False], wholes[0, 2, False]), "option mlp_fused did not change the executed path"
-        assert not torch.equal(wholes[0, 0, False], wholes[1, 0, False]) and not torch.equal(wholes[1, 0, False], wholes[2, 0, False])
+        assert not torch.equal(wholes[0, False], wholes[1, False]) and not torch.equal(wholes[1, False], wholes[2, False])
     finally:
-        fullA.set_option("mlp_fused", 0)
         fullA.set_option("text_ln_fold", 1)
         fullA.truncate_text = True
 

@@ -1,5 +1,5 @@
 """Per-kernel means of the headline step (256 crops, every row) under the library / options the environment selects (HG_LIB_PATH,
-HG_MLP_PAIR, HG_MLP_PAIR_LAG, HG_PAIR_ONLY ...): hipEvent pairs around every GEMM / attention launch (hg_profile), 6 steps; then the
+HG_MLP_PAIR, HG_MLP_PAIR_CHUNK, HG_MLP_PAIR_FC_SLOTS ...): hipEvent pairs around every GEMM / attention launch (hg_profile), 6 steps; then the
 step time without events over 20 steps.  One line."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

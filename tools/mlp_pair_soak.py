@@ -20,7 +20,7 @@ for crops in (256, 171, 40):
     x = torch.randn(crops, 3, 224, 224, device=d, generator=g)
     m.visual.set_option("mlp_pair", 0)
     want = m.encode_image(x).clone()
-    for pair, ch, slots in ((1, 32, 32), (2, 32, 32), (1, 8, 30), (1, 3, 24), (1, 1, 32), (2, 25, 28)):
+    for pair, ch, slots in ((1, 32, 32), (1, 8, 30), (1, 3, 24), (1, 1, 32), (1, 25, 28)):
         m.visual.set_option("mlp_pair", pair); m.visual.set_option("mlp_pair_chunk", ch); m.visual.set_option("mlp_pair_fc_slots", slots)
         mism = 0
         for i in range(N):
@@ -40,7 +40,7 @@ for prompts, L in ((600, 77), (81, 77), (600, 16)):
     tok[torch.arange(prompts, device=d), eot] = 49407
     m.set_option("mlp_pair", 0)
     want = m.encode_text(tok).clone()
-    for pair in (1, 2):
+    for pair in (1,):
         m.set_option("mlp_pair", pair)
         mism = 0
         for i in range(N):

@@ -1,6 +1,6 @@
 """Diagnostics: the fused in_proj + attention kernel (hg_qkv_attn.hip) against the two kernels it replaces, ViT-B/16 shape
 (256 sequences x 197 tokens x 12 heads), hipEvent pairs around every launch (hg_profile_*), alternating, random operands.
-GSZ="6 3 2 1": XCD group sizes to time.  In an -DHG_EXPERIMENTS build HG_QA_MODE knocks parts out (hg_qkv_attn.hip)."""
+GSZ="6 3 2 1": XCD group sizes to time."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

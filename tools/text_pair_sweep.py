@@ -15,7 +15,7 @@ for i, r in enumerate(rows): ids[i, :len(r)] = r
 ids = torch.from_numpy(ids).to(d)
 m.truncate_text = False
 cfgs = [tuple(int(v) for v in t.split(":")) for t in (sys.argv[1] if len(sys.argv) > 1 else
-        "0:32:32 1:32:32 1:32:30 1:32:28 1:8:32 1:4:32 1:2:32 1:8:30 1:4:28 2:8:32").split()]
+        "0:32:32 1:32:32 1:32:30 1:32:28 1:8:32 1:4:32 1:2:32 1:8:30 1:4:28").split()]
 def timed(n=20):
     for _ in range(3): m.encode_text(ids)
     torch.cuda.synchronize()

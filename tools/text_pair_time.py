@@ -1,4 +1,4 @@
-"""encode_text over the 600 HICO prompts (77 tokens and truncated) with option mlp_pair 0 / 1 / 2, alternating, ms per call."""
+"""encode_text over the 600 HICO prompts (77 tokens and truncated) with option mlp_pair 0 / 1, alternating, ms per call."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -24,7 +24,7 @@ for rnd in range(3):
     for trunc in (False, True):
         m.truncate_text = trunc
         out = []
-        for pair in (0, 1, 2):
+        for pair in (0, 1):
             m.set_option("mlp_pair", pair)
             out.append(f"mlp_pair={pair}: {timed():.3f} ms")
         print(f"round {rnd} {'truncated' if trunc else '77 tokens'}: " + " | ".join(out), flush=True)

@@ -1,4 +1,4 @@
-"""Print the per-dispatch durations of one transformer layer from the newest rocprofv3 kernel trace under $OUT/pm (tools/gpu_modes.sh)."""
+"""Print the per-dispatch durations of one transformer layer from the newest rocprofv3 kernel trace under $OUT/pm."""
 import csv, glob, os, sys
 OUT = os.environ.get("OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "out")
 f = sorted(glob.glob(os.path.join(OUT, "pm", "*", "*_kernel_trace.csv")),

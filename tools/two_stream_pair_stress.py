@@ -1,5 +1,5 @@
 """Stress of the MLP pair launch from two streams of one process: encode_image on one stream, encode_text on another (two contexts), 40
-rounds per batch size; with HG_LIB_PATH=ab/nogate.so (-DHG_NO_PAIR_GATE build of hg_api.hip) the same without the library's cross-stream gate."""
+rounds per batch size."""
 import os, sys, time, json
 sys.path.insert(0, "/root/repo")
 import torch
