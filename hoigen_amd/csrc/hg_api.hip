@@ -662,11 +662,15 @@ bool ln_fuse_ok(hg_ctx* c, int M, int D) {
 // `pre_w` / `pre_b` (vision tower): the LayerNorm in front of the first block (ln_pre) has NOT been applied yet; it runs
 // here, fused with the first block's folding statistics when folding is on - and, with `pre_pos` / `pre_cls`, with the class
 // rows and the positional embedding the patch GEMM left out (clipnet/model.py:223-225 in one pass over the rows)
+// `trace` ([layers + 1] entries `trace_stride` floats apart): the stream entering block 0, then after every block - row 0 of every
+// sequence, or with `trace_all` (the stream test hooks) all M rows; the last entry of a row0_out block holds its n_seq rows densely
 int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, int D, int heads, bool causal,
                hipStream_t s, float* trace, int trace_stride, const AdapterCall* ac, bool ln_fold,
                const float** row0_out = nullptr, const int32_t* sel = nullptr, const float* pre_w = nullptr,
-               const float* pre_b = nullptr, const float* pre_pos = nullptr, const float* pre_cls = nullptr, bool gamma_act = false) {
+               const float* pre_b = nullptr, const float* pre_pos = nullptr, const float* pre_cls = nullptr, bool gamma_act = false,
+               bool trace_all = false) {
     const int M = n_seq * L;
+    const int tr_rows = trace_all ? M : n_seq, tr_stride = trace_all ? 1 : L;      // rows a trace entry holds, their stride in the stream
     const bool row0_env = c->opt_row0 != 0;
     if (row0_out) *row0_out = nullptr;
     if (c->pair_err && *(volatile int32_t*)c->pair_err) {
@@ -763,7 +767,7 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
     } else if (pre_w) {
         HG_HIP(launch_layernorm_f32(x, pre_w, pre_b, x, M, D, s, pre_pos, pre_cls, L));
     }
-    if (pre_w && trace) HG_HIP(launch_copy_rows(x, trace, n_seq, L, D, s));
+    if (trace) HG_HIP(launch_copy_rows(x, trace, tr_rows, tr_stride, D, s));      // (x is the fp32 stream here: the folding kernels only read it)
     // Residual stream as centre + hi + lo between the LayerNorm-emitting residual GEMMs (GemmArgs::hl; option stream_hilo):
     // hi IS the centred fp16 copy those GEMMs write anyway, lo its remainder as bf8 - 6 instead of 10
     // bytes per element through every such epilogue and a third fewer partial-line stores.  The first of them reads the fp32 stream (ln_pre wrote it),
@@ -978,8 +982,9 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
         }
         if (trace) {
             // (after finalize_stats muc is the centre the stream's hi / lo halves were written with)
-            if (x_is_hilo) HG_HIP(launch_copy_rows_hilo(h, (const half_t*)c->xlo.p, muc, trace + (size_t)(i + 1) * trace_stride, n_seq, L, D, s));
-            else HG_HIP(launch_copy_rows(x, trace + (size_t)(i + 1) * trace_stride, n_seq, L, D, s));
+            float* tr = trace + (size_t)(i + 1) * trace_stride;
+            if (x_is_hilo) HG_HIP(launch_copy_rows_hilo(h, (const half_t*)c->xlo.p, muc, tr, tr_rows, tr_stride, D, s));
+            else HG_HIP(launch_copy_rows(x, tr, tr_rows, tr_stride, D, s));
         }
     }
     return HG_OK;
@@ -1854,8 +1859,9 @@ int hg_cache_logits(hg_ctx* c, int slot, const float* feats, int R, float* out, 
 }
 
 // ---- image tower ------------------------------------------------------------------------------------------
+// `trace_all` (hg_test_image_stream): every row of the stream into `trace`, one entry of B * L rows per block - one chunk only
 static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors, const uint8_t* mask, int B, int N,
-                             float* out, float* out_local, float* trace, bool variant_c, hipStream_t s) {
+                             float* out, float* out_local, float* trace, bool variant_c, hipStream_t s, bool trace_all = false) {
     if (!c) return HG_ERR_INVALID;
     Vit& v = c->vit;
     if (!v.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vit has not been called");
@@ -1883,8 +1889,8 @@ static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors
         // class rows, positional embedding and ln_pre are one pass over the rows (run_blocks): the GEMM only scatters
         g.M = Bc * G; g.N = D; g.K = v.Kp; g.pos = nullptr; g.G = G; g.L = L;
         HG_HIP(gemm(c, EPI_PATCH_F32, g, s));
-        float* tr = trace ? trace + (size_t)b0 * D : nullptr;      // (row 0 of the trace = after ln_pre: copied inside run_blocks)
-        const int tstride = B * D;
+        float* tr = trace ? trace + (trace_all ? 0 : (size_t)b0 * D) : nullptr;      // (row 0 of the trace = after ln_pre: copied inside run_blocks)
+        const int tstride = trace_all ? M * D : B * D;
         AdapterCall ac;
         ac.enabled = variant_c;
         ac.priors = priors ? priors + (size_t)b0 * N * 64 : nullptr;
@@ -1892,7 +1898,7 @@ static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors
         ac.N = N;
         const float* row0 = nullptr;      // dense class-token rows when the last block ran on them only
         rc = run_blocks(c, v.blocks, Bc, L, D, v.heads, false, s, tr, tstride, &ac, true, variant_c ? nullptr : &row0, nullptr,
-                        v.lnpre_w, v.lnpre_b, v.pos, v.cls);
+                        v.lnpre_w, v.lnpre_b, v.pos, v.cls, false, trace_all);
         if (rc) return rc;
         half_t* h16 = (half_t*)c->head16.p;
         if (!variant_c) {
@@ -1920,6 +1926,15 @@ int hg_encode_image(hg_ctx* c, const float* x_nchw, int B, float* out, void* str
 }
 int hg_encode_image_trace(hg_ctx* c, const float* x_nchw, int B, float* out, float* trace, void* stream) {
     return encode_image_impl(c, x_nchw, nullptr, nullptr, B, 0, out, nullptr, trace, false, (hipStream_t)stream);
+}
+int hg_test_image_stream(hg_ctx* c, const float* x_nchw, int B, float* out, float* trace, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!c->vit.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vit has not been called");
+    for (const AdapterW& a : c->vit.adapters)
+        if (a.present) return fail(c, HG_ERR_INVALID, "hg_test_image_stream: adapters are loaded (under a trace the tower leaves the hi / lo "
+                                                      "stream, a path production does not run)");
+    if (B < 1 || B > c->max_chunk_img || !trace) return fail(c, HG_ERR_INVALID, "hg_test_image_stream: B must be 1..one chunk, trace != NULL");
+    return encode_image_impl(c, x_nchw, nullptr, nullptr, B, 0, out, nullptr, trace, false, (hipStream_t)stream, true);
 }
 int hg_encode_image_prior(hg_ctx* c, const float* x_nchw, const float* priors, const uint8_t* mask, int B, int N,
                           float* out_global, float* out_local_nchw, void* stream) {
@@ -1956,15 +1971,16 @@ static int text_chunk_prompts(const hg_ctx* c, int n_prompts, int Leff) {
     return (int)((n_prompts + passes - 1) / passes);
 }
 
-static int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out, hipStream_t s) {
+// `trace` (hg_test_text_stream): every row of the stream, [layers + 1][Tc * Leff][D]
+static int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out, hipStream_t s, float* trace = nullptr) {
     Text& t = c->text;
     const int D = t.D, E = t.E;
     // option text_ln_fold: 1 (default) folds the LayerNorms with gamma riding in the ACTIVATION copy (6.2e-4 against the reference's
     // fixture, closer than the separate kernels' 6.5e-4, 5.35 -> 5.15 ms for 600 x 77 tokens); 2 folds gamma into the weights (4.8 ms,
     // 7.6e-4, worst prompt 9.6e-4 of the 1e-3 budget); 0 runs the separate kernels
     const float* rows = nullptr;      // dense EOT rows when the last block ran on them only
-    int rc = run_blocks(c, t.blocks, Tc, Leff, D, t.heads, true, s, nullptr, 0, nullptr, c->opt_text_ln_fold != 0, &rows, eot, nullptr,
-                        nullptr, nullptr, nullptr, c->opt_text_ln_fold == 1);
+    int rc = run_blocks(c, t.blocks, Tc, Leff, D, t.heads, true, s, trace, Tc * Leff * D, nullptr, c->opt_text_ln_fold != 0, &rows, eot,
+                        nullptr, nullptr, nullptr, nullptr, c->opt_text_ln_fold == 1, trace != nullptr);
     if (rc) return rc;
     half_t* h16 = (half_t*)c->head16.p;
     // ln_final, select the EOT row, @ text_projection (clipnet/model.py:346-350); LN is row-wise so
@@ -1977,7 +1993,7 @@ static int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out
     return HG_OK;
 }
 
-int hg_encode_text_ids(hg_ctx* c, const int32_t* ids, int T, int L, float* out, int trunc, void* stream) {
+static int encode_text_ids_impl(hg_ctx* c, const int32_t* ids, int T, int L, float* out, int trunc, float* trace, void* stream) {
     if (!c) return HG_ERR_INVALID;
     Text& t = c->text;
     if (!t.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_text has not been called");
@@ -1989,6 +2005,7 @@ int hg_encode_text_ids(hg_ctx* c, const int32_t* ids, int T, int L, float* out, 
     const int Leff = (trunc > 0 && trunc < L) ? trunc : L;
     if (Leff < L && c->eot_flag_dev) HG_HIP(hipMemsetAsync(c->eot_flag_dev, 0, 4, s));
     const int chunk = text_chunk_prompts(c, T, Leff);
+    if (trace && chunk < T) return fail(c, HG_ERR_INVALID, "hg_test_text_stream: the call is longer than one pass of the text tower");
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int Tc = (T - t0 < chunk) ? T - t0 : chunk;
         int rc = ensure_tower_ws(c, Tc * Leff, t.D);
@@ -2000,11 +2017,18 @@ int hg_encode_text_ids(hg_ctx* c, const int32_t* ids, int T, int L, float* out, 
         HG_HIP(launch_eot_argmax(ids + (size_t)t0 * L, Tc, L, eot, nullptr, s));
         if (Leff < L) HG_HIP(launch_clamp_eot(eot, Tc, Leff, eot, c->eot_flag, s, c->eot_flag_dev));
         HG_HIP(launch_embed_tokens(ids + (size_t)t0 * L, L, t.tok, t.pos, (float*)c->x.p, Tc, Leff, t.D, t.vocab, s));
-        rc = text_tail(c, Tc, Leff, eot, out + (size_t)t0 * t.E, s);
+        rc = text_tail(c, Tc, Leff, eot, out + (size_t)t0 * t.E, s, trace);
         if (rc) return rc;
     }
     if (Leff < L) HG_HIP(launch_poison_if_flag(out, (size_t)T * t.E, c->eot_flag_dev, s));
     return HG_OK;
+}
+int hg_encode_text_ids(hg_ctx* c, const int32_t* ids, int T, int L, float* out, int trunc, void* stream) {
+    return encode_text_ids_impl(c, ids, T, L, out, trunc, nullptr, stream);
+}
+int hg_test_text_stream(hg_ctx* c, const int32_t* ids, int T, int L, int trunc, float* out, float* trace, void* stream) {
+    if (c && (T < 1 || !trace)) return fail(c, HG_ERR_INVALID, "hg_test_text_stream: T must be >= 1, trace != NULL");
+    return encode_text_ids_impl(c, ids, T, L, out, trunc, trace, stream);
 }
 
 int hg_encode_text_embeds(hg_ctx* c, const float* prompts, const int32_t* eot_idx, int R, int L, float* out,

@@ -430,6 +430,21 @@ class VisionTransformer(nn.Module):
                                                          _stream_ptr(x.device)), "hg_encode_image_trace")
         return out, tr
 
+    @torch.no_grad()
+    def forward_stream_trace(self, x: torch.Tensor):
+        """Test hook: (embedding [B,E], every row of the residual stream after ln_pre and every block [layers+1,B*L,D]).
+        With option last_block_row0 = 1 the last entry holds the B class rows in its first B rows.  One chunk (256 crops) at most."""
+        _require_cuda(x, "image batch")
+        h = self._sync(x.device)
+        xf = x.detach().to(torch.float32).contiguous()
+        B = xf.shape[0]
+        L = (self.input_resolution // self.patch_size) ** 2 + 1
+        out = torch.empty(B, self.output_dim, device=x.device, dtype=torch.float32)
+        tr = torch.empty(self.transformer.layers + 1, B * L, self.transformer.width, device=x.device, dtype=torch.float32)
+        self._ctx.check(_lib.lib().hg_test_image_stream(h, xf.data_ptr(), B, out.data_ptr(), tr.data_ptr(),
+                                                        _stream_ptr(x.device)), "hg_test_image_stream")
+        return out, tr
+
 
 class TokenEmbedding(nn.Module):
     """nn.Embedding stand-in (``clip_model.token_embedding(ids)``, main_coop_vae.py:85,111)."""
@@ -586,6 +601,24 @@ class CLIP(nn.Module):
             self._trunc_memo = (None, 0, 0, 0)      # a stale truncation length must not survive the error it caused
         self._ctx.check(rc, "hg_encode_text_ids")
         return out.to(self.dtype)
+
+    @torch.no_grad()
+    def encode_text_stream_trace(self, text: torch.Tensor, truncate: bool = True):
+        """Test hook: (encode_text's fp32 output [T,E], every row of the residual stream after the embedding and every block
+        [layers+1,T*Leff,D]); Leff = max(EOT)+1 with `truncate`, else the ids' length.  With option last_block_row0 = 1 the last entry
+        holds the T EOT rows in its first T rows.  One pass of the text tower at most."""
+        dev = self.positional_embedding.device
+        _require_cuda(self.positional_embedding, "CLIP model")
+        h = self._sync_text(dev)
+        T, L = text.shape
+        trunc = int(text.argmax(dim=-1).max().item()) + 1 if truncate else 0
+        leff = trunc if 0 < trunc < L else L
+        ids = text.detach().to(device=dev, dtype=torch.int32).contiguous()
+        out = torch.empty(T, self.text_projection.shape[1], device=dev, dtype=torch.float32)
+        tr = torch.empty(self.transformer.layers + 1, T * leff, self.transformer.width, device=dev, dtype=torch.float32)
+        self._ctx.check(_lib.lib().hg_test_text_stream(h, ids.data_ptr(), T, L, trunc, out.data_ptr(), tr.data_ptr(),
+                                                       _stream_ptr(dev)), "hg_test_text_stream")
+        return out, tr
 
     @_inference_only
     @torch.no_grad()

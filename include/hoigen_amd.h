@@ -344,6 +344,16 @@ int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t*
 int hg_test_qkv_attn(hg_ctx*, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
                      int L, int heads, int fused, float* out, void* stream);
 
+/* Test hooks for the whole residual stream of a tower (every row, not only the rows that reach an output): as
+ * hg_encode_image / hg_encode_text_ids (same options, `out` bit for bit the same), additionally copying the stream into
+ * trace [(layers+1), rows, D] fp32 on the device, rows = B * tokens (image) or T * Leff (text; Leff = trunc when
+ * 0 < trunc < L, else L).  Entry 0 is the stream entering block 0 (after ln_pre / after token + positional embedding),
+ * entry i the stream after block i-1 as block i reads it (centre + hi + lo summed when it is held so).  With option
+ * last_block_row0 = 1 the last entry holds the B / T rows that block ran on densely, in its first rows.  HG_ERR_INVALID
+ * for a vision context with adapters loaded and for calls longer than one chunk (256 crops) / one text pass. */
+int hg_test_image_stream(hg_ctx*, const float* x_nchw, int B, float* out, float* trace, void* stream);
+int hg_test_text_stream(hg_ctx*, const int32_t* ids, int T, int L, int trunc, float* out, float* trace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

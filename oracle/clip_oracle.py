@@ -91,7 +91,7 @@ def attention(x: Tensor, sd: Dict[str, Tensor], pre: str, heads: int, causal: bo
     qkv = linear(x, sd[pre + "attn.in_proj_weight"], sd[pre + "attn.in_proj_bias"])
     q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
     out = torch.empty_like(x)
-    tri = torch.triu(torch.ones(L, L, dtype=torch.bool), diagonal=1) if causal else None
+    tri = torch.triu(torch.ones(L, L, dtype=torch.bool, device=x.device), diagonal=1) if causal else None
     for h in range(heads):
         sl = slice(h * hd, (h + 1) * hd)
         s = (q[..., sl] @ k[..., sl].transpose(1, 2)) * (hd ** -0.5)          # [B,L,L]
