@@ -194,7 +194,7 @@ struct DecW16 {
 
 static constexpr int XP = 136;      // halfs per row of a wave's activation buffer (64 or 128 features + pad)
 static constexpr int KP = 72;       // halfs per row of K [key][64]
-static constexpr int NKMAX = 224;   // keys: 14 tiles of 16 (L <= 224)
+static constexpr int NKMAX = ADAPTER_MAX_L;   // keys: 14 tiles of 16 (L <= 224)
 static constexpr int VP = NKMAX + 8;   // halfs per row of V^T [feature][key slot]
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));

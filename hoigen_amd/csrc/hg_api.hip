@@ -80,6 +80,8 @@ struct Vit {
     float *cls = nullptr, *pos = nullptr, *lnpre_w = nullptr, *lnpre_b = nullptr, *lnpost_w = nullptr,
           *lnpost_b = nullptr;
     half_t* w_projT = nullptr;
+    half_t* w_projT_lo = nullptr;     // variant C of towers beyond the adapters' 224 tokens: 2^11 x the fp16 remainder of proj (hg_load_vit)
+    float* proj_lo_scale = nullptr;   // [E] 2^-11, and [E] zeros behind it (the second pass's bias)
     std::vector<BlockW> blocks;
     std::vector<AdapterW> adapters;
     std::vector<void*> owned, owned_adapters;
@@ -1422,7 +1424,7 @@ int hg_test_gemm_hilo(hg_ctx* c, const float* a, const float* w, const float* bi
 
 int hg_test_attention(hg_ctx* c, const float* qkv, const float* q0, const int32_t* sel, int n_seq, int L, int heads,
                       int causal, float* out, void* stream) {
-    if (!c || !qkv || !out || n_seq <= 0 || L < 1 || L > 224 || heads < 1) return HG_ERR_INVALID;
+    if (!c || !qkv || !out || n_seq <= 0 || L < 1 || L > ATTN_LONG_MAX_L || heads < 1) return HG_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     HG_ON_DEVICE(c);
     const int D = heads * 64;
@@ -1439,7 +1441,9 @@ int hg_test_attention(hg_ctx* c, const float* qkv, const float* q0, const int32_
         HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)n_seq * D, s));
     } else {
         // (causal bit 1: the one-workgroup-per-item launch for L <= 32 instead of four items per workgroup - same bits: tests)
+        ProfScope ps(c, s, HG_PROF_ATTENTION, n_seq, L, heads);      // the kernel alone, as attention() above (tools/bench_vitl336.py)
         HG_HIP(launch_attention((const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, (causal & 1) != 0, s, 0, !(causal & 2)));
+        ps.finish();
         HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, M * D, s));
     }
     return HG_OK;
@@ -1575,15 +1579,44 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
     if (D <= 0 || D % 128 || w->heads * 64 != D)
         return fail(c, HG_ERR_INVALID, "vision width must be a multiple of 128 with heads = width/64 (got %d, %d)", D,
                     w->heads);
-    if (p <= 0 || p % 8 || w->input_resolution % p || (3 * p * p) % 64)
-        return fail(c, HG_ERR_INVALID, "unsupported patch size %d / resolution %d", p, w->input_resolution);
+    if (p <= 0 || w->input_resolution <= 0 || w->input_resolution % p)
+        return fail(c, HG_ERR_INVALID, "unsupported patch size %d / resolution %d (the resolution must be a multiple of the patch size)", p,
+                    w->input_resolution);
     if (w->output_dim <= 0 || w->output_dim % 128)
         return fail(c, HG_ERR_INVALID, "output_dim must be a multiple of 128 (got %d)", w->output_dim);
     v.D = D; v.layers = w->layers; v.heads = w->heads; v.patch = p; v.res = w->input_resolution;
-    v.grid = v.res / p; v.L = v.grid * v.grid + 1; v.E = w->output_dim; v.Kp = 3 * p * p;
-    if (v.L > 224) return fail(c, HG_ERR_INVALID, "at most 224 tokens per image supported (got %d)", v.L);
+    // Kp: the patch GEMM's K = 3 p p rounded up to its 64-column step (p = 14: 588 -> 640; p % 8 == 0 needs no padding).  The weight's
+    // pad columns are zero, the patch matrix's are written as zeros on every call (launch_im2col)
+    v.grid = v.res / p; v.L = v.grid * v.grid + 1; v.E = w->output_dim; v.Kp = im2col_kp(p);
+    if (v.L > ATTN_LONG_MAX_L)
+        return fail(c, HG_ERR_INVALID, "at most %d tokens per image supported (got %d)", ATTN_LONG_MAX_L, v.L);
+    if (v.L > ADAPTER_MAX_L)
+        for (int i = 0; w->adapters && i < w->layers; ++i)
+            if (w->adapters[i].present)
+                return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d (patch %d, resolution "
+                                               "%d); load it without adapter weights (use_adapter=False)", ADAPTER_MAX_L, v.L, p, v.res);
     int rc = 0;
-    keep_first(rc, as_f16(c, v.owned, w->conv1_weight, (size_t)D * v.Kp, &v.w_patch, "visual.conv1.weight"));
+    const int K0 = 3 * p * p;
+    if (v.Kp == K0) {
+        keep_first(rc, as_f16(c, v.owned, w->conv1_weight, (size_t)D * v.Kp, &v.w_patch, "visual.conv1.weight"));
+    } else {
+        std::vector<void*> sc;
+        half_t* dense = nullptr;
+        void* padded = nullptr;
+        int r2 = as_f16(c, sc, w->conv1_weight, (size_t)D * K0, &dense, "visual.conv1.weight");
+        if (!r2) r2 = dev_alloc(c, v.owned, (size_t)D * v.Kp * 2, &padded);
+        if (!r2) {
+            hipError_t e = hipMemset(padded, 0, (size_t)D * v.Kp * 2);
+            if (e == hipSuccess) e = hipDeviceSynchronize();      // (the conversion ran on the null stream)
+            if (e == hipSuccess)
+                e = hipMemcpy2D(padded, (size_t)v.Kp * 2, dense, (size_t)K0 * 2, (size_t)K0 * 2, D, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) r2 = fail(c, HG_ERR_HIP, "padding visual.conv1.weight failed: %s", hipGetErrorString(e));
+        }
+        free_all(sc);
+        v.w_patch = (half_t*)padded;
+        keep_first(rc, r2);
+    }
     keep_first(rc, as_f32(c, v.owned, w->class_embedding, D, &v.cls, "visual.class_embedding"));
     keep_first(rc, as_f32(c, v.owned, w->positional_embedding, (size_t)v.L * D, &v.pos, "visual.positional_embedding"));
     keep_first(rc, as_f32(c, v.owned, w->ln_pre_weight, D, &v.lnpre_w, "visual.ln_pre.weight"));
@@ -1591,6 +1624,37 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
     keep_first(rc, as_f32(c, v.owned, w->ln_post_weight, D, &v.lnpost_w, "visual.ln_post.weight"));
     keep_first(rc, as_f32(c, v.owned, w->ln_post_bias, D, &v.lnpost_b, "visual.ln_post.bias"));
     keep_first(rc, as_f16_T(c, v.owned, w->proj, D, v.E, &v.w_projT, "visual.proj"));
+    // Variant C of the reference keeps proj in fp32 (CLIP_models_adapter_prior2.py:980 converts nothing); its local map is summed over
+    // hundreds of tokens by its users (RoI pooling), which weighs the fp16 rounding of a proj column as often: measured on the 576
+    // tokens of ViT-L/14@336px, proj's rounding alone moves the map's sum by 9e-4.  Towers that only this head serves in variant C
+    // (more tokens than the adapters take) therefore get proj as hi + lo: a second GEMM pass over 2^11 x fp16(W - hi), scaled back in
+    // its epilogue (the remainder itself would sit in fp16's subnormals).  Towers of up to 224 tokens keep their one pass and their bits.
+    if (!rc && v.L > ADAPTER_MAX_L && w->proj.dtype == HG_F32) {
+        std::vector<void*> sc;
+        float* p32 = nullptr;
+        int r2 = as_f32(c, sc, w->proj, (size_t)D * v.E, &p32, "visual.proj");
+        std::vector<float> host((size_t)D * v.E);
+        if (!r2 && hipMemcpy(host.data(), p32, host.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) r2 = HG_ERR_HIP;
+        free_all(sc);
+        if (!r2) {
+            std::vector<half_t> lo((size_t)v.E * D);
+            for (int d = 0; d < D; ++d)
+                for (int e = 0; e < v.E; ++e) {
+                    const float x = host[(size_t)d * v.E + e];
+                    lo[(size_t)e * D + d] = (half_t)((x - (float)(half_t)x) * 2048.0f);
+                }
+            std::vector<float> sb((size_t)2 * v.E, 0.f);
+            for (int e = 0; e < v.E; ++e) sb[e] = 1.0f / 2048.0f;
+            void *plo = nullptr, *psb = nullptr;
+            r2 = dev_alloc(c, v.owned, lo.size() * 2, &plo);
+            if (!r2) r2 = dev_alloc(c, v.owned, sb.size() * 4, &psb);
+            if (!r2 && (hipMemcpy(plo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(psb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
+                r2 = HG_ERR_HIP;
+            if (!r2) { v.w_projT_lo = (half_t*)plo; v.proj_lo_scale = (float*)psb; }
+        }
+        if (r2) return fail(c, r2 < 0 ? r2 : HG_ERR_INVALID, "splitting visual.proj into hi + lo failed");
+    }
     if (rc) return rc < 0 ? rc : HG_ERR_INVALID;
     rc = load_blocks(c, v.owned, w->blocks, v.layers, D, v.blocks, true);
     if (rc) return rc;
@@ -1604,6 +1668,11 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
 int hg_update_adapters(hg_ctx* c, const hg_adapter_weights* adapters, int layers) {
     if (!c) return HG_ERR_INVALID;
     if (!c->vit.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vit first");
+    if (c->vit.L > ADAPTER_MAX_L)
+        for (int i = 0; adapters && i < layers; ++i)
+            if (adapters[i].present)
+                return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d", ADAPTER_MAX_L,
+                            c->vit.L);
     HG_ON_DEVICE(c);
     HG_HIP(hipDeviceSynchronize());
     return load_adapters(c, adapters, layers);
@@ -1859,6 +1928,15 @@ int hg_cache_logits(hg_ctx* c, int slot, const float* feats, int R, float* out, 
 }
 
 // ---- image tower ------------------------------------------------------------------------------------------
+// Crops per pass of the image tower: max_chunk_img (256) for every tower of up to 224 tokens; a longer one gets the ROWS such a pass
+// can hold at most (256 x 224 = 57 344: 99 crops of 577 tokens), so no workspace grows beyond what a 224-token tower of the same width
+// takes and every GEMM stays far inside gemm_ring_ok's 32-bit byte offsets (Mp x 4096 x 2 < 2^31 at 262 144 rows).  Rows of different
+// crops never meet in any kernel, so where the boundary falls does not reach the results.
+static int image_chunk(const hg_ctx* c, int L) {
+    if (L <= ATTN_MAX_L_RESIDENT) return c->max_chunk_img;
+    const int n = c->max_chunk_img * ATTN_MAX_L_RESIDENT / L;
+    return n > 0 ? n : 1;
+}
 // `trace_all` (hg_test_image_stream): every row of the stream into `trace`, one entry of B * L rows per block - one chunk only
 static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors, const uint8_t* mask, int B, int N,
                              float* out, float* out_local, float* trace, bool variant_c, hipStream_t s, bool trace_all = false) {
@@ -1872,8 +1950,9 @@ static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors
     HG_ON_DEVICE(c);
     const int D = v.D, L = v.L, G = L - 1, E = v.E;
     const size_t img = (size_t)3 * v.res * v.res;
-    for (int b0 = 0; b0 < B; b0 += c->max_chunk_img) {
-        const int Bc = (B - b0 < c->max_chunk_img) ? B - b0 : c->max_chunk_img;
+    const int chunk = image_chunk(c, L);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int Bc = (B - b0 < chunk) ? B - b0 : chunk;
         const int M = Bc * L;
         int rc = ensure_tower_ws(c, M, D);
         if (!rc) rc = ensure(c, c->head16, rup(variant_c ? M : Bc, 256) * D * 2);
@@ -1914,6 +1993,10 @@ static int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors
             g = GemmArgs{};
             g.A = h16; g.lda = D; g.W = v.w_projT; g.out = c->tok32.p; g.ldc = E; g.M = M; g.N = E; g.K = D;
             HG_HIP(gemm(c, EPI_BIAS_F32, g, s));
+            if (v.w_projT_lo) {      // + h16 x lo (hg_load_vit): tok32 += (acc + 0) * 2^-11
+                g.W = v.w_projT_lo; g.pos = v.proj_lo_scale; g.bias = v.proj_lo_scale + E;
+                HG_HIP(gemm(c, EPI_SCALE_RESID_F32, g, s));
+            }
             HG_HIP(launch_split_global_local((const float*)c->tok32.p, out + (size_t)b0 * E,
                                              out_local + (size_t)b0 * E * G, Bc, L, E, s));
         }
@@ -1933,7 +2016,7 @@ int hg_test_image_stream(hg_ctx* c, const float* x_nchw, int B, float* out, floa
     for (const AdapterW& a : c->vit.adapters)
         if (a.present) return fail(c, HG_ERR_INVALID, "hg_test_image_stream: adapters are loaded (under a trace the tower leaves the hi / lo "
                                                       "stream, a path production does not run)");
-    if (B < 1 || B > c->max_chunk_img || !trace) return fail(c, HG_ERR_INVALID, "hg_test_image_stream: B must be 1..one chunk, trace != NULL");
+    if (B < 1 || B > image_chunk(c, c->vit.L) || !trace) return fail(c, HG_ERR_INVALID, "hg_test_image_stream: B must be 1..one chunk, trace != NULL");
     return encode_image_impl(c, x_nchw, nullptr, nullptr, B, 0, out, nullptr, trace, false, (hipStream_t)stream, true);
 }
 int hg_encode_image_prior(hg_ctx* c, const float* x_nchw, const float* priors, const uint8_t* mask, int B, int N,

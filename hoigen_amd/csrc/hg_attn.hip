@@ -1,5 +1,6 @@
 // Fused scaled-dot-product attention for gfx950, head_dim 64, whole K/V of one (sequence, head) LDS
-// resident (L <= 224: 197 ViT tokens, 77 text tokens).  Replaces the SDPA inside
+// resident (L <= 224: 197 ViT tokens, 77 text tokens; 225 .. 640 tokens take attention_long_kernel, hg_attn_long.hip, from the two
+// launchers at the end of this file).  Replaces the SDPA inside
 // nn.MultiheadAttention (clipnet/model.py:171,181-183).  The [L,L] score matrix
 // never leaves registers.
 //
@@ -180,7 +181,8 @@ static hipError_t launch_t(const half_t* qkv, half_t* out, int n_seq, int L, int
 hipError_t launch_attention(const half_t* qkv, half_t* out, int n_seq, int L, int heads, bool causal,
                             hipStream_t s, int ldo, bool pack) {
     if (n_seq <= 0) return hipSuccess;
-    if (L < 1 || L > 224 || (ldo != 0 && (ldo < heads * HD || ldo % 8))) return hipErrorInvalidValue;
+    if (L < 1 || L > ATTN_LONG_MAX_L || (ldo != 0 && (ldo < heads * HD || ldo % 8))) return hipErrorInvalidValue;
+    if (L > ATTN_MAX_L_RESIDENT) return launch_attention_long(qkv, out, n_seq, L, heads, causal, s, ldo);
     if (pack && L <= 32)      // one wave per item: four items per workgroup (same bits)
         return causal ? launch_t<true, false, true>(qkv, out, n_seq, L, heads, s, nullptr, nullptr, ldo)
                       : launch_t<false, false, true>(qkv, out, n_seq, L, heads, s, nullptr, nullptr, ldo);
@@ -191,7 +193,8 @@ hipError_t launch_attention(const half_t* qkv, half_t* out, int n_seq, int L, in
 hipError_t launch_attention_row0(const half_t* qkv, const half_t* q0, const int32_t* sel, half_t* out, int n_seq, int L,
                                  int heads, bool causal, hipStream_t s) {
     if (n_seq <= 0) return hipSuccess;
-    if (L < 1 || L > 224 || !q0) return hipErrorInvalidValue;
+    if (L < 1 || L > ATTN_LONG_MAX_L || !q0) return hipErrorInvalidValue;
+    if (L > ATTN_MAX_L_RESIDENT) return launch_attention_long_row0(qkv, q0, sel, out, n_seq, L, heads, causal, s);
     return causal ? launch_t<true, true>(qkv, out, n_seq, L, heads, s, q0, sel)
                   : launch_t<false, true>(qkv, out, n_seq, L, heads, s, q0, sel);
 }

@@ -120,9 +120,60 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ x
         *reinterpret_cast<half8*>(out + ((size_t)b * g * g + gy * g + gx) * K + c * p * p + ky * p + kx) = h;
     }
 }
+// Any patch size (p = 14: rows of 14 floats = 56 B are 8-byte aligned in the image, 4-byte aligned in the fp16 matrix, so the 8-pixel
+// mapping above does not apply): thread -> the p pixels of one image row inside one patch, neighbouring threads neighbouring patches
+// of the same image row (the reads of a wave are one contiguous stretch).  Row stride of the matrix is Kp >= 3*p*p; the thread that
+// holds a patch's first row (c = 0, ky = 0) also writes zeros into its pad columns 3*p*p .. Kp-1 - on every call, whatever the
+// workspace held.  EVEN: p is even, two pixels per load / store.
+template <bool EVEN>
+__global__ __launch_bounds__(256) void im2col_pad_kernel(const float* __restrict__ x, half_t* __restrict__ out, int B, int R, int p,
+                                                         int Kp) {
+    const int g = R / p, K = 3 * p * p;
+    const size_t total = (size_t)B * 3 * R * g;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int gx = (int)(i % g);
+        size_t rest = i / g;
+        const int y = (int)(rest % R);
+        rest /= R;
+        const int c = (int)(rest % 3);
+        const int b = (int)(rest / 3);
+        const int gy = y / p, ky = y - gy * p;
+        const float* src = x + (((size_t)b * 3 + c) * R + y) * R + gx * p;
+        half_t* row = out + ((size_t)b * g * g + gy * g + gx) * Kp;
+        half_t* dst = row + c * p * p + ky * p;
+        if constexpr (EVEN) {
+            for (int e = 0; e < p; e += 2) {
+                const float2 a = *reinterpret_cast<const float2*>(src + e);
+                half2v h;
+                h[0] = (half_t)a.x;
+                h[1] = (half_t)a.y;
+                *reinterpret_cast<half2v*>(dst + e) = h;
+            }
+        } else {
+            for (int e = 0; e < p; ++e) dst[e] = (half_t)src[e];
+        }
+        if (c == 0 && ky == 0) {
+            if constexpr (EVEN) {
+                half2v z;
+                z[0] = (half_t)0.f;
+                z[1] = (half_t)0.f;
+                for (int e = K; e < Kp; e += 2) *reinterpret_cast<half2v*>(row + e) = z;
+            } else {
+                for (int e = K; e < Kp; ++e) row[e] = (half_t)0.f;
+            }
+        }
+    }
+}
 hipError_t launch_im2col(const float* x, half_t* out, int B, int R, int p, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (p % 8 || R % p) return hipErrorInvalidValue;
+    if (p <= 0 || R % p) return hipErrorInvalidValue;
+    if (p % 8) {
+        const size_t total = (size_t)B * 3 * R * (R / p);
+        const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+        if (p % 2) hipLaunchKernelGGL(im2col_pad_kernel<false>, dim3(grid), dim3(256), 0, s, x, out, B, R, p, im2col_kp(p));
+        else hipLaunchKernelGGL(im2col_pad_kernel<true>, dim3(grid), dim3(256), 0, s, x, out, B, R, p, im2col_kp(p));
+        return hipGetLastError();
+    }
     const size_t total = (size_t)B * 3 * R * (R / 8);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(im2col_kernel, dim3(grid), dim3(256), 0, s, x, out, B, R, p);

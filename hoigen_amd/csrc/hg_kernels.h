@@ -110,15 +110,23 @@ hipError_t launch_gemm_duo(int epi, const GemmArgs& a, hipStream_t s);
 
 // ---- attention: softmax(Q K^T / sqrt(64) [+causal]) V, head_dim 64 --------------------------
 // qkv fp16 [n_seq*L, 3*D] rows = tokens (q|k|v column blocks, head h = 64h..64h+63);
-// out fp16 [n_seq*L, D].  L <= 224.
+// out fp16 [n_seq*L, D].  1 <= L <= ATTN_LONG_MAX_L, either mask; above it hipErrorInvalidValue.
+// L <= ATTN_MAX_L_RESIDENT: attention_kernel (hg_attn.hip, one wave per 32-query tile); longer: attention_long_kernel
+// (hg_attn_long.hip, up to 16 waves walking the query tiles; 640 = the K and V rows that fill a CU's 160 KiB of LDS)
 // ldo: row stride of out in halfs (0 = heads * 64)
 // pack: L <= 32 (one wave per item) runs four items per workgroup (dispatch-bound otherwise; bit-identical)
+static constexpr int ATTN_MAX_L_RESIDENT = 224;
+static constexpr int ATTN_LONG_MAX_L = 640;
 hipError_t launch_attention(const half_t* qkv, half_t* out, int n_seq, int L, int heads, bool causal,
                             hipStream_t s, int ldo = 0, bool pack = true);
 // attention of ONE query row per sequence (row sel[seq], row 0 when sel is null; sel[seq] < L): K and V from
 // qkv [n_seq*L, 3*heads*64], the queries from q0 [n_seq, heads*64] (dense), out [n_seq, heads*64] (dense)
 hipError_t launch_attention_row0(const half_t* qkv, const half_t* q0, const int32_t* sel, half_t* out, int n_seq, int L,
                                  int heads, bool causal, hipStream_t s);
+// the two forms for ATTN_MAX_L_RESIDENT < L <= ATTN_LONG_MAX_L (hg_attn_long.hip); launch_attention / launch_attention_row0 dispatch
+hipError_t launch_attention_long(const half_t* qkv, half_t* out, int n_seq, int L, int heads, bool causal, hipStream_t s, int ldo);
+hipError_t launch_attention_long_row0(const half_t* qkv, const half_t* q0, const int32_t* sel, half_t* out, int n_seq, int L,
+                                      int heads, bool causal, hipStream_t s);
 
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
@@ -183,7 +191,11 @@ hipError_t launch_layernorm_f16(const float* x, const float* w, const float* b, 
 // pos / cls / L (ln_pre of the vision tower): row r is first replaced by (r % L == 0 ? cls : x[r]) + pos[r % L]
 hipError_t launch_layernorm_f32(const float* x, const float* w, const float* b, float* out, int M, int D,
                                 hipStream_t s, const float* pos = nullptr, const float* cls = nullptr, int L = 1);
-// NCHW fp32 crops -> patch matrix fp16 [B*g*g, 3*p*p] (token t = g*row+col, k = c*p*p+ky*p+kx).
+// NCHW fp32 crops -> patch matrix fp16 [B*g*g, Kp] (token t = g*row+col, k = c*p*p+ky*p+kx), Kp = im2col_kp(p) = 3*p*p rounded up
+// to 64 (the GEMMs' K step).  p % 8 == 0: 3*p*p is a multiple of 64 already (p = 16, 32), 8 pixels per thread, no pad columns.
+// Any other p with R % p == 0 (p = 14: 588 -> 640): one thread per patch row, and columns 3*p*p .. Kp-1 are written as zeros on
+// EVERY call (the matrix lives in a shared workspace; the weight's pad columns are zero, but 0 x NaN is NaN).
+inline int im2col_kp(int p) { return (3 * p * p + 63) / 64 * 64; }
 hipError_t launch_im2col(const float* x, half_t* out, int B, int R, int p, hipStream_t s);
 // x[r][:] = table[ids[r/L*ld_ids + r%L]][:] + pos[r%L][:]   (text: token_embedding + positional)
 hipError_t launch_embed_tokens(const int32_t* ids, int ld_ids, const float* table, const float* pos, float* x,
@@ -256,6 +268,8 @@ hipError_t launch_roi_align(const float* feat, int C, int H, int W, const float*
                             int P, float* out_pooled, float* out_mean, hipStream_t s);
 
 // ---- adapter (variant C) --------------------------------------------------------------------
+// tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
+static constexpr int ADAPTER_MAX_L = 224;
 struct AdapterDev {      // device pointers, all fp32 except the two MFMA operands
     const half_t* down_w;   // [d, D] fp16
     const float* down_b;    // [d]

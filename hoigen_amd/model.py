@@ -433,7 +433,8 @@ class VisionTransformer(nn.Module):
     @torch.no_grad()
     def forward_stream_trace(self, x: torch.Tensor):
         """Test hook: (embedding [B,E], every row of the residual stream after ln_pre and every block [layers+1,B*L,D]).
-        With option last_block_row0 = 1 the last entry holds the B class rows in its first B rows.  One chunk (256 crops) at most."""
+        With option last_block_row0 = 1 the last entry holds the B class rows in its first B rows.  One pass of the tower at most
+        (256 crops; 99 at 577 tokens per image)."""
         _require_cuda(x, "image batch")
         h = self._sync(x.device)
         xf = x.detach().to(torch.float32).contiguous()
@@ -478,7 +479,7 @@ class CLIP(nn.Module):
                  variant_c: bool = False, adapter_layers: Optional[List[int]] = None, adapter_num_layers: int = 1):
         super().__init__()
         if isinstance(vision_layers, (tuple, list)):
-            raise NotImplementedError("hoigen_amd: ModifiedResNet towers are outside the hot path (HOIGen uses ViT-B/16)")
+            raise NotImplementedError("hoigen_amd: ModifiedResNet towers are outside the hot path (HOIGen uses ViT-B/16 and ViT-L/14@336px)")
         self.context_length = context_length
         self.visual = VisionTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
                                         vision_width // 64, embed_dim, returns_local=variant_c,

@@ -59,6 +59,11 @@ VIT_B16 = dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_wid
                vision_patch_size=16, context_length=77, vocab_size=49408, transformer_width=512,
                transformer_heads=8, transformer_layers=12)
 
+# the reference's other backbone (ViT-L/14@336px: 577 tokens per image, 427.9 M parameters)
+VIT_L14_336 = dict(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024,
+                   vision_patch_size=14, context_length=77, vocab_size=49408, transformer_width=768,
+                   transformer_heads=12, transformer_layers=12)
+
 # heads = width // 64 is fixed by the reference (clipnet/model.py:268,417), so the smallest
 # multi-head configuration has width 128.
 TINY = dict(embed_dim=128, image_resolution=32, vision_layers=2, vision_width=128,

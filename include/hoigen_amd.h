@@ -138,6 +138,12 @@ const char* hg_version(void);
 /* ---- weights (replace nn.Module.load_state_dict / build_model: clipnet/model.py:395-432,
  *      CLIP_models_adapter_prior2.py:934-984).  Weights are copied/converted; the caller may free
  *      its tensors afterwards.  Loading again replaces the previous set. -------------------------- */
+/* hg_load_vit limits: width a multiple of 128 with heads = width / 64, width <= 1024; output_dim a multiple of 128; any patch
+ * size p that divides input_resolution (p = 16, 32: 8 pixels per thread; any other p, e.g. 14: one patch row per thread, the patch
+ * GEMM's K = 3 p p padded with zeros to a multiple of 64, 588 -> 640); tokens per image L = (input_resolution / p)^2 + 1 <= 640
+ * (ViT-B/16: 197, ViT-L/14: 257, ViT-L/14@336px: 577; L <= 224 and 225 .. 640 run different attention kernels).  Instance adapters
+ * need L <= 224: adapter weights for a tower with more tokens are refused here and by hg_update_adapters (HG_ERR_INVALID, the
+ * message says so); such a tower runs variants A and C-without-adapters (hg_encode_image_prior with priors == NULL). */
 int hg_load_vit(hg_ctx*, const hg_vit_weights*);
 int hg_load_text(hg_ctx*, const hg_text_weights*);
 int hg_load_vae(hg_ctx*, int slot, const hg_vae_weights*);
@@ -148,11 +154,14 @@ int hg_update_adapters(hg_ctx*, const hg_adapter_weights* adapters, int layers);
 
 /* ---- image tower --------------------------------------------------------------------------- */
 /* CLIP.encode_image / VisionTransformer.forward, variant A (clipnet/model.py:219-236,336-337):
- * x [B,3,R,R] fp32 NCHW -> out [B,E] fp32. */
+ * x [B,3,R,R] fp32 NCHW -> out [B,E] fp32.  Any B: a call runs in passes of 256 crops (L <= 224 tokens per image) or of
+ * 256 * 224 / L crops (longer towers: 99 crops of 577 tokens), which bounds the workspaces; results do not depend on where a pass
+ * ends.  Limits of L and p: hg_load_vit. */
 int hg_encode_image(hg_ctx*, const float* x_nchw, int B, float* out, void* stream);
 /* Variant C VisionTransformer.forward(x, prior) (CLIP_models_adapter_prior2.py:489-506).
  * priors [B,N,64] fp32 and mask [B,N] uint8 (1 = padded key) or both NULL / N == 0 for prior=None.
- * out_global [B,E]; out_local [B,E,g,g] (NCHW).  Blocks without a loaded adapter behave as A. */
+ * out_global [B,E]; out_local [B,E,g,g] (NCHW).  Blocks without a loaded adapter behave as A.  Towers of more than 224 tokens
+ * per image loaded with an fp32 proj apply it as hi + lo fp16 (two GEMM passes) in this entry point. */
 int hg_encode_image_prior(hg_ctx*, const float* x_nchw, const float* priors, const uint8_t* mask,
                           int B, int N, float* out_global, float* out_local_nchw, void* stream);
 /* Test hook: as hg_encode_image, additionally copies the CLS row of the residual stream after
@@ -331,7 +340,10 @@ int hg_test_gemm_hilo(hg_ctx*, const float* a, const float* w, const float* bias
 /* Test hook for the attention kernels (clipnet/model.py:171,181-183: the SDPA inside nn.MultiheadAttention, head_dim
  * 64): qkv [n_seq*L, 3*heads*64] fp32 on the device (rounded to fp16 inside).  q0 == NULL: full attention, out
  * [n_seq*L, heads*64].  q0 != NULL: [n_seq, heads*64] queries of ONE row per sequence (row sel[seq], device int32, or
- * row 0 when sel is NULL - the row index only matters for the causal mask), out [n_seq, heads*64]. */
+ * row 0 when sel is NULL - the row index only matters for the causal mask), out [n_seq, heads*64].
+ * 1 <= L <= 640 in both forms, either mask (L <= 224: hg_attn.hip; 225 .. 640: hg_attn_long.hip; 640 is what a compute unit's
+ * 160 KiB of LDS holds of K and V); L > 640: HG_ERR_INVALID.  Under hg_profile_begin(HG_PROF_ATTENTION) the full form's kernel
+ * launch is recorded. */
 int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t* sel, int n_seq, int L, int heads,
                       int causal, float* out, void* stream);
 
@@ -350,7 +362,7 @@ int hg_test_qkv_attn(hg_ctx*, const float* a, const float* w, const float* bias,
  * 0 < trunc < L, else L).  Entry 0 is the stream entering block 0 (after ln_pre / after token + positional embedding),
  * entry i the stream after block i-1 as block i reads it (centre + hi + lo summed when it is held so).  With option
  * last_block_row0 = 1 the last entry holds the B / T rows that block ran on densely, in its first rows.  HG_ERR_INVALID
- * for a vision context with adapters loaded and for calls longer than one chunk (256 crops) / one text pass. */
+ * for a vision context with adapters loaded and for calls longer than one pass (256 crops; 256 * 224 / L for L > 224) / one text pass. */
 int hg_test_image_stream(hg_ctx*, const float* x_nchw, int B, float* out, float* trace, void* stream);
 int hg_test_text_stream(hg_ctx*, const int32_t* ids, int T, int L, int trunc, float* out, float* trace, void* stream);
 
