@@ -46,6 +46,10 @@ struct BlockW {
     // MFMA fragments per head pair); null when the width does not qualify
     half_t* wp_qkv;
     float* bcs_qkv;
+    // the same packing of the layer's OWN w_qkv with bf_qkv / csg_qkv: the operands of the fused kernel where the LayerNorm weight
+    // rides in the activation copy (text tower, text_ln_fold = 1: hg_qkv_attn_text.hip); null elsewhere
+    half_t* wpg_qkv;
+    float* bcsg_qkv;
 };
 
 struct AdapterW {
@@ -156,6 +160,8 @@ struct hg_ctx {
     int opt_text_ln_fold = 1;    // text tower: 1 (default) LayerNorm folded into its GEMMs with the LayerNorm weight in the ACTIVATION copy (GemmArgs::gamma:
                                  // the GEMMs keep the layer's own fp16 weights - closer to the reference than the separate kernels, 4 % faster);
                                  // 2 the weight folded into fp16(W * gamma) as in the vision tower (10 % faster, 7.6e-4 instead of 6.2e-4); 0 separate kernels
+    int opt_qkv_attn_text = 0;   // text tower: in_proj + causal attention as one kernel for L <= 80 (hg_qkv_attn_text.hip; folded blocks): 0 two kernels,
+                                 // 1 where it measured faster (qkv_attn_text_pays: profiles/qkv_attn_text.txt), 2 wherever the shapes allow
     int opt_qkv_attn_c = 1;      // ... also in the blocks that carry a folded adapter (variant C on the hi / lo stream: K = D + 64)
     int opt_vae_fused = 1;       // CoOp-VAE Encoder -> reparameterise -> Generator as ONE kernel (hg_vae_fused.hip) for the rows that fill
                                  // whole rounds of 128-row items over the CUs (the rest: the GEMM path); 2: every row; 0: GEMM path only
@@ -388,6 +394,31 @@ int load_blocks(hg_ctx* c, std::vector<void*>& owned, const hg_block_weights* sr
         }
 
     }
+    return HG_OK;
+}
+
+// Option qkv_attn_text: the in_proj operands of the text tower's blocks in the fused kernel's fragment order (hg_qkv_attn_text.hip),
+// packed on the first text call that runs with the option on and only in the form that call's text_ln_fold needs (gamma: the layer's
+// own w_qkv with csg_qkv; else wf_qkv with cs_qkv) - 3 D^2 x 2 bytes per block and form (18.9 MB for the 12 blocks of D = 512); with
+// the option at 0 nothing is allocated.
+int ensure_text_packs(hg_ctx* c, std::vector<void*>& owned, std::vector<BlockW>& blocks, int D, bool gamma) {
+    if (!qkv_attn_text_ok(1, 77, D, D / 64, D)) return HG_OK;
+    bool packed = false;
+    for (BlockW& b : blocks) {
+        half_t*& wp = gamma ? b.wpg_qkv : b.wp_qkv;
+        float*& bcs = gamma ? b.bcsg_qkv : b.bcs_qkv;
+        if (wp) continue;
+        if (!b.wf_qkv) return HG_OK;      // (loaded without the folded operands: the option does not apply)
+        int rc = 0;
+        half_t* wp_new = nullptr;
+        keep_first(rc, dev_alloc(c, owned, (size_t)3 * D * D * 2, (void**)&wp_new));
+        keep_first(rc, dev_alloc(c, owned, (size_t)(D / 128) * 768 * 4, (void**)&bcs));
+        if (rc) return rc < 0 ? rc : HG_ERR_OOM;
+        HG_HIP(launch_pack_qkv(gamma ? b.w_qkv : b.wf_qkv, b.bf_qkv, gamma ? b.csg_qkv : b.cs_qkv, wp_new, bcs, D, D / 64, 0));
+        wp = wp_new;
+        packed = true;
+    }
+    if (packed) HG_HIP(hipStreamSynchronize(0));      // (packed on the null stream, as at load time; the call's stream may be any)
     return HG_OK;
 }
 
@@ -826,6 +857,13 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
         if (g.hl == 1 || g.hl == 2) { g.out3 = hg; g.ld3 = D; a_ln = hg; }
         else a_ln = h;
     };
+    // the text tower's form of qa_on (option qkv_attn_text, hg_qkv_attn_text.hip): causal, L <= 80, folded LayerNorm in either text_ln_fold
+    // form, no adapters; a pack of whole sequences per row tile.  Bit-identical to the GEMM + attention_kernel it replaces.
+    const bool qat_on = fuse && causal && !adapters && c->opt_qkv_attn_text && qkv_attn_text_ok(n_seq, L, D, heads, D) &&
+                        (c->opt_qkv_attn_text == 2 || qkv_attn_text_pays(n_seq, L, heads, c->n_cu));
+    auto qat_block = [&](size_t i, bool row0_last_blk) {
+        return qat_on && !row0_last_blk && (gs ? blocks[i].wpg_qkv : blocks[i].wp_qkv) != nullptr;
+    };
     // c_fc and c_proj of a block as ONE persistent launch (option mlp_pair, hg_mlp_pair.hip): LayerNorm-folded blocks without adapters
     // where c_proj is a LayerNorm-emitting residual GEMM on the hi / lo (or fp32) stream (every block but the tower's last)
     const int pair_panels = (int)rup(mlp_pair_ready_words(M), 64);      // words per block: the census, then a counter per 256-row panel
@@ -882,6 +920,14 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
             qa.a_bytes = (unsigned)(rup(M, 256) * (size_t)D * 2);
             ProfScope ps(c, s, HG_PROF_QKV_ATTN, n_seq, L, heads);
             HG_HIP(launch_qkv_attn(qa, s));
+        } else if (qat_block(i, row0_last)) {
+            // the text tower's in_proj + causal attention in one kernel (hg_qkv_attn_text.hip): the operands of the GEMM below
+            QkvAttnArgs qa{};
+            qa.x16 = gs ? a_ln : h; qa.lda = D; qa.wp = gs ? b.wpg_qkv : b.wp_qkv; qa.bcs = gs ? b.bcsg_qkv : b.bcs_qkv; qa.mr = mr;
+            qa.out = att; qa.ldo = D; qa.n_seq = n_seq; qa.L = L; qa.D = D; qa.heads = heads; qa.gsz = 0;
+            qa.a_bytes = (unsigned)(rup(M, 256) * (size_t)D * 2);
+            ProfScope ps(c, s, HG_PROF_QKV_ATTN, n_seq, L, heads);
+            HG_HIP(launch_qkv_attn_text(qa, s));
         } else if (fuse) {
             g.W = b.wf_qkv + qoff * D; g.bias = b.bf_qkv + qoff; g.cs = b.cs_qkv + qoff; g.mr = mr;
             if (gs) { g.A = a_ln; g.W = b.w_qkv + qoff * D; g.cs = b.csg_qkv + qoff; }
@@ -923,7 +969,7 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, int n_seq, int L, i
             break;
         }
         half_t* const att_o = hilo_c ? att2 : att;      // where the attention output (the out-proj operand) goes
-        if (!(fuse && qa_block(i, row0_last))) HG_HIP(attention(c, qkv, att_o, n_seq, L, heads, causal, s, kcat ? D + 64 : 0));
+        if (!(fuse && qa_block(i, row0_last)) && !qat_block(i, row0_last)) HG_HIP(attention(c, qkv, att_o, n_seq, L, heads, causal, s, kcat ? D + 64 : 0));
         g = GemmArgs{};
         g.A = att_o; g.lda = D; g.W = b.w_out; g.bias = b.b_out; g.out = x; g.ldc = D; g.M = M; g.N = D; g.K = D;
         if (kcat == 2) {      // x += [att | e] [W_out | Q]^T + b_out: the adapter's update rides along
@@ -1114,7 +1160,7 @@ hg_ctx* hg_create(int device) {
     struct { const char* env; const char* key; } init[] = {{"HG_CHUNK_ROWS", "chunk_rows"}, {"HG_LAST_BLOCK_ROW0", "last_block_row0"},
                                                            {"HG_LN_FUSE", "ln_fuse"}, {"HG_ADAPTER_FUSE", "adapter_fuse"},
                                                            {"HG_ADAPTER_FOLD", "adapter_fold"}, {"HG_STREAM_HILO", "stream_hilo"},
-                                                           {"HG_QKV_ATTN", "qkv_attn"}, {"HG_QKV_ATTN_MIN_SEQ", "qkv_attn_min_seq"},
+                                                           {"HG_QKV_ATTN", "qkv_attn"}, {"HG_QKV_ATTN_TEXT", "qkv_attn_text"}, {"HG_QKV_ATTN_MIN_SEQ", "qkv_attn_min_seq"},
                                                            {"HG_QKV_ATTN_GSZ", "qkv_attn_gsz"}, {"HG_QKV_ATTN_C", "qkv_attn_c"}, {"HG_TEXT_LN_FOLD", "text_ln_fold"}, {"HG_VAE_FUSED", "vae_fused"},
                                                            {"HG_MLP_PAIR", "mlp_pair"},
                                                            {"HG_MLP_PAIR_CHUNK", "mlp_pair_chunk"}, {"HG_MLP_PAIR_FC_SLOTS", "mlp_pair_fc_slots"},
@@ -1139,6 +1185,9 @@ int hg_set_option(hg_ctx* c, const char* key, int value) {
     else if (k == "qkv_attn") {
         if (value < 0 || value > 2) return fail(c, HG_ERR_INVALID, "qkv_attn must be 0, 1 or 2 (got %d)", value);
         c->opt_qkv_attn = value;
+    } else if (k == "qkv_attn_text") {
+        if (value < 0 || value > 2) return fail(c, HG_ERR_INVALID, "qkv_attn_text must be 0, 1 or 2 (got %d)", value);
+        c->opt_qkv_attn_text = value;
     } else if (k == "qkv_attn_min_seq") {
         if (value < 1) return fail(c, HG_ERR_INVALID, "qkv_attn_min_seq must be >= 1 (got %d)", value);
         c->opt_qkv_attn_min_seq = value;
@@ -1183,6 +1232,7 @@ int hg_get_option(hg_ctx* c, const char* key, int* value) {
     else if (k == "stream_hilo") *value = c->opt_stream_hilo;
     else if (k == "stream_lo_bits") *value = 8;      // read-only: the low half of the stream is bf8
     else if (k == "qkv_attn") *value = c->opt_qkv_attn;
+    else if (k == "qkv_attn_text") *value = c->opt_qkv_attn_text;
     else if (k == "qkv_attn_min_seq") *value = c->opt_qkv_attn_min_seq;
     else if (k == "qkv_attn_gsz") *value = c->opt_qkv_attn_gsz;
     else if (k == "qkv_attn_c") *value = c->opt_qkv_attn_c;
@@ -1456,9 +1506,17 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
     HG_ON_DEVICE(c);
     const int D = heads * 64, M = n_seq * L;
     const int K = D + ((fused & 2) ? 64 : 0);      // (bit 1: a is [M, D + 64], w [3D, D + 64] - the shape of a block with a folded adapter)
+    // bit 2: the causal mask - the text tower's kernel (hg_qkv_attn_text.hip, L <= 80) against the folded GEMM + the causal attention launch
+    const bool causal = (fused & 4) != 0;
+    if ((fused & ~7) || (causal && (fused & 2))) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: fused must be 0 .. 5");
     fused &= 1;
-    const size_t Mp = rup(M, 256);
-    if (fused && !qkv_attn_ok(n_seq, L, D, heads, K, K)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused kernel");
+    // (the folded ring GEMM wants 512 rows: a shorter causal call runs it over zero rows up to there - a row's result does not
+    // depend on the rows beside it)
+    const int Mg = causal && M < 512 ? 512 : M;
+    const size_t Mp = rup(Mg, 256);
+    if (fused && causal && !qkv_attn_text_ok(n_seq, L, D, heads, K))
+        return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused causal kernel");
+    if (fused && !causal && !qkv_attn_ok(n_seq, L, D, heads, K, K)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused kernel");
     int rc = ensure(c, c->h, Mp * K * 2);
     if (!rc) rc = ensure(c, c->fc, (size_t)3 * D * K * 2 * 2 + (size_t)(heads / 2 + 1) * 768 * 4);
     if (!rc) rc = ensure(c, c->qkv, Mp * 3 * D * 2);
@@ -1486,7 +1544,7 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
         HG_HIP(hipMemsetAsync(c->cq.p, 0, 256 * 8 * 16 * 8, s));
 #endif
         ProfScope ps(c, s, HG_PROF_QKV_ATTN, n_seq, L, heads);
-        hipError_t e = launch_qkv_attn(qa, s);
+        hipError_t e = causal ? launch_qkv_attn_text(qa, s) : launch_qkv_attn(qa, s);
         ps.finish();
         if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test qkv_attn launch failed: %s", hipGetErrorString(e));
 #ifdef HG_STAMPS
@@ -1513,10 +1571,10 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
     } else {
         GemmArgs g{};
         g.A = (const half_t*)c->h.p; g.lda = K; g.W = w16; g.bias = bias; g.cs = cs; g.mr = (const float*)c->mr.p;
-        g.out = c->qkv.p; g.ldc = 3 * D; g.M = M; g.N = 3 * D; g.K = K;
+        g.out = c->qkv.p; g.ldc = 3 * D; g.M = Mg; g.N = 3 * D; g.K = K;
         if (!gemm_ln_ok(EPI_LN_BIAS_F16, g)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the folded GEMM");
         HG_HIP(gemm(c, EPI_LN_BIAS_F16, g, s));
-        HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, false, s));
+        HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, causal, s));
     }
     HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)M * D, s));
     return HG_OK;
@@ -2062,6 +2120,10 @@ static int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out
     // fixture, closer than the separate kernels' 6.5e-4, 5.35 -> 5.15 ms for 600 x 77 tokens); 2 folds gamma into the weights (4.8 ms,
     // 7.6e-4, worst prompt 9.6e-4 of the 1e-3 budget); 0 runs the separate kernels
     const float* rows = nullptr;      // dense EOT rows when the last block ran on them only
+    if (c->opt_qkv_attn_text && c->opt_text_ln_fold) {
+        int rcp = ensure_text_packs(c, t.owned, t.blocks, D, c->opt_text_ln_fold == 1);
+        if (rcp) return rcp;
+    }
     int rc = run_blocks(c, t.blocks, Tc, Leff, D, t.heads, true, s, trace, Tc * Leff * D, nullptr, c->opt_text_ln_fold != 0, &rows, eot,
                         nullptr, nullptr, nullptr, nullptr, c->opt_text_ln_fold == 1, trace != nullptr);
     if (rc) return rc;

@@ -33,7 +33,10 @@ __device__ __forceinline__ void tile_scores(const char* kb, const int (&k_off)[4
     }
 }
 
-template <bool CAUSAL>
+// VMASK (hg_qkv_attn_text.hip: several sequences in one LDS tile): the V rows behind row L - 1 are another sequence's, so on a masked
+// tile the V values of keys >= L are read as zeros - their probabilities are zero already, but 0 * Inf / 0 * NaN would carry a
+// neighbour's non-finite values into this sequence (finite data: the same bits as with the clamped pad rows of attention_kernel).
+template <bool CAUSAL, bool VMASK = false>
 __device__ __forceinline__ void tile_softmax_pv(const char* vb, const int (&v_off)[2], f32x16& s, const int kt, const int qt,
                                                 const int q, const int L, const int rs, const int hh, const float c,
                                                 float& m, float& lsum, f32x16 (&o)[2]) {
@@ -98,6 +101,13 @@ __device__ __forceinline__ void tile_softmax_pv(const char* vb, const int (&v_of
             for (int e = 0; e < 4; ++e) {
                 vf[e] = (half_t)vr[dt][0][e];
                 vf[4 + e] = (half_t)vr[dt][1][e];
+            }
+            if constexpr (VMASK) {
+                if (kt * 32 + 32 > L) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (kt * 32 + 16 * sstep + 8 * (j >> 2) + 4 * hh + (j & 3) >= L) vf[j] = (half_t)0.f;
+                }
             }
             o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[sstep], o[dt], 0, 0, 0);
         }

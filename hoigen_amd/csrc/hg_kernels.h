@@ -153,6 +153,13 @@ bool qkv_attn_pays(int n_seq, int heads, int n_cu);
 hipError_t launch_pack_qkv(const half_t* W, const float* bias, const float* cs, half_t* Wp, float* bcs, int D, int heads,
                            hipStream_t s, int K = 0);
 hipError_t launch_qkv_attn(const QkvAttnArgs& a, hipStream_t s);
+// the causal short-sequence member (hg_qkv_attn_text.hip, the text tower): a work item is a pack of floor(160 / L) whole sequences x
+// a head pair; K = D.  1 <= L <= 80, heads even, D = 64 * heads, D / 64 >= 6 and = 3 m or 3 m + 2 (D = 512, 768)
+bool qkv_attn_text_ok(int n_seq, int L, int D, int heads, int lda);
+int qkv_attn_text_items(int n_seq, int L, int heads);      // (pack, head pair) work items of a call
+// speed only: is the one kernel expected to beat the two it replaces at this shape (n_cu <= 0: 256)
+bool qkv_attn_text_pays(int n_seq, int L, int heads, int n_cu);
+hipError_t launch_qkv_attn_text(const QkvAttnArgs& a, hipStream_t s);
 
 // ---- CoOp-VAE as one kernel (hg_vae_fused.hip): Encoder -> reparameterise -> Generator with both hidden layers and z on chip --------
 // (main_coop_vae.py:261-296,444-448).  wp = the weights packed by launch_pack_vae into the fragment stream the kernel walks:

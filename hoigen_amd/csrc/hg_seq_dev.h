@@ -22,14 +22,24 @@
 
 namespace hg {
 
-constexpr int SQ_RB = 13;                          // 16-row blocks of a sequence tile (L <= 208)
+// The including kernel may set SQ_RB_BLOCKS (16-row blocks of its row tile, 2 mod 6: 13 = the default, or 10 - the 160-row packs of
+// hg_qkv_attn_text.hip) and SQ_S12_KIB (the region shared with its phase between two K loops) before this header.
+#ifndef SQ_RB_BLOCKS
+#define SQ_RB_BLOCKS 13
+#endif
+#ifndef SQ_S12_KIB
+#define SQ_S12_KIB 80
+#endif
+constexpr int SQ_RB = SQ_RB_BLOCKS;                // 16-row blocks of a sequence tile (13: L <= 208)
 constexpr int SQ_NCB = 3;                          // 16-column blocks per wave: 8 waves x 48 = 384 columns per panel
-constexpr int SQ_NA = 3;                           // A pieces (1 KiB = 8 rows) per wave and K-tile; waves 0 and 1 issue one more
+constexpr int SQ_NA = 2 * SQ_RB / 8;               // A pieces (1 KiB = 8 rows) per wave and K-tile (13 row blocks: 3; 10: 2) ...
+constexpr int SQ_NAX = 2 * SQ_RB - 8 * SQ_NA;      // ... and waves below this one issue one more (13 row blocks: waves 0 and 1; 10: 0-3)
 constexpr int SQ_WSLOT = 2 * SQ_NCB * 1024;        // one wave's W ring: a K-tile of fragments
 constexpr int SQ_ASTG = SQ_RB * 2048;              // one A stage: 208 rows x 128 B
 constexpr int SQ_A0 = 8 * SQ_WSLOT;                // stage 0
 constexpr int SQ_S12 = SQ_A0 + SQ_ASTG;            // stages 1 and 2 (shared with the caller's phase between two K loops)
-constexpr int SQ_S12_BYTES = 80 * 1024;
+constexpr int SQ_S12_BYTES = SQ_S12_KIB * 1024;
+static_assert((2 * SQ_RB) % 6 == 2 && 2 * SQ_ASTG <= SQ_S12_BYTES, "ring slot of position 0 (hg_seq_kloop_run.inc); stages 1 and 2");
 constexpr int SQ_END = SQ_S12 + SQ_S12_BYTES;      // first free byte behind the K loop's LDS
 #ifndef SQ_AR
 #define SQ_AR 6                                    // activation-fragment ring: SQ_AR - 1 reads ahead (3 or 6: 26 positions = 2 mod SQ_AR)

@@ -1,5 +1,5 @@
 // K loop of the sequence-tile GEMMs (hg_seq_dev.h), expanded inside a kernel body.  Expects in scope: `smem` (THE extern
-// __shared__ array), `lane`, `wave`, `nk` (K / 64, a multiple of 3), and the macros
+// __shared__ array), `lane`, `wave`, `nk` (K / 64; its residue mod 3 = SQ_NKMOD), and the macros
 // SQ_A_PTR / SQ_A_BYTES / SQ_LDA (fp16 activations [rows, lda], bytes readable), SQ_W_PTR / SQ_W_BYTES (packed weight).
 // Defines: seq_prologue(row0, pn), stage_base(st), and what hg_seq_kloop_run.inc (the loop itself, expanded inside the item loop) needs.
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(SQ_A_PTR), 0, (SQ_A_BYTES), 0x00020000);
@@ -17,7 +17,7 @@
     };
     auto stage_base = [&](int st) { return st == 0 ? SQ_A0 : SQ_S12 + (st - 1) * SQ_ASTG; };
     // all pieces of one K-tile of the rows row0 .. row0 + 207 (26 pieces: waves 0 and 1 issue a fourth - an operation more
-    // only makes the counted waits below stricter, never looser)
+    // only makes the counted waits below stricter, never looser; 10 row blocks: 20 pieces, two per wave and a third from waves 0-3)
     auto issue_A = [&](int row0, int kt, int sbase) {
         const int soff = (row0 * sq_lda + kt * 64) * 2;
         const int ln = lane_now();
@@ -28,9 +28,9 @@
                                                      soff + i * 64 * sq_lda * 2, 0, 0);
         int w_now = wave;      // (opaque: a hoisted copy of this condition is one more value the allocator has to keep across the loop)
         asm volatile("" : "+s"(w_now));
-        if (w_now < 2)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (HG_LDS void*)(smem + sbase + (wave + 24) * 1024), 16, voffA,
-                                                     soff + 3 * 64 * sq_lda * 2, 0, 0);
+        if (w_now < SQ_NAX)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (HG_LDS void*)(smem + sbase + (wave + 8 * SQ_NA) * 1024), 16, voffA,
+                                                     soff + SQ_NA * 64 * sq_lda * 2, 0, 0);
     };
     char* wring = smem + wave * SQ_WSLOT;
     // fragment slot (ks, c) of K-tile kt of panel pn: Wp[pn][2 kt + ks][wave][c][lane][8]

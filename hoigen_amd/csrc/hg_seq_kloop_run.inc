@@ -6,17 +6,22 @@
     // issued further VMEM operations of its own just before (tables for its epilogue: older operations only make the counted
     // waits stricter).  On return the last MFMAs are issued and the next item's first K-tile is in flight: the caller waits
     // vmcnt(0) + barrier before it touches stages 1 and 2 or lets stores enter vmcnt.
-    //   position 21 (five reads before the boundary): counted wait for this wave's pieces of stage kt+1, s_barrier (publishes
+    //   (RB = SQ_RB row blocks, NPOS = 2 RB positions per K-tile, PUB = NPOS - 5; 13 row blocks: RB - 3 = 10, PUB = 21; 10: 7 and 15)
+    //   position PUB (five reads before the boundary): counted wait for this wave's pieces of stage kt+1, s_barrier (publishes
     //     stage kt+1; every wave has left K-tile kt-1 behind: its stage is free), then the A group of stage kt+2 into it.
-    //   VMEM operations of K-tile kt in issue order:   R_0 R_1 R_2 | R_3 R_4 R_5 | A A A
+    //   VMEM operations of K-tile kt in issue order:   R_0 R_1 R_2 | R_3 R_4 R_5 | A x SQ_NA (one more from waves < SQ_NAX)
     //     R_j: refill of W slot j with K-tile kt+1's fragment, issued once the k-step's fragments are in registers.
-    //   Counted waits (vmcnt is in issue order), all "6":
-    //     before reading slots 3-5 (k-step 0, row block 10):  R_3-5 of K-tile kt-1 landed; issued since: A A A, R_0-2
-    //     position 21:                                         A group of K-tile kt-1 (= stage kt+1) landed; since: R_0-2, R_3-5
-    //     before reading slots 0-2 (k-step 1, row block 10):  R_0-2 of this K-tile landed; issued since: R_3-5, A A A
+    //   Counted waits (vmcnt is in issue order; NCB = 3 refills per k-step, SQ_NA = 3 pieces with 13 row blocks, 2 with 10):
+    //     before reading slots 3-5 (k-step 0, row block RB - 3):  R_3-5 of K-tile kt-1 landed; issued since: the A group, R_0-2
+    //                                                              -> NCB + SQ_NA (6 / 5)
+    //     position PUB:                                            A group of K-tile kt-1 (= stage kt+1) landed; since: R_0-2, R_3-5
+    //                                                              -> 2 NCB (6)
+    //     before reading slots 0-2 (k-step 1, row block RB - 3):  R_0-2 of this K-tile landed; issued since: R_3-5, the A group
+    //                                                              -> NCB + SQ_NA (6 / 5)
+    //     (a wave that issued the extra piece has one operation more behind the one it waits for: the same count is stricter for it)
     // KIND 0: first K-tile of an item (primes the ring and reads its W fragments here; stage 1 is issued at the start of the
     // loop), 1: middle, 2: last (stages 1 and 2 of the next item would overlay the caller's phase: no A group, no barrier; the R_j
-    // fetch the next item's first K-tile; nothing is read ahead).  PH = kt % 3: the stage, and the ring slot of position 0 (26
+    // fetch the next item's first K-tile; nothing is read ahead).  PH = kt % 3: the stage, and the ring slot of position 0 (NPOS = 26 or 20
     // positions = 2 mod 6 per K-tile).
     // SQ_NKMOD = nk % 3 (a macro of the including kernel, default 0).  nk = 3 m + 1 (K = 832: the adapter's 64 extra columns): the last
     // K-tile sits in stage 0 itself, so the next item's first K-tile cannot be fetched under this item's last ones: KIND 3 = the
@@ -83,8 +88,9 @@
                         SQ_STAMP_B();
                         // (behind a K-tile that issued no activation group the refills R_3-5 of K-tile kt - 1 have only R_0-2 behind them)
                         // (... and in that K-tile itself R_0-2 have only R_3-5 behind them at k-step 1)
+                        // (otherwise: the three refills and an activation group - SQ_NA pieces from every wave - were issued since)
                         if ((AFTER_NO_A && ks == 0) || (NO_A && ks == 1)) wait_vm<NCB>();
-                        else if (!(FIRST && ks == 0)) wait_vm<2 * NCB>();
+                        else if (!(FIRST && ks == 0)) wait_vm<NCB + SQ_NA>();
                         SQ_STAMP_E(2);      // counted wait for the W slots
 #pragma unroll
                         for (int c = 0; c < NCB; ++c) wn[c] = read_W((1 - ks) * NCB + c);
@@ -110,10 +116,22 @@
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
-        using I3 = std::integral_constant<int, 3>;
-        using I4 = std::integral_constant<int, 4>;
+        using I3 [[maybe_unused]] = std::integral_constant<int, 3>;
+        using I4 [[maybe_unused]] = std::integral_constant<int, 4>;
         ktile(0, I0{}, I0{});
-#if !defined(SQ_NKMOD) || SQ_NKMOD == 0
+#if defined(SQ_NKMOD) && SQ_NKMOD == 2
+        // nk = 3 m + 2 (K = 512: the text tower of ViT-B): the last K-tile sits in stage 1 and stage 0 holds K-tile nk-2 until every
+        // wave has left it, so - as with 3 m + 1 - the caller fetches the next item's first K-tile behind the loop.  K-tiles 1 .. nk-3
+        // (3 m - 1 of them: stages 1 2 | 0 1 2 | ..), then nk-2 (stage 0, no activation group), nk-1 (stage 1)
+        for (int kt = 1; kt < nk - 2; kt += 3) {
+            ktile(kt, I1{}, I1{});
+            ktile(kt + 1, I1{}, I2{});
+            if (kt + 2 >= nk - 2) break;
+            ktile(kt + 2, I1{}, I0{});
+        }
+        ktile(nk - 2, I3{}, I0{});
+        ktile(nk - 1, I4{}, I1{});
+#elif !defined(SQ_NKMOD) || SQ_NKMOD == 0
         for (int kt = 1; kt < nk - 2; kt += 3) {      // K-tiles 1 .. nk-3 (a multiple of 3 of them)
             ktile(kt, I1{}, I1{});
             ktile(kt + 1, I1{}, I2{});

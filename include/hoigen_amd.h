@@ -256,6 +256,11 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      (hoigen_amd/csrc/hg_qkv_attn.hip: q, k, v stay in LDS; 192 < tokens <= 208, i.e. ViT-B/16); 0: two kernels with the
  *                      qkv matrix in HBM between them; 2: the one kernel wherever the shapes allow (1 also asks that the last round
  *                      of its (sequence, head pair) items is well filled: speed only).  Bit-identical results either way.
+ *   "qkv_attn_text"   [HG_QKV_ATTN_TEXT]   the same for the text tower (hoigen_amd/csrc/hg_qkv_attn_text.hip: causal, tokens <= 80, a work item is a
+ *                      pack of floor(160 / tokens) whole prompts x a head pair; width 512 or 768; either folded text_ln_fold form; not the
+ *                      last block's EOT-row path).  0 (default): two kernels; 1: the one kernel where it measured faster: at least one
+ *                      round of (pack, head pair) items on the CUs and a last round that leaves at most a fifth of the launch idle
+ *                      (qkv_attn_text_pays; profiles/qkv_attn_text.txt: 600 prompts x 77 tokens yes, -3 %; 600 x 13 no); 2: wherever the shapes allow.  Bit-identical results.
  *   "qkv_attn_min_seq" [HG_QKV_ATTN_MIN_SEQ] ... from this many sequences per call on (default 32)
  *   "qkv_attn_gsz"    [HG_QKV_ATTN_GSZ]    head pairs per XCD group of that kernel (0 = all six side by side; speed only)
  *   "text_ln_fold"    [HG_TEXT_LN_FOLD]    how the text tower's LayerNorms reach its GEMMs.  1 (default): folded, with the LayerNorm weight
@@ -352,7 +357,10 @@ int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t*
  * LayerNorm-folded in_proj weight, bias / cs [3D], mr [n_seq*L, 2] = (mean - centre, rstd), D = 64 * heads; out [n_seq*L, D]
  * fp32 = the attention output.  fused bit 0 set: the one kernel (192 < L <= 208, heads even, D / 64 a multiple of 3);
  * clear: the folded GEMM followed by hg_test_attention's kernel - the two must agree bit for bit.  fused bit 1 set: a is
- * [n_seq*L, D + 64] and w [3D, D + 64], the summed length of a block whose adapter is folded into in_proj (variant C). */
+ * [n_seq*L, D + 64] and w [3D, D + 64], the summed length of a block whose adapter is folded into in_proj (variant C).
+ * fused bit 2 set: the causal mask (not with bit 1).  With bit 0: the text tower's kernel (hg_qkv_attn_text.hip: L <= 80, heads even,
+ * D / 64 >= 6 and 3 m or 3 m + 2); without: the folded GEMM (over zero rows up to 512 where the call has fewer) followed by the causal
+ * attention launch run_blocks picks at that L.  Values above 5 are HG_ERR_INVALID. */
 int hg_test_qkv_attn(hg_ctx*, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
                      int L, int heads, int fused, float* out, void* stream);
 
