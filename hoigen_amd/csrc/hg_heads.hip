@@ -1,0 +1,208 @@
+// The row-parallel heads: CoOp-VAE (Encoder -> reparameterise -> Generator), mlp_net and the cache-model logits, in chunks of rows.
+#include "hg_host.h"
+
+namespace {
+
+// Rows of the next chunk of a row-parallel call with `left` rows to go: max_chunk_rows, except that the LAST chunk absorbs a
+// tail of up to an eighth of it (100 000 rows = 32 768 + 32 768 + 34 464 instead of + 32 768 + 1 696: the four dependent GEMMs of a
+// 1 696-row chunk fill 14-56 tiles each and cost 0.12 ms for 1.7 % of the rows; workspace +5 %)
+inline int chunk_rows(const hg_ctx* c, int left) {
+    const int m = c->max_chunk_rows;
+    return left <= m + m / 8 ? left : m;
+}
+
+// Rows (from row 0) that go to the one-kernel path: its work items are 128 rows and take 0.3-0.4 ms each, so it only pays for whole
+// rounds of items over the CUs (100 000 rows = 782 items = 3 rounds of 256 + 14: the 14 would cost a fourth round); the rest - and calls
+// too small to fill most of one round - take the GEMM path, whose 256 x 256 tiles quantise a hundred times finer.
+inline int fused_item_rows(const hg_ctx* c, int opt, int R) {
+    if (opt == 0 || R <= 0) return 0;
+    if (opt == 2) return R;
+    const int per = vae_fused_rows_per_item();
+    const long items = ((long)R + per - 1) / per, ncu = c->n_cu;
+    const long full = items / ncu * ncu, rem = items - full;
+    const long take = full + (rem * 100 >= ncu * 70 ? rem : 0);
+    const long rows = take * per;
+    return (int)(rows < R ? rows : R);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- cache-model logits -----------------------------------------------------------------
+int hg_cache_logits(hg_ctx* c, int slot, const float* feats, int R, float* out, void* stream) {
+    if (!c || slot < 0 || slot >= HG_MAX_CACHE_SLOTS) return HG_ERR_INVALID;
+    Cache& m = c->cache[slot];
+    if (!m.loaded) return fail(c, HG_ERR_NOT_LOADED, "cache slot %d not loaded", slot);
+    if (R == 0) return HG_OK;
+    if (R < 0 || !feats || !out) return fail(c, HG_ERR_INVALID, "bad arguments to cache_logits");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    for (int r0 = 0, Rc = 0; r0 < R; r0 += Rc) {
+        Rc = chunk_rows(c, R - r0);
+        const size_t Rp = rup(Rc, 256);
+        const int Np = m.has_labels ? m.Cp : m.Sp, Nout = m.has_labels ? m.C : m.S;
+        int rc = ensure(c, c->h, Rp * m.K * 2);
+        if (!rc) rc = ensure(c, c->att, Rp * m.Sp * 2);
+        if (!rc) rc = ensure(c, c->x, Rp * Np * 4);
+        if (rc) return rc;
+        half_t* f16 = (half_t*)c->h.p;
+        half_t* phi = (half_t*)c->att.p;
+        float* tmp = (float*)c->x.p;
+        HG_HIP(launch_f32_to_f16(feats + (size_t)r0 * m.K, f16, (size_t)Rc * m.K, s));
+        if (!m.has_labels) {
+            HG_HIP(gemm(c, EPI_BIAS_F32, gemm_args(f16, m.K, m.w16, m.b, tmp, m.Sp, Rc, m.Sp, m.K), s));
+        } else {
+            HG_HIP(gemm(c, EPI_BIAS_F16, gemm_args(f16, m.K, m.w16, nullptr, phi, m.Sp, Rc, m.Sp, m.K), s));
+            HG_HIP(hipMemsetAsync(tmp, 0, (size_t)Rc * m.Cp * 4, s));
+            GemmArgs g = gemm_args(phi, m.Sp, m.lt16, m.bias_c, tmp, m.Cp, Rc, m.Cp, m.Sp);
+            g.pos = m.scale;
+            HG_HIP(gemm(c, EPI_SCALE_RESID_F32, g, s));          // 0 + (phi L + b L) * scale
+        }
+        HG_HIP(launch_copy_cols(tmp, Np, out + (size_t)r0 * Nout, Rc, Nout, s));
+    }
+    return HG_OK;
+}
+
+// ---- CoOp-VAE ---------------------------------------------------------------------------------------------
+static int vae_fused_rows(const hg_ctx* c, int R) { return fused_item_rows(c, c->opt_vae_fused, R); }
+static int generator_rows(hg_ctx* c, Vae& v, const half_t* z16, int R, float* bias, hipStream_t s) {
+    // Generator: relu(z W0^T + b0) W2^T + b2  (main_coop_vae.py:282-296)
+    half_t* g1 = (half_t*)c->fc.p;
+    HG_HIP(gemm(c, EPI_BIAS_RELU_F16, gemm_args(z16, v.dim, v.g_w0, v.g_b0, g1, v.gh, R, v.gh, v.dim), s));
+    HG_HIP(gemm(c, EPI_BIAS_F32, gemm_args(g1, v.gh, v.g_w2, v.g_b2, bias, v.dim, R, v.dim, v.gh), s));
+    return HG_OK;
+}
+
+int hg_vae_forward(hg_ctx* c, int slot, const float* x, const float* eps, int R, float* mean, float* logvar,
+                   float* z, float* bias, void* stream) {
+    if (!c || slot < 0 || slot >= HG_MAX_SLOTS) return HG_ERR_INVALID;
+    Vae& v = c->vae[slot];
+    if (!v.enc || (bias && !v.gen)) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vae(slot %d) incomplete", slot);
+    if (R == 0) return HG_OK;
+    if (R < 0 || !x || !eps) return fail(c, HG_ERR_INVALID, "bad arguments to vae_forward");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const int dim = v.dim;
+    // Option vae_fused = 2: the leading rows that fill whole rounds of items (all rows) go through ONE kernel, hidden layers and z on
+    // chip (hg_vae_fused.hip).  Default (1): the Encoder stays on the GEMM path - the one kernel computes its hidden layer twice (1 024
+    // output columns do not fit a wave's registers) and loses to the GEMMs there: measured 1.94 ms against 1.72 ms for 98 304 rows - and
+    // the Generator of those rows runs as the one kernel on the fp16 z the reparameterisation kernel writes (0.86 against 0.92 ms).
+    const int Rf = v.wp ? vae_fused_rows(c, R) : 0;
+    const bool all_fused = Rf > 0 && c->opt_vae_fused == 2;
+    if (all_fused) {
+        int rc = ensure(c, c->zpark, vae_fused_park_bytes(Rf));
+        if (rc) return rc;
+        VaeFusedArgs a{};
+        a.x = x; a.eps = eps; a.mean = mean; a.logvar = logvar; a.z = z; a.bias = bias; a.wp = v.wp;
+        a.b0e = v.e_b0; a.bml = v.e_bml; a.b0g = v.g_b0; a.b2g = v.g_b2; a.zpark = (half_t*)c->zpark.p;
+        a.R = Rf; a.eh = v.eh; a.gh = v.gen ? v.gh : 0; a.mode = bias ? 0 : 1; a.has_enc = true;
+        ProfScope ps(c, s, HG_PROF_VAE_FUSED, Rf, bias ? 3 : 2, v.eh);
+        HG_HIP(launch_vae_fused(a, s));
+    }
+    // rows of the call whose Generator runs as the one kernel (hybrid): the chunks below stop at that boundary
+    const int Rg = (!all_fused && bias && Rf > 0) ? Rf : 0;
+    if (Rg > 0) {      // z of those rows as fp16, for ONE Generator launch behind the chunks (three items per CU instead of three launches)
+        int rc = ensure(c, c->zpark, (size_t)rup(Rg, 256) * dim * 2);
+        if (rc) return rc;
+    }
+    for (int r0 = all_fused ? Rf : 0, Rc = 0; r0 < R; r0 += Rc) {
+        Rc = chunk_rows(c, R - r0);
+        if (r0 < Rg && r0 + Rc > Rg) Rc = Rg - r0;
+        const bool gen_fused = r0 < Rg;
+        const size_t Rp = rup(Rc, 256);
+        int rc = ensure(c, c->h, Rp * dim * 2);
+        if (!rc) rc = ensure(c, c->att, Rp * dim * 2);
+        if (!rc) rc = ensure(c, c->qkv, Rp * v.eh * 2);
+        if (!rc) rc = ensure(c, c->x, Rp * 2 * dim * 4);
+        if (!rc && bias && !gen_fused) rc = ensure(c, c->fc, Rp * v.gh * 2);
+        if (rc) return rc;
+        half_t* x16 = (half_t*)c->h.p;
+        const size_t o = (size_t)r0 * dim;
+        half_t* z16 = gen_fused ? (half_t*)c->zpark.p + o : (half_t*)c->att.p;
+        half_t* h1 = (half_t*)c->qkv.p;
+        float* ml = (float*)c->x.p;          // [2][Rp, dim] planes for the halves the caller did not ask for
+        float* mean_o = mean ? mean + o : ml;
+        float* lv_o = logvar ? logvar + o : ml + Rp * dim;
+        HG_HIP(launch_f32_to_f16(x + o, x16, (size_t)Rc * dim, s));
+        HG_HIP(gemm(c, EPI_BIAS_RELU_F16, gemm_args(x16, dim, v.e_w0, v.e_b0, h1, v.eh, Rc, v.eh, dim), s));
+        // mean | log_var as ONE N = 2*dim GEMM whose two column halves land directly in the caller's tensors
+        GemmArgs g = gemm_args(h1, v.eh, v.e_wml, v.e_bml, mean_o, dim, Rc, 2 * dim, v.eh);
+        // (The reparameterisation on the accumulators of a row-interleaved mean | log_var GEMM was built and measured in round 3:
+        // bit-identical, one launch and 410 MB less per 100 k rows, 0.5-2 % SLOWER - its 56 partial-line stores per wave cost the
+        // GEMM what the HBM-speed reparam kernel costs on its own; commit 2b473ec and earlier carry it.)
+        g.out_hi = lv_o; g.n_split = dim;
+        HG_HIP(gemm(c, EPI_BIAS_F32, g, s));
+        HG_HIP(launch_reparam(mean_o, lv_o, eps + o, Rc, dim, z ? z + o : nullptr, z16, dim, s));
+        if (bias && !gen_fused) {
+            rc = generator_rows(c, v, z16, Rc, bias + o, s);
+            if (rc) return rc;
+        }
+    }
+    if (Rg > 0) {
+        VaeFusedArgs a{};
+        a.x16 = (const half_t*)c->zpark.p; a.bias = bias; a.wp = v.wp; a.b0g = v.g_b0; a.b2g = v.g_b2;
+        a.R = Rg; a.eh = v.eh; a.gh = v.gh; a.mode = 2; a.has_enc = true;
+        ProfScope ps(c, s, HG_PROF_VAE_FUSED, Rg, 1, v.gh);
+        HG_HIP(launch_vae_fused(a, s));
+    }
+    return HG_OK;
+}
+
+int hg_generator(hg_ctx* c, int slot, const float* z, int R, float* bias, void* stream) {
+    if (!c || slot < 0 || slot >= HG_MAX_SLOTS) return HG_ERR_INVALID;
+    Vae& v = c->vae[slot];
+    if (!v.gen) return fail(c, HG_ERR_NOT_LOADED, "generator of slot %d not loaded", slot);
+    if (R == 0) return HG_OK;
+    if (R < 0 || !z || !bias) return fail(c, HG_ERR_INVALID, "bad arguments to generator");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const int Rf = v.wp ? vae_fused_rows(c, R) : 0;
+    if (Rf > 0) {
+        VaeFusedArgs a{};
+        a.x = z; a.bias = bias; a.wp = v.wp; a.b0g = v.g_b0; a.b2g = v.g_b2;
+        a.R = Rf; a.eh = v.enc ? v.eh : 0; a.gh = v.gh; a.mode = 2; a.has_enc = v.enc;
+        ProfScope ps(c, s, HG_PROF_VAE_FUSED, Rf, 1, v.gh);
+        HG_HIP(launch_vae_fused(a, s));
+    }
+    for (int r0 = Rf, Rc = 0; r0 < R; r0 += Rc) {
+        Rc = chunk_rows(c, R - r0);
+        const size_t Rp = rup(Rc, 256);
+        int rc = ensure(c, c->att, Rp * v.dim * 2);
+        if (!rc) rc = ensure(c, c->fc, Rp * v.gh * 2);
+        if (rc) return rc;
+        half_t* z16 = (half_t*)c->att.p;
+        HG_HIP(launch_f32_to_f16(z + (size_t)r0 * v.dim, z16, (size_t)Rc * v.dim, s));
+        rc = generator_rows(c, v, z16, Rc, bias + (size_t)r0 * v.dim, s);
+        if (rc) return rc;
+    }
+    return HG_OK;
+}
+
+int hg_mlp_net(hg_ctx* c, int slot, const float* x, int R, float* out, void* stream) {
+    if (!c || slot < 0 || slot >= HG_MAX_SLOTS) return HG_ERR_INVALID;
+    Mlp& m = c->mlp[slot];
+    if (!m.loaded) return fail(c, HG_ERR_NOT_LOADED, "mlp_net slot %d not loaded", slot);
+    if (R == 0) return HG_OK;
+    if (R < 0 || !x || !out) return fail(c, HG_ERR_INVALID, "bad arguments to mlp_net");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    for (int r0 = 0, Rc = 0; r0 < R; r0 += Rc) {
+        Rc = chunk_rows(c, R - r0);
+        const size_t Rp = rup(Rc, 256);
+        int rc = ensure(c, c->h, Rp * m.in * 2);
+        if (!rc) rc = ensure(c, c->att, Rp * m.hid * 2);
+        if (!rc) rc = ensure(c, c->qkv, Rp * m.hid * 2);
+        if (rc) return rc;
+        half_t* x16 = (half_t*)c->h.p;
+        half_t* a1 = (half_t*)c->att.p;
+        half_t* a2 = (half_t*)c->qkv.p;
+        HG_HIP(launch_f32_to_f16(x + (size_t)r0 * m.in, x16, (size_t)Rc * m.in, s));
+        HG_HIP(gemm(c, EPI_BIAS_RELU_F16, gemm_args(x16, m.in, m.w0, m.b0, a1, m.hid, Rc, m.hid, m.in), s));
+        HG_HIP(gemm(c, EPI_BIAS_RELU_F16, gemm_args(a1, m.hid, m.w2, m.b2, a2, m.hid, Rc, m.hid, m.hid), s));
+        HG_HIP(gemm(c, EPI_BIAS_F32, gemm_args(a2, m.hid, m.w4, m.b4, out + (size_t)r0 * m.out, m.out, Rc, m.out, m.hid), s));
+    }
+    return HG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,300 @@
+// What the host files of the C ABI share (hg_api.hip, hg_load.hip, hg_tower.hip, hg_heads.hip, hg_test_hooks.hip): the context and the
+// weight structs, error reporting, the grow-only workspace, the profiler scope and the GEMM / attention wrappers.  Host code only.
+//
+// Device data layout:
+//   residual stream x   fp32 [M, D]      M = n_seq * L rows (token-major, sequence-contiguous)
+//   h / att / fc        fp16 [M, D|4D]   MFMA A operands (K contiguous)
+//   qkv                 fp16 [M, 3D]     q|k|v column blocks, head h = columns 64h..64h+63
+//   linear weights      fp16 [N, K]      exactly nn.Linear's [out, in] -> both GEMM operands K-contiguous
+//   proj/text_projection fp16 [E, D]     transposed once at load ([D,E] in the state dict)
+//   biases, LN affine, embeddings, positional: fp32
+#pragma once
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/hoigen_amd.h"
+#include "hg_kernels.h"
+
+using namespace hg;
+
+namespace hg_host {      // (the host files' own names: nothing as plain as fail / gemm / ensure leaves the library unqualified)
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+struct BlockW {
+    half_t *w_qkv, *w_out, *w_fc, *w_proj;
+    float *b_qkv, *b_out, *b_fc, *b_proj, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+    // LayerNorm folded into the consuming GEMM: W' = fp16(W * gamma), cs[n] = sum_k W'[n][k],
+    // b' = b + W beta;  LN(x) W^T + b = rstd * (x16 W'^T - mean * cs) + b'
+    half_t *wf_qkv, *wf_fc;
+    float *cs_qkv, *bf_qkv, *cs_fc, *bf_fc;
+    // column sums sum_k gamma[k] W[n][k] for the form that keeps the LayerNorm weight in the activation copy and W unrounded (text tower)
+    float *csg_qkv, *csg_fc;
+    // wf_qkv / bf_qkv / cs_qkv once more in the order the fused in_proj + attention kernel streams them (hg_qkv_attn.hip:
+    // MFMA fragments per head pair); null when the width does not qualify
+    half_t* wp_qkv;
+    float* bcs_qkv;
+    // the same packing of the layer's OWN w_qkv with bf_qkv / csg_qkv: the operands of the fused kernel where the LayerNorm weight
+    // rides in the activation copy (text tower, text_ln_fold = 1: hg_qkv_attn_text.hip); null elsewhere
+    half_t* wpg_qkv;
+    float* bcsg_qkv;
+};
+
+struct AdapterW {
+    bool present = false;
+    int d = 0;
+    half_t* down_w = nullptr;  // [128 (padded), D]
+    float* down_b = nullptr;   // [128]
+    float* down_cs = nullptr;  // [128] row sums of the fp16 weight: down_proj on the CENTRED fp16 copy adds mu * cs back
+    half_t* up_w = nullptr;    // [D, 64]
+    float* up_b = nullptr;
+    float* scale = nullptr;
+    // The adapter folded into the block's GEMMs altogether (hg_elem.hip adapter_q_kernel): a = Q e with e = the last decoder
+    // layer's normalised output; [0] = prior path (last layer of the mhsa_layers chain), [1] = self path (mhsa)
+    struct Fold {
+        half_t* down2 = nullptr;    // [128, D]: down_proj rows | Q^T (the cross term of the statistics rides in the padded half)
+        half_t* wk_out = nullptr;   // [D, D + 64] = [W_out | Q]
+        half_t* wq_cat = nullptr;   // [3D, D + 64] = [W'_qkv | W'_qkv Q]
+        half_t* wp_qcat = nullptr;  // wq_cat in the fused in_proj + attention kernel's fragment order (launch_pack_qkv, K = D + 64)
+        half_t* g16 = nullptr;      // [64, 64] Q^T Q
+        float* qm = nullptr;        // [64] column sums of Q
+    } fold[2];
+    float* dl[2][12] = {};     // see AdapterDev
+    half_t* w16[2][6] = {};    // see AdapterDev
+    struct Extra { float* dl[12] = {}; half_t* w16[6] = {}; };
+    std::vector<Extra> extra;  // mhsa_layers.1 .. N-1 (adapter_num_layers > 1), prior path only
+};
+
+struct Vit {
+    bool loaded = false;
+    int D = 0, layers = 0, heads = 0, patch = 0, res = 0, grid = 0, L = 0, E = 0, Kp = 0;
+    half_t* w_patch = nullptr;
+    float *cls = nullptr, *pos = nullptr, *lnpre_w = nullptr, *lnpre_b = nullptr, *lnpost_w = nullptr,
+          *lnpost_b = nullptr;
+    half_t* w_projT = nullptr;
+    half_t* w_projT_lo = nullptr;     // variant C of towers beyond the adapters' 224 tokens: 2^11 x the fp16 remainder of proj (hg_load_vit)
+    float* proj_lo_scale = nullptr;   // [E] 2^-11, and [E] zeros behind it (the second pass's bias)
+    std::vector<BlockW> blocks;
+    std::vector<AdapterW> adapters;
+    std::vector<void*> owned, owned_adapters;
+};
+
+struct Text {
+    bool loaded = false;
+    int D = 0, layers = 0, heads = 0, ctx = 0, vocab = 0, E = 0;
+    float *tok = nullptr, *pos = nullptr, *lnf_w = nullptr, *lnf_b = nullptr;
+    half_t* w_projT = nullptr;
+    std::vector<BlockW> blocks;
+    std::vector<void*> owned;
+};
+
+struct Vae {
+    bool enc = false, gen = false;
+    int dim = 0, eh = 0, gh = 0;
+    half_t *e_w0 = nullptr, *e_wml = nullptr, *g_w0 = nullptr, *g_w2 = nullptr;
+    float *e_b0 = nullptr, *e_bml = nullptr, *g_b0 = nullptr, *g_b2 = nullptr;
+    half_t* wp = nullptr;      // the same weights as the fragment stream of the one-kernel path (hg_vae_fused.hip): [E0 | E1 | G]
+    // the same stacked mean | log_var operand with its rows interleaved in blocks of 128 (EPI_VAE_REPARAM_F32)
+    std::vector<void*> owned;
+};
+
+struct Cache {
+    bool loaded = false, has_labels = false;
+    int S = 0, K = 0, C = 0, Sp = 0, Cp = 0;
+    half_t *w16 = nullptr, *lt16 = nullptr;   // [Sp,K] ; labels^T [Cp,Sp]
+    float *b = nullptr, *bias_c = nullptr, *scale = nullptr;   // [Sp] ; [Cp] bias @ labels ; [Cp] 1 / (lens * post_div)
+    std::vector<void*> owned;
+};
+
+struct Mlp {
+    bool loaded = false;
+    int in = 0, hid = 0, out = 0;
+    half_t *w0 = nullptr, *w2 = nullptr, *w4 = nullptr;
+    float *b0 = nullptr, *b2 = nullptr, *b4 = nullptr;
+    std::vector<void*> owned;
+};
+}  // namespace hg_host
+using namespace hg_host;
+
+struct hg_ctx {
+    int device = 0;
+    std::string err;
+    Vit vit;
+    Text text;
+    Vae vae[HG_MAX_SLOTS];
+    Mlp mlp[HG_MAX_SLOTS];
+    Cache cache[HG_MAX_CACHE_SLOTS];
+    // workspace (grow-only)
+    Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
+    Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
+    Buf att2;            // variant C with the stream as centre + hi + lo: the out-proj operand [att | e] beside the in_proj one [x16 | e]
+    Buf zpark;           // hg_vae_fused.hip: the encoder's first z half as fp16 fragments, per wave
+    Buf xlo;             // low half of the residual stream while it is held as centre + hi + lo (GemmArgs::hl)
+    Buf pair_ready;      // hg_mlp_pair.hip: ready counters [blocks][256-row panels], zeroed at the start of every tower pass
+    int max_chunk_img = 256;
+    int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
+    int max_chunk_rows = 32768;
+    // behaviour options: hg_set_option; the environment (HG_LAST_BLOCK_ROW0, HG_LN_FUSE, HG_ADAPTER_FUSE, HG_ADAPTER_FOLD,
+    // HG_CHUNK_ROWS) only gives their values at hg_create - nothing on the call path reads the environment
+    int opt_row0 = 1;            // last block of a tower without token outputs on the one row that leaves it
+    int opt_ln_fuse = 1;         // LayerNorm folded into the GEMMs where the shapes allow
+    int opt_adapter_fuse = 1;    // ... also behind the instance adapters (variant C)
+    int opt_adapter_fold = 1;    // adapter folded into the block's own QKV / out-proj GEMMs (0: separate up_proj GEMM)
+    int opt_stream_hilo = 1;     // residual stream as centre + hi + lo (fp16 copy + bf8 remainder) between the folded blocks (0: fp32)
+    int opt_qkv_attn = 1;        // in_proj + attention as one kernel, q / k / v kept in LDS (vision tower, folded blocks; 0: two kernels)
+    int opt_qkv_attn_min_seq = 32;   // ... from this many sequences per call on, and where its last round of items is filled well
+                                     // enough (qkv_attn_pays; qkv_attn = 2: wherever the shapes allow)
+    int opt_qkv_attn_gsz = 0;    // head pairs per XCD group of that kernel (0 = all)
+    int opt_text_ln_fold = 1;    // text tower: 1 (default) LayerNorm folded into its GEMMs with the LayerNorm weight in the ACTIVATION copy (GemmArgs::gamma:
+                                 // the GEMMs keep the layer's own fp16 weights - closer to the reference than the separate kernels, 4 % faster);
+                                 // 2 the weight folded into fp16(W * gamma) as in the vision tower (10 % faster, 7.6e-4 instead of 6.2e-4); 0 separate kernels
+    int opt_qkv_attn_text = 0;   // text tower: in_proj + causal attention as one kernel for L <= 80 (hg_qkv_attn_text.hip; folded blocks): 0 two kernels,
+                                 // 1 where it measured faster (qkv_attn_text_pays: profiles/qkv_attn_text.txt), 2 wherever the shapes allow
+    int opt_qkv_attn_c = 1;      // ... also in the blocks that carry a folded adapter (variant C on the hi / lo stream: K = D + 64)
+    int opt_vae_fused = 1;       // CoOp-VAE Encoder -> reparameterise -> Generator as ONE kernel (hg_vae_fused.hip) for the rows that fill
+                                 // whole rounds of 128-row items over the CUs (the rest: the GEMM path); 2: every row; 0: GEMM path only
+    int opt_mlp_pair = 1;        // c_fc -> QuickGELU -> c_proj of a LayerNorm-folded block as ONE persistent launch with per-row-panel ready
+                                 // counters between its tiles (hg_mlp_pair.hip; both towers, variant A); bit-identical to the two launches
+    int opt_mlp_pair_chunk = 32; // ... 256-row panels of an XCD per chunk
+    int opt_mlp_pair_fc_slots = 32;  // ... workgroups per XCD that run c_fc tiles (the rest start with c_proj)
+    int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
+    int n_cu = 256;
+    // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became
+    // resident); the call in flight returned garbage, the next tower call reports HG_ERR_HIP
+    int32_t* pair_err = nullptr;
+    // sticky device->host flag (host-mapped): inside a tower with folded LayerNorms a row reached further from its centre than the centred
+    // fp16 copy / the hi half of the stream can hold (|x - row centre| > 65504, bounded through the row statistics: finalize_stats).
+    // Reported as HG_ERR_INVALID by the next tower call.
+    int32_t* range_flag = nullptr;
+    // sticky device->host flag (host-mapped): set by clamp_eot when a caller-supplied text truncation was shorter than
+    // max(EOT)+1 (a stale host memo); reported as HG_ERR_INVALID by the next text call
+    int32_t* eot_flag = nullptr;
+    int32_t* eot_flag_dev = nullptr;   // the same condition for the call in flight, in device memory (zeroed per call): poison_if_flag polls it
+    // live per-kernel timing for bench.py (hg_profile_begin/end): hipEvent pairs around the launches of one kernel
+    // kind (or of every GEMM and attention launch), on the stream the kernel is launched on
+    int prof_kind = HG_PROF_OFF;
+    std::vector<hipEvent_t> prof_ev;
+    std::vector<hg_prof_rec> prof_rec;
+    size_t prof_n = 0;
+};
+
+namespace hg_host {
+// every workspace buffer of a context: what hg_destroy frees and hg_workspace_bytes adds up
+#define HG_WORKSPACE_BUFS(c)                                                                                                          \
+    {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
+     &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
+     &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready}
+
+inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
+    char tmp[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(tmp, sizeof tmp, fmt, ap);
+    va_end(ap);
+    if (c) c->err = tmp;
+    return code;
+}
+
+#define HG_HIP(call)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return fail(c, HG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
+                        __LINE__);                                                                     \
+    } while (0)
+
+// Entry points run on the context's device and give the caller's current device back on return (torch tracks the
+// current device per thread; a library that silently changes it redirects the caller's next allocation).
+struct DevGuard {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit DevGuard(const hg_ctx* c) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != c->device) err = hipSetDevice(c->device);
+        else prev = -1;
+    }
+    ~DevGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+#define HG_ON_DEVICE(c)                                                                                 \
+    DevGuard dev_guard_(c);                                                                             \
+    if (dev_guard_.err != hipSuccess)                                                                   \
+        return fail(c, HG_ERR_HIP, "hipSetDevice(%d) failed: %s", (c)->device, hipGetErrorString(dev_guard_.err))
+// first failing status wins (OR-ing negative codes can turn OOM into another code)
+inline void keep_first(int& rc, int r) {
+    if (!rc) rc = r;
+}
+
+inline int ensure(hg_ctx* c, Buf& b, size_t bytes) {
+    if (b.bytes >= bytes) return HG_OK;
+    if (b.p) HG_HIP(hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    bytes = (bytes + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) return fail(c, HG_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    // growth only (never in steady state): zero the padding rows and order the memset against every stream, also
+    // non-blocking ones that do not synchronise with the null stream
+    HG_HIP(hipMemset(b.p, 0, bytes));
+    HG_HIP(hipDeviceSynchronize());
+    b.bytes = bytes;
+    return HG_OK;
+}
+
+inline void free_all(std::vector<void*>& v) {
+    for (void* p : v) (void)hipFree(p);
+    v.clear();
+}
+
+inline size_t rup(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// hipEvent pair around one launch when its kind is being profiled
+struct ProfScope {
+    hg_ctx* c;
+    hipStream_t s;
+    bool on;
+    ProfScope(hg_ctx* c_, hipStream_t s_, int kind, int M, int N, int K) : c(c_), s(s_), on(false) {
+        if (c->prof_kind == HG_PROF_OFF || (c->prof_kind != HG_PROF_ALL && c->prof_kind != kind)) return;
+        if (2 * c->prof_n + 1 >= c->prof_ev.size()) return;
+        if (hipEventRecord(c->prof_ev[2 * c->prof_n], s) != hipSuccess) return;
+        c->prof_rec[c->prof_n] = hg_prof_rec{kind, M, N, K, 0.f};
+        on = true;
+    }
+    void finish() {
+        if (on && hipEventRecord(c->prof_ev[2 * c->prof_n + 1], s) == hipSuccess) c->prof_n++;
+        on = false;
+    }
+    ~ProfScope() { finish(); }
+};
+
+inline hipError_t gemm(hg_ctx* c, int epi, const GemmArgs& g, hipStream_t s) {
+    ProfScope ps(c, s, epi, g.M, g.N, g.K);
+    return launch_gemm(epi, g, s);
+}
+
+inline hipError_t attention(hg_ctx* c, const half_t* qkv, half_t* out, int n_seq, int L, int heads, bool causal, hipStream_t s,
+                     int ldo = 0) {
+    ProfScope ps(c, s, HG_PROF_ATTENTION, n_seq, L, heads);
+    return launch_attention(qkv, out, n_seq, L, heads, causal, s, ldo);
+}
+
+// the nine fields every GEMM call sets; what a call sets beyond them it sets behind this
+inline GemmArgs gemm_args(const half_t* A, int lda, const half_t* W, const float* bias, void* out, int ldc, int M, int N, int K) {
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.bias = bias; g.out = out; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+// hg_load.hip: the text tower's in_proj operands in the fused kernel's fragment order, packed on the first call that needs them
+int ensure_text_packs(hg_ctx* c, std::vector<void*>& owned, std::vector<BlockW>& blocks, int D, bool gamma);
+}  // namespace hg_host

@@ -1,0 +1,240 @@
+// Test hooks: single kernels behind the C ABI, operands rounded to fp16 on the device (tests/test_gpu_gemm.py, test_gpu_attention*.py).
+#include "hg_host.h"
+
+extern "C" {
+
+// Test hook: out[M,N] (fp32) (+)= epilogue(A[M,K] x W[N,K]^T) with the operands rounded to fp16 on the device.
+// kernel: 0 = dispatcher's choice, 1 = simple 128x128 kernel, 2 = persistent ring kernel.
+int hg_test_gemm(hg_ctx* c, const float* a, const float* w, const float* bias, float* out, int M, int N, int K,
+                 int epi, int kernel, void* stream) {
+    if (!c || !a || !w || !out || M <= 0) return HG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    int rc = ensure(c, c->h, rup(M, 256) * K * 2);
+    if (!rc) rc = ensure(c, c->att, (size_t)N * K * 2);
+    const bool f16out = (epi == EPI_BIAS_F16 || epi == EPI_BIAS_QGELU_F16 || epi == EPI_BIAS_RELU_F16);
+    if (!rc && f16out) rc = ensure(c, c->qkv, rup(M, 256) * N * 2);
+    // EPI_RESID_LN_F32 (timing only): centred fp16 copy into the qkv buffer, partial statistics + zero centres into cq
+    const bool rln = (epi == EPI_RESID_LN_F32);
+    const int sld = 4 * N / 256;
+    if (!rc && rln) rc = ensure(c, c->qkv, rup(M, 256) * N * 2);
+    if (!rc && rln) rc = ensure(c, c->cq, rup(M, 256) * (size_t)(2 * sld + 1) * 4);
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(a, (half_t*)c->h.p, (size_t)M * K, s));
+    HG_HIP(launch_f32_to_f16(w, (half_t*)c->att.p, (size_t)N * K, s));
+    GemmArgs g = gemm_args((half_t*)c->h.p, K, (half_t*)c->att.p, bias, f16out ? c->qkv.p : (void*)out, N, M, N, K);
+    if (rln) {
+        g.out2 = (half_t*)c->qkv.p; g.stats = (float*)c->cq.p; g.stats_ld = sld;
+        g.mu = (float*)c->cq.p + (size_t)rup(M, 256) * 2 * sld;
+        HG_HIP(hipMemsetAsync((void*)g.mu, 0, (size_t)M * 4, s));
+    }
+    hipError_t e;
+    ProfScope ps(c, s, epi, M, N, K);
+    if (kernel == 1) e = launch_gemm_simple(epi, g, s);
+    else if (kernel == 2) e = gemm_ring_ok(g) ? launch_gemm_ring(epi, g, s) : hipErrorInvalidValue;
+    else if (kernel == 3) e = gemm_duo_ok(epi, g) ? launch_gemm_duo(epi, g, s) : hipErrorInvalidValue;
+    else e = launch_gemm(epi, g, s);
+    ps.finish();
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test gemm launch failed: %s", hipGetErrorString(e));
+    if (f16out) HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, out, (size_t)M * N, s));
+    return HG_OK;
+}
+
+int hg_test_gemm_ln(hg_ctx* c, const float* a, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
+                    int kernel, const float* cs, const float* mr, const float* mu, const float* scale, float* out2,
+                    float* mr_out, float* mu_out, void* stream) {
+    if (!c || !a || !w || !out || M <= 0) return HG_ERR_INVALID;
+    const bool lnc = (epi == EPI_LN_BIAS_F16 || epi == EPI_LN_BIAS_QGELU_F16);
+    const bool rln = (epi == EPI_RESID_LN_F32 || epi == EPI_SCALE_RESID_LN_F32);
+    if (!lnc && !rln) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ln: epi must be 8, 9, 10 or 12");
+    if (lnc && (!cs || !mr)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ln: epi 8/9 need cs and mr");
+    if (rln && (!mu || !out2 || !mr_out || !mu_out || (epi == EPI_SCALE_RESID_LN_F32 && !scale)))
+        return fail(c, HG_ERR_INVALID, "hg_test_gemm_ln: epi 10/12 need mu, out2, mr_out, mu_out (12: scale)");
+    if (N % 256) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ln: N must be a multiple of 256");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Mp = rup(M, 256);
+    const int sld = 4 * (N / 256);
+    int rc = ensure(c, c->h, Mp * K * 2);
+    if (!rc) rc = ensure(c, c->att, (size_t)N * K * 2);
+    if (!rc) rc = ensure(c, c->qkv, Mp * N * 2);
+    if (!rc) rc = ensure(c, c->mr, Mp * 2 * 4);
+    if (!rc) rc = ensure(c, c->mu, Mp * 4);
+    if (!rc) rc = ensure(c, c->stats, Mp * (size_t)sld * 2 * 4);
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(a, (half_t*)c->h.p, (size_t)M * K, s));
+    HG_HIP(launch_f32_to_f16(w, (half_t*)c->att.p, (size_t)N * K, s));
+    GemmArgs g = gemm_args((half_t*)c->h.p, K, (half_t*)c->att.p, bias, nullptr, N, M, N, K);
+    if (lnc) {
+        HG_HIP(hipMemsetAsync(c->mr.p, 0, Mp * 2 * 4, s));                  // padded rows are read by the tile's DMA
+        HG_HIP(hipMemcpyAsync(c->mr.p, mr, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+        g.cs = cs; g.mr = (const float*)c->mr.p; g.out = c->qkv.p;
+    } else {
+        HG_HIP(hipMemcpyAsync(c->mu.p, mu, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+        g.out = out; g.out2 = (half_t*)c->qkv.p; g.stats = (float*)c->stats.p; g.stats_ld = sld; g.mu = (const float*)c->mu.p;
+        g.pos = scale;
+    }
+    hipError_t e;
+    if (kernel == 2) {
+        ProfScope ps(c, s, epi, M, N, K);
+        e = gemm_ln_ok(epi, g) ? launch_gemm_ring(epi, g, s) : hipErrorInvalidValue;
+    } else if (kernel == 3) e = gemm_duo_ok(epi, g) ? launch_gemm_duo(epi, g, s) : hipErrorInvalidValue;
+    else e = launch_gemm(epi, g, s);
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test gemm (ln) launch failed: %s", hipGetErrorString(e));
+    if (lnc) {
+        HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, out, (size_t)M * N, s));
+    } else {
+        HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, out2, (size_t)M * N, s));
+        HG_HIP(launch_finalize_stats((const float*)c->stats.p, (float*)c->mr.p, (float*)c->mu.p, M, sld, 64, s));
+        HG_HIP(hipMemcpyAsync(mr_out, c->mr.p, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+        HG_HIP(hipMemcpyAsync(mu_out, c->mu.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return HG_OK;
+}
+
+int hg_test_gemm_hilo(hg_ctx* c, const float* a, const float* w, const float* bias, float* x, int M, int N, int K, int steps,
+                      int hilo, float* mu, float* out2, float* mr_out, void* stream) {
+    if (!c || !a || !w || !x || !mu || M <= 0 || steps < 1 || steps > 16) return HG_ERR_INVALID;
+    if (N % 256) return fail(c, HG_ERR_INVALID, "hg_test_gemm_hilo: N must be a multiple of 256");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Mp = rup(M, 256);
+    const int sld = 4 * (N / 256);
+    int rc = ensure(c, c->h, Mp * K * 2);
+    if (!rc) rc = ensure(c, c->att, (size_t)N * K * 2);
+    if (!rc) rc = ensure(c, c->qkv, Mp * N * 2);
+    if (!rc) rc = ensure(c, c->mr, Mp * 2 * 4);
+    if (!rc) rc = ensure(c, c->mu, Mp * 4);
+    if (!rc) rc = ensure(c, c->muc, Mp * 4);
+    if (!rc) rc = ensure(c, c->stats, Mp * (size_t)sld * 2 * 4);
+    if (!rc) rc = ensure(c, c->xlo, gemm_lo_bytes(M, N));
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(a, (half_t*)c->h.p, (size_t)M * K, s));
+    HG_HIP(launch_f32_to_f16(w, (half_t*)c->att.p, (size_t)N * K, s));
+    HG_HIP(hipMemcpyAsync(c->mu.p, mu, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    GemmArgs g = gemm_args((half_t*)c->h.p, K, (half_t*)c->att.p, bias, x, N, M, N, K);
+    g.out2 = (half_t*)c->qkv.p; g.stats = (float*)c->stats.p; g.stats_ld = sld; g.mu = (const float*)c->mu.p;
+    g.lo = (half_t*)c->xlo.p; g.muc = (const float*)c->muc.p;
+    if (!gemm_ring2_ok(g)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_hilo: shape not eligible for gemm_ring2");
+    for (int i = 0; i < steps; ++i) {
+        g.hl = (hilo && steps >= 2) ? (i == 0 ? 1 : (i == steps - 1 ? 3 : 2)) : 0;
+        ProfScope ps(c, s, EPI_RESID_LN_F32, M, N, K);
+        hipError_t e = launch_gemm_ring2(EPI_RESID_LN_F32, g, s);
+        ps.finish();
+        if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test gemm (hi / lo) launch failed: %s", hipGetErrorString(e));
+        HG_HIP(launch_finalize_stats((const float*)c->stats.p, (float*)c->mr.p, (float*)c->mu.p, M, sld, 64, s, (float*)c->muc.p));
+    }
+    if (out2) HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, out2, (size_t)M * N, s));
+    if (mr_out) HG_HIP(hipMemcpyAsync(mr_out, c->mr.p, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+    HG_HIP(hipMemcpyAsync(mu, c->mu.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    return HG_OK;
+}
+
+int hg_test_attention(hg_ctx* c, const float* qkv, const float* q0, const int32_t* sel, int n_seq, int L, int heads,
+                      int causal, float* out, void* stream) {
+    if (!c || !qkv || !out || n_seq <= 0 || L < 1 || L > ATTN_LONG_MAX_L || heads < 1) return HG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const int D = heads * 64;
+    const size_t M = (size_t)n_seq * L;
+    int rc = ensure(c, c->qkv, rup(M, 256) * 3 * D * 2);
+    if (!rc) rc = ensure(c, c->att, rup(M, 256) * D * 2);
+    if (!rc && q0) rc = ensure(c, c->cq, rup(n_seq, 256) * (size_t)D * 2);
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(qkv, (half_t*)c->qkv.p, M * 3 * D, s));
+    if (q0) {      // one query row per sequence (row sel[seq], or 0): out [n_seq, D]
+        HG_HIP(launch_f32_to_f16(q0, (half_t*)c->cq.p, (size_t)n_seq * D, s));
+        HG_HIP(launch_attention_row0((const half_t*)c->qkv.p, (const half_t*)c->cq.p, sel, (half_t*)c->att.p, n_seq, L,
+                                     heads, (causal & 1) != 0, s));
+        HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)n_seq * D, s));
+    } else {
+        // (causal bit 1: the one-workgroup-per-item launch for L <= 32 instead of four items per workgroup - same bits: tests)
+        ProfScope ps(c, s, HG_PROF_ATTENTION, n_seq, L, heads);      // the kernel alone, as attention() above (tools/bench_vitl336.py)
+        HG_HIP(launch_attention((const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, (causal & 1) != 0, s, 0, !(causal & 2)));
+        ps.finish();
+        HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, M * D, s));
+    }
+    return HG_OK;
+}
+
+int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
+                     int L, int heads, int fused, float* out, void* stream) {
+    if (!c || !a || !w || !cs || !mr || !out || n_seq <= 0 || heads < 1) return HG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const int D = heads * 64, M = n_seq * L;
+    const int K = D + ((fused & 2) ? 64 : 0);      // (bit 1: a is [M, D + 64], w [3D, D + 64] - the shape of a block with a folded adapter)
+    // bit 2: the causal mask - the text tower's kernel (hg_qkv_attn_text.hip, L <= 80) against the folded GEMM + the causal attention launch
+    const bool causal = (fused & 4) != 0;
+    if ((fused & ~7) || (causal && (fused & 2))) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: fused must be 0 .. 5");
+    fused &= 1;
+    // (the folded ring GEMM wants 512 rows: a shorter causal call runs it over zero rows up to there - a row's result does not
+    // depend on the rows beside it)
+    const int Mg = causal && M < 512 ? 512 : M;
+    const size_t Mp = rup(Mg, 256);
+    if (fused && causal && !qkv_attn_text_ok(n_seq, L, D, heads, K))
+        return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused causal kernel");
+    if (fused && !causal && !qkv_attn_ok(n_seq, L, D, heads, K, K)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused kernel");
+    int rc = ensure(c, c->h, Mp * K * 2);
+    if (!rc) rc = ensure(c, c->fc, (size_t)3 * D * K * 2 * 2 + (size_t)(heads / 2 + 1) * 768 * 4);
+    if (!rc) rc = ensure(c, c->qkv, Mp * 3 * D * 2);
+    if (!rc) rc = ensure(c, c->att, Mp * D * 2);
+    if (!rc) rc = ensure(c, c->mr, Mp * 2 * 4);
+    if (rc) return rc;
+    half_t* w16 = (half_t*)c->fc.p;
+    half_t* wp = w16 + (size_t)3 * D * K;
+    float* bcs = (float*)(wp + (size_t)3 * D * K);
+    HG_HIP(hipMemsetAsync(c->h.p, 0, Mp * K * 2, s));
+    HG_HIP(launch_f32_to_f16(a, (half_t*)c->h.p, (size_t)M * K, s));
+    HG_HIP(launch_f32_to_f16(w, w16, (size_t)3 * D * K, s));
+    HG_HIP(hipMemsetAsync(c->mr.p, 0, Mp * 2 * 4, s));
+    HG_HIP(hipMemcpyAsync(c->mr.p, mr, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+    HG_HIP(hipMemsetAsync(c->att.p, 0, Mp * D * 2, s));
+    if (fused) {
+        HG_HIP(launch_pack_qkv(w16, bias, cs, wp, bcs, D, heads, s, K));
+        QkvAttnArgs qa{};
+        qa.x16 = (const half_t*)c->h.p; qa.lda = K; qa.K = K; qa.wp = wp; qa.bcs = bcs; qa.mr = (const float*)c->mr.p;
+        qa.out = (half_t*)c->att.p; qa.ldo = D; qa.n_seq = n_seq; qa.L = L; qa.D = D; qa.heads = heads;
+        qa.gsz = c->opt_qkv_attn_gsz; qa.a_bytes = (unsigned)(Mp * (size_t)K * 2);
+#ifdef HG_STAMPS
+        if (!(rc = ensure(c, c->cq, 256 * 8 * 16 * 8))) qa.dbg = (unsigned long long*)c->cq.p;      // read back by tools/qkv_attn_stamps.py
+        else return rc;
+        HG_HIP(hipMemsetAsync(c->cq.p, 0, 256 * 8 * 16 * 8, s));
+#endif
+        ProfScope ps(c, s, HG_PROF_QKV_ATTN, n_seq, L, heads);
+        hipError_t e = causal ? launch_qkv_attn_text(qa, s) : launch_qkv_attn(qa, s);
+        ps.finish();
+        if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test qkv_attn launch failed: %s", hipGetErrorString(e));
+#ifdef HG_STAMPS
+        {      // diagnostic build: median over workgroups of the per-wave s_memtime totals of every phase (hg_qkv_attn.hip QA_ST)
+            HG_HIP(hipStreamSynchronize(s));
+            std::vector<unsigned long long> hd((size_t)256 * 8 * 16);
+            HG_HIP(hipMemcpy(hd.data(), c->cq.p, hd.size() * 8, hipMemcpyDeviceToHost));
+            static const char* nm[14] = {"K loop", "drain+barrier", "barrier behind head a", "attention a", "barrier", "head b -> LDS",
+                                         "attention b", "barrier", "whole kernel", "LN fold", "head a -> LDS", "K loop: wait A", "K loop: barrier",
+                                         "K loop: wait W"};
+            for (int wv : {0, 3, 4, 6, 7}) {
+                fprintf(stderr, "[stamps] wave %d:", wv);
+                for (int k = 0; k < 14; ++k) {
+                    std::vector<unsigned long long> v;
+                    for (int b = 0; b < 256; ++b) if (hd[((size_t)b * 8 + wv) * 16 + 8]) v.push_back(hd[((size_t)b * 8 + wv) * 16 + k]);
+                    if (v.empty()) continue;
+                    std::sort(v.begin(), v.end());
+                    fprintf(stderr, " %s %llu |", nm[k], v[v.size() / 2]);
+                }
+                fprintf(stderr, "\n");
+            }
+        }
+#endif
+    } else {
+        GemmArgs g = gemm_args((const half_t*)c->h.p, K, w16, bias, c->qkv.p, 3 * D, Mg, 3 * D, K);
+        g.cs = cs; g.mr = (const float*)c->mr.p;
+        if (!gemm_ln_ok(EPI_LN_BIAS_F16, g)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the folded GEMM");
+        HG_HIP(gemm(c, EPI_LN_BIAS_F16, g, s));
+        HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, causal, s));
+    }
+    HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)M * D, s));
+    return HG_OK;
+}
+
+}  // extern "C"

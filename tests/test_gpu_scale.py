@@ -175,7 +175,7 @@ def test_mlp_pair_wait_that_cannot_end_is_an_error_not_a_hang(fullA):
 def test_mlp_pair_launches_from_two_streams_do_not_wait_for_each_other(fullA, g0):
     """Both towers run the MLP pair launch, whose 256 workgroups wait for each other: if encode_image on one stream and encode_text on
     another (two contexts) ever held part of the CUs each, both would sit out their bounds.  The library therefore serialises pair
-    launches of a device across streams from the moment a second stream shows up (hg_api.hip PairGate; tools/two_stream_pair_stress.py
+    launches of a device across streams from the moment a second stream shows up (hg_tower.hip PairGate; tools/two_stream_pair_stress.py
     is the long version of this test and ran clean with and without the gate - the gate closes a window, it does not fix a failure
     that was seen): both calls give the bits of the single-stream calls, no wait gives up (the next calls do not raise), and the two
     streams together take no longer than about the two calls one after the other."""

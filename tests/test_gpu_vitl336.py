@@ -20,7 +20,7 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TOL = 1e-3
 CFG = synth.VIT_L14_336
 L, GRID, D, E, LAYERS = 577, 24, 1024, 768, 24
-CHUNK = 256 * 224 // L          # crops per pass of the image tower at this length (hg_api.hip: image_chunk) = 99
+CHUNK = 256 * 224 // L          # crops per pass of the image tower at this length (hg_tower.hip: image_chunk) = 99
 
 
 def dev():
