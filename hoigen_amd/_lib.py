@@ -129,6 +129,7 @@ SIGNATURES = {
     "hg_test_gemm_hilo": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "hg_test_image_stream": (_I, [_P, _P, _I, _P, _P, _P]),
     "hg_test_text_stream": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "hg_test_adapter": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

@@ -748,6 +748,29 @@ hipError_t launch_rowstats_cast(const float* x, half_t* x16, float* mr, float* m
     return hipGetLastError();
 }
 
+// The copy and statistics rowstats_cast left (centre = the row's own mean) moved to the centre c[m] a preceding residual GEMM would have
+// used (its previous mean): x16 = fp16(x - c) with row stride ld16, mr[m][0] = mean - c, muc[m] = c; mu (the mean) and rstd stay.
+// Test hook only (hg_test_adapter).
+__global__ __launch_bounds__(256) void recentre_cast_kernel(const float* __restrict__ x, const float* __restrict__ c,
+                                                            half_t* __restrict__ x16, int ld16, float* __restrict__ mr,
+                                                            const float* __restrict__ mu, float* __restrict__ muc, int M, int D) {
+    const int r = blockIdx.x;
+    if (r >= M) return;
+    const float cr = c[r];
+    for (int k = threadIdx.x; k < D; k += 256) x16[(size_t)r * ld16 + k] = (half_t)(x[(size_t)r * D + k] - cr);
+    if (threadIdx.x == 0) {
+        mr[2 * (size_t)r] = mu[r] - cr;
+        muc[r] = cr;
+    }
+}
+hipError_t launch_recentre_cast(const float* x, const float* c, half_t* x16, int ld16, float* mr, const float* mu, float* muc, int M,
+                                int D, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    if (ld16 < D) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(recentre_cast_kernel, dim3(M), dim3(256), 0, s, x, c, x16, ld16, mr, mu, muc, M, D);
+    return hipGetLastError();
+}
+
 // partial statistics of row m over nt column groups of `gw` columns each: (sum_k, M2_k = sum (x - mean_k)^2);
 // combined with Chan's parallel-variance formula (no E[x^2] - mean^2 cancellation)
 __global__ void finalize_stats_kernel(const float* __restrict__ stats, float* __restrict__ mr, float* __restrict__ mu,

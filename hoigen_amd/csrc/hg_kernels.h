@@ -249,6 +249,9 @@ hipError_t launch_fold_ln(const half_t* w16, const float* gamma, const float* be
 // x fp32 [M,D] -> centred fp16 copy x16 = fp16(x - mean), mu[m] = mean, mr[m] = (0, rstd) (eps 1e-5, biased variance)
 hipError_t launch_rowstats_cast(const float* x, half_t* x16, float* mr, float* mu, int M, int D, hipStream_t s,
                                 float* muc = nullptr, const float* gamma = nullptr);   // muc (optional): centre of the copy as well (= mu)
+// behind rowstats_cast: the copy and mr moved to the centre c[m] (hg_test_adapter: the state a preceding residual GEMM leaves)
+hipError_t launch_recentre_cast(const float* x, const float* c, half_t* x16, int ld16, float* mr, const float* mu, float* muc, int M,
+                                int D, hipStream_t s);
 // x = LayerNorm(x; w, b) in place (fp32) followed by rowstats_cast of the result, in one pass (ln_pre of the vision tower)
 hipError_t launch_layernorm_rowstats(float* x, const float* w, const float* b, half_t* x16, float* mr, float* mu, float* muc,
                                      int M, int D, hipStream_t s, const float* pos = nullptr, const float* cls = nullptr,

@@ -712,6 +712,92 @@ int hg_encode_image_prior(hg_ctx* c, const float* x_nchw, const float* priors, c
                              (hipStream_t)stream);
 }
 
+// One launch of run_adapter on a caller-supplied stream, the workspace prepared as plan_tower and the step in front of the block leave it:
+// ln_pre in front of block 0 (centre = the row's mean) or, with `centre`, the preceding block's last residual GEMM (tests/test_gpu_adapter.py).
+// Refuses the shapes run_adapter has no path for; mode 2 takes any number of rows (plan_tower folds from 512 rows on: the launches of
+// mode 2 - down_proj on the simple GEMM or inside the decoder, one workgroup per sequence - do not depend on it), without the second
+// operand buffer e2 of the hi / lo stream (a second store of the same registers).
+int hg_test_adapter(hg_ctx* c, int block, int mode, const float* x, const float* centre, int n_seq, int L, int D, const float* priors,
+                    const uint8_t* mask, int N,
+                    float* out, float* copy_out, float* mr_out, float* muc_out, float* q_out, int32_t* path, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    Vit& v = c->vit;
+    if (!v.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vit has not been called");
+    if (block < 0 || block >= (int)v.adapters.size() || !v.adapters[block].present)
+        return fail(c, HG_ERR_INVALID, "hg_test_adapter: block %d carries no adapter", block);
+    if (mode < 0 || mode > 2) return fail(c, HG_ERR_INVALID, "hg_test_adapter: mode must be 0, 1 or 2 (got %d)", mode);
+    if (!x || !out || n_seq < 1 || L < 1) return fail(c, HG_ERR_INVALID, "hg_test_adapter: x, out, n_seq >= 1 and L >= 1 are needed");
+    if (L > ADAPTER_MAX_L) return fail(c, HG_ERR_INVALID, "hg_test_adapter: the adapters serve at most %d tokens (got %d)", ADAPTER_MAX_L, L);
+    if (priors && N < 1) return fail(c, HG_ERR_INVALID, "hg_test_adapter: priors given but N <= 0");
+    if (mode >= 1 && (!mr_out || !muc_out || (mode == 1 && !copy_out)))
+        return fail(c, HG_ERR_INVALID, "hg_test_adapter: modes 1 and 2 return mr and muc (mode 1: the fp16 copy as well)");
+    const AdapterW& a = v.adapters[block];
+    if (D != v.D) return fail(c, HG_ERR_INVALID, "hg_test_adapter: the stream is %d wide, the tower %d", D, v.D);
+    if (centre && mode == 0) return fail(c, HG_ERR_INVALID, "hg_test_adapter: mode 0 reads the fp32 stream, it has no centre");
+    const int M = n_seq * L, sld = 4 * (D / 256);
+    if (!priors) N = 0;
+    AdapterDev ad{};
+    for (int k = 0; k < 2; ++k) ad.w16[k][0] = a.w16[k][0];
+    const bool mfma = adapter_decoder_mfma_ok(ad, priors != nullptr, L, N);
+    const bool down_fused = mode == 2 && adapter_decoder_fused_down_ok(ad, priors != nullptr, L, N);
+    if (mode >= 1 && D % 256) return fail(c, HG_ERR_INVALID, "hg_test_adapter: LayerNorm folding needs a width that is a multiple of 256 (got %d)", D);
+    if (mode == 1) {      // plan_tower: folding stays on behind an adapter only where its up_proj can re-emit the copy and the statistics
+        float dummy = 0.f;
+        GemmArgs u = gemm_args(nullptr, 64, nullptr, nullptr, nullptr, D, M, D, 64);
+        u.out2 = (half_t*)&dummy; u.stats = &dummy; u.mu = &dummy; u.pos = &dummy; u.stats_ld = sld;
+        if (!gemm_duo_ok(EPI_SCALE_RESID_LN_F32, u))
+            return fail(c, HG_ERR_INVALID, "hg_test_adapter: mode 1 needs at least 512 rows (got %d): the scaled residual GEMM that re-emits the copy", M);
+    }
+    if (mode == 2) {
+        if (priors && N > 32) return fail(c, HG_ERR_INVALID, "hg_test_adapter: the folded adapter serves at most 32 prior tokens (got %d)", N);
+        if (!mfma || !a.fold[priors ? 0 : 1].wq_cat) return fail(c, HG_ERR_INVALID, "hg_test_adapter: this adapter was loaded without its folded operands");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Mp = rup(M, 256);
+    int rc = 0;
+    keep_first(rc, ensure(c, c->x, Mp * D * 4));
+    keep_first(rc, ensure(c, c->h, Mp * D * 2));
+    keep_first(rc, ensure(c, c->ad32, Mp * 128 * 4));
+    keep_first(rc, ensure(c, c->ad16, Mp * 64 * 2));
+    keep_first(rc, ensure(c, c->adkv, (size_t)n_seq * (priors ? N : L) * 64 * 4 * 2));
+    if (mode >= 1) {
+        keep_first(rc, ensure(c, c->mr, Mp * 2 * 4));
+        keep_first(rc, ensure(c, c->mu, Mp * 4));
+        keep_first(rc, ensure(c, c->muc, Mp * 4));
+        keep_first(rc, ensure(c, c->stats, Mp * (size_t)sld * 2 * 4));
+    }
+    if (mode == 2) keep_first(rc, ensure(c, c->att, Mp * (size_t)(D + 64) * 2));
+    if (rc) return rc;
+    HG_HIP(hipMemcpyAsync(c->x.p, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    // the centred fp16 copy, its centre and the statistics of the stream as the step in front of the block leaves them
+    if (mode >= 1) HG_HIP(launch_rowstats_cast((const float*)c->x.p, (half_t*)c->h.p, (float*)c->mr.p, (float*)c->mu.p, M, D, s, (float*)c->muc.p));
+    // ... or, with `centre`, as a preceding block's last residual GEMM + finalize_stats leave them: the copy written with the row's
+    // PREVIOUS mean as its centre, muc = that centre, mu = the mean, mr = (mean - centre, rstd)
+    if (centre) HG_HIP(launch_recentre_cast((const float*)c->x.p, centre, (half_t*)c->h.p, D, (float*)c->mr.p, (const float*)c->mu.p, (float*)c->muc.p, M, D, s));
+    if (mode == 2)      // ... in columns 0 .. D-1 of the in_proj operand buffer [x16 | e]
+        HG_HIP(hipMemcpy2DAsync(c->att.p, (size_t)(D + 64) * 2, c->h.p, (size_t)D * 2, (size_t)D * 2, M, hipMemcpyDeviceToDevice, s));
+    const AdapterCall ac{priors, priors ? mask : nullptr, N, true};
+    if (int r = run_adapter(c, a, n_seq, L, D, ac, s, mode >= 1, mode == 2, nullptr)) return r;
+    if (path) { path[0] = mfma ? 1 : 0; path[1] = down_fused ? 1 : 0; }
+    if (mode == 2) {
+        HG_HIP(hipMemcpy2DAsync(c->ad16.p, 64 * 2, (const half_t*)c->att.p + D, (size_t)(D + 64) * 2, 64 * 2, M, hipMemcpyDeviceToDevice, s));
+        HG_HIP(launch_f16_to_f32((const half_t*)c->ad16.p, out, (size_t)M * 64, s));
+        if (q_out) {      // Q as the block's GEMMs hold it: columns D .. D+63 of [W_out | Q] (h is free again: Mp >= 64 rows of D)
+            HG_HIP(hipMemcpy2DAsync(c->h.p, 64 * 2, a.fold[priors ? 0 : 1].wk_out + D, (size_t)(D + 64) * 2, 64 * 2, D, hipMemcpyDeviceToDevice, s));
+            HG_HIP(launch_f16_to_f32((const half_t*)c->h.p, q_out, (size_t)D * 64, s));
+        }
+    } else {
+        HG_HIP(hipMemcpyAsync(out, c->x.p, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (mode == 1) HG_HIP(launch_f16_to_f32((const half_t*)c->h.p, copy_out, (size_t)M * D, s));
+    if (mode >= 1) {
+        HG_HIP(hipMemcpyAsync(mr_out, c->mr.p, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+        HG_HIP(hipMemcpyAsync(muc_out, c->muc.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return HG_OK;
+}
+
 int hg_encode_text_ids(hg_ctx* c, const int32_t* ids, int T, int L, float* out, int trunc, void* stream) {
     return encode_text_ids_impl(c, ids, T, L, out, trunc, nullptr, stream);
 }

@@ -446,6 +446,48 @@ class VisionTransformer(nn.Module):
                                                         _stream_ptr(x.device)), "hg_test_image_stream")
         return out, tr
 
+    @torch.no_grad()
+    def adapter_launch(self, block: int, mode: int, x: torch.Tensor, prior=None, centre=None) -> dict:
+        """Test hook (hg_test_adapter): the instance adapter in front of ``block`` on the stream ``x [n_seq, L, D]`` alone; ``centre [n_seq, L]``
+        (modes 1 and 2): the centre of the fp16 copy the adapter reads, as a preceding block leaves it (default: the row's mean).
+        Returns ``out`` (mode 0 / 1: the updated stream [n_seq*L, D]; mode 2: e [n_seq*L, 64]), in modes 1 and 2 ``mr`` and ``muc``,
+        in mode 1 ``copy``, in mode 2 ``q`` (Q as the device holds it), and ``mfma`` / ``down_fused``: the decoder that ran and whether down_proj ran inside it."""
+        _require_cuda(x, "stream")
+        h = self._sync(x.device)
+        n_seq, L, D = x.shape
+        if D != self.transformer.width:
+            raise RuntimeError(f"hoigen_amd: the stream must be [n_seq, L, {self.transformer.width}], got {tuple(x.shape)}")
+        M = n_seq * L
+        cf = None if centre is None else centre.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        if cf is not None and cf.numel() != M:
+            raise RuntimeError(f"hoigen_amd: centre must hold one value per row ({M}), got {tuple(centre.shape)}")
+        xf = x.detach().to(torch.float32).contiguous()
+        pp = mp = None
+        N = 0
+        if prior is not None:
+            pri, mask = prior
+            pri_f = pri.detach().to(device=x.device, dtype=torch.float32).contiguous()
+            N = pri_f.shape[1]
+            pp = pri_f.data_ptr()
+            if mask is not None:
+                m8 = mask.to(device=x.device, dtype=torch.uint8).contiguous()
+                mp = m8.data_ptr()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        res = {"out": torch.empty(M, 64 if mode == 2 else D, **f32)}
+        if mode in (1, 2):
+            res["mr"], res["muc"] = torch.empty(M, 2, **f32), torch.empty(M, **f32)
+        if mode == 1:
+            res["copy"] = torch.empty(M, D, **f32)
+        if mode == 2:
+            res["q"] = torch.empty(D, 64, **f32)
+        path = (C.c_int32 * 2)(-1, -1)
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        self._ctx.check(_lib.lib().hg_test_adapter(h, block, mode, xf.data_ptr(), None if cf is None else cf.data_ptr(), n_seq, L, D, pp, mp, N,
+                                                   ptr("out"), ptr("copy"),
+                                                   ptr("mr"), ptr("muc"), ptr("q"), path, _stream_ptr(x.device)), "hg_test_adapter")
+        res["mfma"], res["down_fused"] = bool(path[0]), bool(path[1])
+        return res
+
 
 class TokenEmbedding(nn.Module):
     """nn.Embedding stand-in (``clip_model.token_embedding(ids)``, main_coop_vae.py:85,111)."""

@@ -374,6 +374,30 @@ int hg_test_qkv_attn(hg_ctx*, const float* a, const float* w, const float* bias,
 int hg_test_image_stream(hg_ctx*, const float* x_nchw, int B, float* out, float* trace, void* stream);
 int hg_test_text_stream(hg_ctx*, const int32_t* ids, int T, int L, int trunc, float* out, float* trace, void* stream);
 
+/* Test hook for the instance adapter in front of block `block` of a vision tower loaded with adapters (variant C;
+ * CLIP_models_adapter_prior2.py:183-203, :456): ONE call of the routine the tower runs there, on the caller's stream x [n_seq*L, D]
+ * fp32 (device; D must be the tower's width), 1 <= L <= 224 whatever the tower's own length; priors [n_seq, N, 64] fp32 and mask
+ * [n_seq, N] bytes (non-zero = pad) or NULL (memory = the sequence itself; mask alone may be NULL).  The workspace is prepared as a
+ * tower call leaves it in front of the block.  In modes 1 and 2 that is the centred fp16 copy of x, its centre muc, mu = the row mean
+ * and mr = (mean - muc, rstd): with centre == NULL as ln_pre leaves them in front of block 0 (muc = the mean, mr[.][0] = 0), with
+ * centre [n_seq*L] as a preceding block's last residual GEMM does (the copy is fp16(x - centre[m]), muc = centre, mr[.][0] = mean -
+ * centre: the row's previous mean in a tower).
+ *   mode 0  separate path: fp32 -> fp16 copy, down_proj GEMM, decoder, up_proj with the scaled residual epilogue.  out [M, D] = y.
+ *   mode 1  LayerNorm folding on, adapter not folded: out = y, copy_out [M, D] = the re-emitted fp16 copy (as fp32), mr_out [M, 2] and
+ *           muc_out [M] of y.  Needs M = n_seq * L >= 512.
+ *   mode 2  adapter folded into the block's GEMMs: out [M, 64] = e (fp16 values as fp32; the update is Q e), mr_out = the statistics of
+ *           x + Q e, muc_out, q_out [D, 64] (may be NULL) = Q as the block's GEMMs hold it (fp16 values).  down_proj runs inside the
+ *           decoder from L = 161 on.  Any number of rows: a tower folds the adapter from 512 rows on, but nothing this mode launches
+ *           depends on the row count (one workgroup per sequence; down_proj on the simple GEMM or inside the decoder).  The second
+ *           operand buffer of the hi / lo stream (a second store of e) is not written.
+ * path (host, may be NULL): path[0] = 1 MFMA decoder / 0 the fp32 one-lane-per-token kernels (N > 32), path[1] = 1 when down_proj ran inside
+ * the decoder.  HG_ERR_INVALID for what run_adapter has no path for or a tower refuses at load: L > 224, D other than the tower's, a
+ * width that is no multiple of 256 in modes 1 and 2, N > 32 in mode 2 or with adapter_num_layers > 1, fewer than 512 rows in mode 1,
+ * a centre in mode 0. */
+int hg_test_adapter(hg_ctx*, int block, int mode, const float* x, const float* centre, int n_seq, int L, int D, const float* priors,
+                    const uint8_t* mask, int N, float* out, float* copy_out, float* mr_out, float* muc_out, float* q_out,
+                    int32_t* path, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

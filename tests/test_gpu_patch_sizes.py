@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from hoigen_amd import synth
+from hoigen_amd import _lib, synth
 from hoigen_amd.model import build_model
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +77,60 @@ def test_width_768_with_257_tokens_vs_oracle():
         finally:
             for k, v in prev.items():
                 m.visual.set_option(k, v)
+
+
+@pytest.mark.parametrize("res", [60, 65])
+def test_width_256_with_adapters_on_either_side_of_the_fused_down_proj_switch(res):
+    """plan_tower's own choice (tests/test_gpu_adapter.py bypasses the plan): patch 5 on 60 x 60 / 65 x 65 crops = 145 / 170 tokens, below
+    and above the 161 from which down_proj runs inside the adapter's decoder; four crops (580 / 680 rows: LayerNorm folding on, the
+    adapters folded into the blocks' GEMMs), with priors and without, against the oracle in fp64."""
+    from oracle import clip_oracle as co
+    cfg = dict(synth.TINY, vision_width=256, vision_patch_size=5, image_resolution=res)
+    raw = synth.clip_state_dict(cfg, 31)
+    raw.update(synth.adapter_state_dict(cfg, 32))
+    m = build_model(synth.to_torch(raw), use_adapter=True, adapter_pos="all").float().to(dev())
+    assert m.visual.get_option("adapter_fold") == 1 and m.visual.get_option("ln_fuse") == 1
+    sd = {k: v.double() for k, v in co.as_tensors(raw).items() if k.startswith("visual.")}
+    img = torch.from_numpy(synth.crops(4, res, seed=res))
+    pri, mask = synth.priors(4, n=14, dim=64, n_pad=4, seed=33)
+    pri, mask = torch.from_numpy(pri), torch.from_numpy(mask)
+    for prior in (None, (pri, mask)):
+        want_g, want_l = co.visual_with_prior(sd, img.double(), None if prior is None else (pri.double(), mask), range(2), torch.float64)
+        args = (img.to(dev()), None if prior is None else (pri.to(dev()), mask.to(dev())))
+        m.visual(*args)      # (loads the weights: the context exists)
+        (got_g, got_l), recs = _lib.profile(m.visual._ctx.handle, _lib.HG_PROF_ALL, 64, lambda: m.visual(*args))
+        # what plan_tower chose, from the GEMM launches (kind, M, N, K): both blocks' in_proj over [x16 | e] (K = 256 + 64, folded
+        # LayerNorm), no up_proj launch (K = 64), and down_proj as a GEMM of its own (kind 11, N = 128) below 161 tokens only
+        gemms = [(k, M, N, K) for k, M, N, K, _ in recs]
+        M = 4 * ((res // 5) ** 2 + 1)
+        assert gemms.count((8, M, 768, 320)) == 2 and not [g for g in gemms if g[3] == 64], gemms
+        assert gemms.count((11, M, 128, 256)) == (2 if M // 4 < 161 else 0), gemms
+        tag = f"width 256, {(res // 5) ** 2 + 1} tokens, {'priors' if prior else 'no prior'}"
+        check(got_g, want_g, tag + ": global")
+        check(got_l.permute(0, 2, 3, 1), want_l.permute(0, 2, 3, 1), tag + ": local")
+
+
+def test_more_than_32_prior_tokens_through_the_tower():
+    """visual(x, (priors, mask)) with 40 prior tokens: the fp32 one-lane-per-token adapter kernels (adapter_kv_kernel,
+    adapter_decoder_kernel) on the tiny tower against the oracle; with adapter_num_layers = 2 the call is refused."""
+    from oracle import clip_oracle as co
+    raw = synth.clip_state_dict(synth.TINY, 10)
+    raw.update(synth.adapter_state_dict(synth.TINY, 13))
+    m = build_model(synth.to_torch(raw), use_adapter=True, adapter_pos="all").float().to(dev())
+    img = torch.from_numpy(synth.crops(3, 32, seed=11))
+    pri = torch.from_numpy(synth.hg_normal((3, 40, 64), 740))
+    mask = torch.zeros(3, 40, dtype=torch.bool)
+    mask[0, 33:] = True
+    mask[1, ::3] = True
+    mask[2, :39] = True
+    want_g, want_l = co.visual_with_prior(co.as_tensors(raw), img, (pri, mask), adapter_layers=range(2))
+    got_g, got_l = m.visual(img.to(dev()), (pri.to(dev()), mask.to(dev())))
+    check(got_g, want_g, "tiny tower, 40 prior tokens: global")
+    check(got_l.permute(0, 2, 3, 1), want_l.permute(0, 2, 3, 1), "tiny tower, 40 prior tokens: local")
+    raw.update(synth.adapter_state_dict(synth.TINY, 13, num_layers=2))
+    m2 = build_model(synth.to_torch(raw), use_adapter=True, adapter_pos="all", adapter_num_layers=2).float().to(dev())
+    with pytest.raises(RuntimeError, match="at most 32 prior tokens"):
+        m2.visual(img.to(dev()), (pri.to(dev()), mask.to(dev())))
 
 
 def test_update_adapters_refuses_a_tower_of_more_than_224_tokens():
