@@ -1,10 +1,12 @@
 """Attention for sequences of 225 .. 640 tokens (hg_attn_long.hip: the 577 tokens of ViT-L/14@336px) through hg_test_attention,
-against a plain PyTorch fp32 softmax(QK^T/8)V of the fp16-rounded inputs - the reference and the bound of tests/test_gpu_attention.py
-(2e-3 x max|want|: fp16 probabilities and fp16 output) - plus: two launches agree bit for bit, the one-row form is the full
-kernel's row, the maximum + 1 is refused, and a non-finite sequence stays in its own rows."""
+against an exact float64 softmax(QK^T/8)V of the fp16-rounded inputs on the CPU and the per-element rounding bound B of
+tests/attention_bound.py - the reference, the bound and the six input families of tests/test_gpu_attention.py - plus: two launches
+agree bit for bit, the one-row form is the full kernel's row, the maximum + 1 is refused, and a non-finite sequence stays in its own
+rows."""
 import pytest
 import torch
 
+import attention_bound as ab
 from hoigen_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -19,16 +21,6 @@ def ctx():
     assert h
     yield h
     _lib.lib().hg_destroy(h)
-
-
-def ref_attention(qkv, n_seq, L, heads, causal):
-    D = heads * 64
-    x = qkv.half().float().view(n_seq, L, 3, heads, 64)
-    q, k, v = (x[:, :, i].permute(0, 2, 1, 3) for i in range(3))          # [n, h, L, 64]
-    s = q @ k.transpose(-1, -2) * 0.125
-    if causal:
-        s = s + torch.full((L, L), float("-inf"), device=s.device).triu(1)
-    return (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3).reshape(n_seq * L, D)
 
 
 def run_full(ctx, qkv, n_seq, L, heads, causal):
@@ -66,14 +58,34 @@ CASES = [
 
 @pytest.mark.parametrize("n_seq,L,heads,causal", CASES)
 def test_long_attention_vs_fp32_reference(ctx, n_seq, L, heads, causal):
+    """(the name is from when the reference was fp32 PyTorch on the device: it is float64 on the CPU now, the bound per element, and
+    the earlier 2e-3 x max|want| on top of it)"""
     g = torch.Generator(device="cuda").manual_seed(L * 131 + heads)
     qkv = torch.randn(n_seq * L, 3 * heads * 64, device="cuda", generator=g) * 1.5
-    want = ref_attention(qkv, n_seq, L, heads, causal)
     got = run_full(ctx, qkv, n_seq, L, heads, causal)
-    err, top = (got - want).abs().max().item(), want.abs().max().item()
-    print(f"n_seq {n_seq} L {L} heads {heads} causal {causal}: max|d| {err:.3e} = {err / top:.3e} of max|want| {top:.3f}")
+    ref = ab.reference(qkv, n_seq, L, heads, causal)
+    w = ab.worst(got, ref)
+    err, top = (got.cpu().double() - ref["want"]).abs().max().item(), ref["want"].abs().max().item()
+    print(f"ATTN_RATIO long      randn1.5 causal {int(causal)} n_seq {n_seq} heads {heads} L {L}: worst |err| / B {w:.3f}; "
+          f"max|d| {err:.3e} = {err / top:.3e} of max|want| {top:.3f}")
+    assert w <= 1.0, f"worst |err| / B {w:.3f}"
     assert err <= 2e-3 * top
     assert torch.equal(got, run_full(ctx, qkv, n_seq, L, heads, causal)), "deterministic"
+
+
+# the first length, around every multiple of 16 and 32 a tile boundary falls on (half a key tile staged, one key short of a tile, a
+# full tile, one key into the next), 17 and more query tiles (a wave's second round), the maximum and the length below it
+SWEEP_L = (225, 240, 241, 256, 257, 272, 273, 522, 543, 544, 577, 609, 639, 640)
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("family", ab.FAMILIES)
+def test_long_lengths_within_the_bound(ctx, family, causal):
+    """each output element within B, a second launch bit-identical, `onehot` rows exact (attention_bound.sweep)"""
+    def run(qkv, n_seq, L, heads, causal):
+        return run_full(ctx, qkv.cuda(), n_seq, L, heads, causal).cpu()
+    failures = ab.sweep(run, "long", family, causal, SWEEP_L, 2, 2)
+    assert not failures, "\n".join(failures)
 
 
 def test_above_the_maximum_is_refused(ctx):
@@ -99,6 +111,26 @@ def test_one_row_variant_is_the_full_kernels_row(ctx, n_seq, L, heads, causal):
         q0 = qkv.view(n_seq, L, 3 * D)[torch.arange(n_seq, device="cuda"), idx, :D].contiguous()
         rows = run_rows(ctx, qkv, q0, sel, n_seq, L, heads, causal)
         assert torch.equal(rows, full[torch.arange(n_seq, device="cuda"), idx]), "same instruction sequence, same bits"
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("family", ["randn", "sink", "ramp"])
+def test_one_row_variant_on_hard_inputs(ctx, family, causal):
+    """rows 0 (sel = null and sel = 0), L - 1 and a random row of every sequence through the one-row kernel: the full kernel's bits
+    (which test_long_lengths_within_the_bound holds to the bound at these lengths)"""
+    n_seq, heads = 2, 2
+    D = heads * 64
+    ar = torch.arange(n_seq, device="cuda")
+    for L in (225, 577, MAX_L):
+        seed = ab.seed_of(family, L, causal, n_seq, heads)
+        qkv = ab.make_qkv(family, n_seq, L, heads, seed).cuda()
+        full = run_full(ctx, qkv, n_seq, L, heads, causal).view(n_seq, L, D)
+        rand = torch.randint(0, L, (n_seq,), generator=torch.Generator().manual_seed(seed), dtype=torch.int32).cuda()
+        for sel in (None, torch.zeros_like(rand), torch.full_like(rand, L - 1), rand):
+            idx = sel.long() if sel is not None else torch.zeros_like(ar)
+            q0 = qkv.view(n_seq, L, 3 * D)[ar, idx, :D].contiguous()
+            got = run_rows(ctx, qkv, q0, sel, n_seq, L, heads, causal)
+            assert torch.equal(got, full[ar, idx]), (L, None if sel is None else sel.tolist())
 
 
 @pytest.mark.parametrize("L", [577, 522])
