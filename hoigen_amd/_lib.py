@@ -88,6 +88,11 @@ class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
 
+class hg_test_gemm_ex_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("a", "w", "bias", "out", "out_hi", "pos", "scale", "mu", "cs", "gamma", "out2", "out3", "mr_out", "mu_out")] + \
+               [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldc", "epi", "kernel", "G", "L", "n_split", "ld2", "ld3", "chain", "stop")]
+
+
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 
 _P = C.c_void_p
@@ -123,6 +128,7 @@ SIGNATURES = {
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
     "hg_test_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "hg_test_gemm_ex": (_I, [_P, C.POINTER(hg_test_gemm_ex_args), _P]),
     "hg_test_gemm_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hg_test_qkv_attn": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),

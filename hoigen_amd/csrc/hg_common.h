@@ -27,6 +27,18 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const HG_GLOBAL void*)gsrc, (HG_LDS void*)lds_wave_base, 16, 0, 0);
 }
 
+// a * b + c, ONE rounding per element, for EPI_SCALE_RESID_F32 in the three kernels that have it (simple, ring, ring2): left to
+// -ffp-contract the compiler fuses `x + v * scale` in one of them and not in another, and a row's result then depends on which kernel
+// its batch size selects (tests/test_gpu_gemm.py::test_scaled_residual_epilogue).  EPI_SCALE_RESID_LN_F32 exists in the duo kernel only
+// (no second kernel to agree with) and is left as written there: with adapter_fuse = 0 / 1 a row goes through one or the other of the
+// two epilogues, which are not held bit for bit to each other.
+__device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) {
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = __builtin_fmaf(a[i], b[i], c[i]);
+    return r;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -60,7 +60,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, int m, int n, f32x4 
     } else if constexpr (EPI == EPI_SCALE_RESID_F32) {
         const f32x4 sc = *reinterpret_cast<const f32x4*>(p.pos + n);
         f32x4* dst = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n);
-        *dst = *dst + v * sc;
+        *dst = fma4(v, sc, *dst);
     } else if constexpr (EPI == EPI_BIAS_F32 || EPI == EPI_BIAS_RELU_F32 || EPI == EPI_MU_BIAS_RELU_F32) {
         if constexpr (EPI == EPI_BIAS_RELU_F32) {
 #pragma unroll

@@ -590,9 +590,9 @@ __device__ __forceinline__ void gemm_ring2_body(const GemmArgs& p, const int til
                             f32x4 v = acc[ha][hb][f][g2] + *reinterpret_cast<const f32x4*>(smem + BIAS_OFF + n * 4);
                             if constexpr (RESID) {
                                 if (INTERIOR || m < p.M) {
-                                    if constexpr (EPI == EPI_SCALE_RESID_F32) v *= *reinterpret_cast<const f32x4*>(p.pos + n);
-                                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n) =
-                                        xres[ha][hb][f][g2] + v;
+                                    f32x4* dst = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n);
+                                    if constexpr (EPI == EPI_SCALE_RESID_F32) *dst = fma4(v, *reinterpret_cast<const f32x4*>(p.pos + n), xres[ha][hb][f][g2]);
+                                    else *dst = xres[ha][hb][f][g2] + v;
                                 }
                             } else {
                                 epilogue_ring<EPI>(p, m, n, v);

@@ -609,8 +609,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
                         const int c = (rg * 2 + hb) * 2 + g2;
                         const int n = n0 + hb * 128 + wn * 32 + g2 * 16 + 4 * q;
                         f32x4 a = acc[ha][hb][f][g2] + *reinterpret_cast<const f32x4*>(smem + BIAS_OFF + n * 4);
-                        if constexpr (EPI == EPI_SCALE_RESID_F32) a *= *reinterpret_cast<const f32x4*>(p.pos + n);
-                        v[hb][g2] = xw[c % ROLL_W] + a;
+                        if constexpr (EPI == EPI_SCALE_RESID_F32) v[hb][g2] = fma4(a, *reinterpret_cast<const f32x4*>(p.pos + n), xw[c % ROLL_W]);
+                        else v[hb][g2] = xw[c % ROLL_W] + a;
                         if (m < p.M)
                             *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n) = v[hb][g2];
                         if (c + ROLL_W < 8 * MF) xw[c % ROLL_W] = chunk_load(c + ROLL_W);
@@ -674,10 +674,12 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
                         f32x4 v = acc[ha][hb][f][g2] + *reinterpret_cast<const f32x4*>(smem + BIAS_OFF + n * 4);
                         if constexpr (RESID) {
                             if (m < p.M) {
-                                if constexpr (EPI == EPI_SCALE_RESID_F32) v *= *reinterpret_cast<const f32x4*>(p.pos + n);
                                 f32x4* dst = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n);
-                                if constexpr (XPRE) *dst = xres[ha][hb][f][g2] + v;
-                                else *dst = *dst + v;
+                                f32x4 x;
+                                if constexpr (XPRE) x = xres[ha][hb][f][g2];
+                                else x = *dst;
+                                if constexpr (EPI == EPI_SCALE_RESID_F32) *dst = fma4(v, *reinterpret_cast<const f32x4*>(p.pos + n), x);
+                                else *dst = x + v;
                             }
                         } else {
                             epilogue_ring<EPI>(p, m, n, v);

@@ -4,7 +4,7 @@
 extern "C" {
 
 // Test hook: out[M,N] (fp32) (+)= epilogue(A[M,K] x W[N,K]^T) with the operands rounded to fp16 on the device.
-// kernel: 0 = dispatcher's choice, 1 = simple 128x128 kernel, 2 = persistent ring kernel.
+// kernel: 0 = dispatcher's choice, 1 = simple 128x128 kernel, 2 = persistent ring kernels, 3 = two-workgroups-per-CU (duo) kernel.
 int hg_test_gemm(hg_ctx* c, const float* a, const float* w, const float* bias, float* out, int M, int N, int K,
                  int epi, int kernel, void* stream) {
     if (!c || !a || !w || !out || M <= 0) return HG_ERR_INVALID;
@@ -127,6 +127,126 @@ int hg_test_gemm_hilo(hg_ctx* c, const float* a, const float* w, const float* bi
     if (out2) HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, out2, (size_t)M * N, s));
     if (mr_out) HG_HIP(hipMemcpyAsync(mr_out, c->mr.p, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
     HG_HIP(hipMemcpyAsync(mu, c->mu.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    return HG_OK;
+}
+
+// hg_test_gemm_ex, epi 10: gemm_ring2's residual epilogue with the copy's own row stride (ld2), the copy scaled by gamma (out3, ld3) and
+// the stream as fp32 (chain = 0: one launch) or as centre + hi + lo (chain >= 2 launches planned, hl = 1, 2 .., 3; the first `stop` made).
+// The fp16 buffers are filled with the byte 0x5A first, so that the columns behind N of a row come back as 203.25.
+static int gemm_ex_resid_ln(hg_ctx* c, const hg_test_gemm_ex_args* x, hipStream_t s) {
+    const int M = x->M, N = x->N, K = x->K, lda = x->lda, ldc = x->ldc;
+    const int ld2 = x->ld2 ? x->ld2 : ldc, ld3 = x->ld3 ? x->ld3 : ldc;
+    const int chain = x->chain, stop = chain ? x->stop : 1;
+    if (x->kernel != 4) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 10 runs on kernel 4 (ring2) here");
+    if (!x->mu || !x->out2 || !x->mr_out || !x->mu_out) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 10 needs mu, out2, mr_out, mu_out");
+    if (N % 256 || ld2 < N || ld3 < N || ld2 % 8 || ld3 % 8) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 10 needs N % 256 == 0, ld2 and ld3 >= N, multiples of 8");
+    if (chain && (chain < 2 || chain > 16 || stop < 1 || stop > chain)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: chain is 0 or 2 .. 16, 1 <= stop <= chain");
+    if (x->out3 && !x->gamma) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: out3 goes with gamma");
+    const size_t Mp = rup(M, 256);
+    const int sld = 4 * (N / 256);
+    GemmArgs g = gemm_args(nullptr, lda, nullptr, x->bias, x->out, ldc, M, N, K);
+    if (!gemm_ring2_ok(g)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: the shape is not eligible for kernel 4");
+    int rc = ensure(c, c->h, Mp * lda * 2);
+    if (!rc) rc = ensure(c, c->att, (size_t)N * K * 2);
+    if (!rc) rc = ensure(c, c->qkv, Mp * ld2 * 2);
+    if (!rc) rc = ensure(c, c->hg, Mp * ld3 * 2);
+    if (!rc) rc = ensure(c, c->mr, Mp * 2 * 4);
+    if (!rc) rc = ensure(c, c->mu, Mp * 4);
+    if (!rc) rc = ensure(c, c->muc, Mp * 4);
+    if (!rc) rc = ensure(c, c->stats, Mp * (size_t)sld * 2 * 4);
+    if (!rc) rc = ensure(c, c->xlo, gemm_lo_bytes(M, N));
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(x->a, (half_t*)c->h.p, (size_t)M * lda, s));
+    HG_HIP(launch_f32_to_f16(x->w, (half_t*)c->att.p, (size_t)N * K, s));
+    HG_HIP(hipMemcpyAsync(c->mu.p, x->mu, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    HG_HIP(hipMemsetAsync(c->qkv.p, 0x5A, Mp * ld2 * 2, s));
+    HG_HIP(hipMemsetAsync(c->hg.p, 0x5A, Mp * ld3 * 2, s));
+    g.A = (const half_t*)c->h.p; g.W = (const half_t*)c->att.p;
+    g.out2 = (half_t*)c->qkv.p; g.ld2 = ld2; g.stats = (float*)c->stats.p; g.stats_ld = sld; g.mu = (const float*)c->mu.p;
+    g.lo = (half_t*)c->xlo.p; g.muc = (const float*)c->muc.p;
+    g.gamma = x->gamma; g.out3 = (half_t*)c->hg.p; g.ld3 = ld3;
+    for (int i = 0; i < stop; ++i) {
+        g.hl = chain ? (i == 0 ? 1 : (i == chain - 1 ? 3 : 2)) : 0;
+        ProfScope ps(c, s, EPI_RESID_LN_F32, M, N, K);
+        hipError_t e = launch_gemm_ring2(EPI_RESID_LN_F32, g, s);
+        ps.finish();
+        if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test gemm (ex, epi 10) launch failed: %s", hipGetErrorString(e));
+        HG_HIP(launch_finalize_stats((const float*)c->stats.p, (float*)c->mr.p, (float*)c->mu.p, M, sld, 64, s, (float*)c->muc.p));
+    }
+    HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, x->out2, (size_t)M * ld2, s));
+    if (x->out3) HG_HIP(launch_f16_to_f32((const half_t*)c->hg.p, x->out3, (size_t)M * ld3, s));
+    HG_HIP(hipMemcpyAsync(x->mr_out, c->mr.p, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+    HG_HIP(hipMemcpyAsync(x->mu_out, c->mu.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    return HG_OK;
+}
+
+// One GEMM launch with the arguments the hooks above cannot set (include/hoigen_amd.h has the contract).  Nothing is launched unless the
+// chosen kernel's own eligibility test accepts the call.
+int hg_test_gemm_ex(hg_ctx* c, const hg_test_gemm_ex_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x || !x->a || !x->w || !x->out || x->M <= 0 || x->N <= 0 || x->K <= 0) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: a, w, out and M, N, K > 0 are required");
+    const int M = x->M, N = x->N, K = x->K, lda = x->lda, ldc = x->ldc, epi = x->epi;
+    const bool f16out = (epi == EPI_BIAS_F16 || epi == EPI_BIAS_QGELU_F16 || epi == EPI_BIAS_RELU_F16);
+    const bool f32out = (epi == EPI_BIAS_RESID_F32 || epi == EPI_BIAS_F32 || epi == EPI_PATCH_F32 || epi == EPI_BIAS_RELU_F32 ||
+                         epi == EPI_SCALE_RESID_F32 || epi == EPI_MU_BIAS_RELU_F32);
+    if (epi == EPI_RESID_LN_F32) {
+        if (lda < K || ldc < N || lda % 8 || ldc % 8) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: lda >= K, ldc >= N, both multiples of 8");
+        HG_ON_DEVICE(c);
+        return gemm_ex_resid_ln(c, x, (hipStream_t)stream);
+    }
+    if (!f16out && !f32out) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi must be 0 .. 7, 10 or 11");
+    // (two destinations: a row of either holds its own half only)
+    const int cols = x->out_hi ? (x->n_split > N - x->n_split ? x->n_split : N - x->n_split) : N;
+    if (lda < K || ldc < cols || lda % 8 || ldc % 8) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: lda >= K, ldc >= N (with out_hi: the wider half), both multiples of 8");
+    if (epi == EPI_PATCH_F32 && (x->G <= 0 || x->L <= x->G || M % x->G)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 5 needs 0 < G < L and M a multiple of G");
+    if (epi == EPI_SCALE_RESID_F32 && !x->scale) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 7 needs scale");
+    if (epi == EPI_MU_BIAS_RELU_F32 && (!x->mu || !x->cs || x->n_split < 0 || x->n_split % 16)) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: epi 11 needs mu, cs and n_split a multiple of 16");
+    if (x->out_hi && !((epi == EPI_BIAS_F32 || epi == EPI_BIAS_RELU_F32) && x->n_split > 0 && x->n_split < N && x->n_split % 16 == 0))
+        return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: out_hi goes with epi 4 / 6 and 0 < n_split < N, a multiple of 16");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    GemmArgs g = gemm_args(nullptr, lda, nullptr, x->bias, x->out, ldc, M, N, K);
+    g.G = x->G; g.L = x->L;
+    g.pos = epi == EPI_PATCH_F32 ? x->pos : (epi == EPI_SCALE_RESID_F32 ? x->scale : nullptr);
+    if (epi == EPI_MU_BIAS_RELU_F32) { g.mu = x->mu; g.cs = x->cs; g.n_split = x->n_split; }
+    if (x->out_hi) { g.out_hi = x->out_hi; g.n_split = x->n_split; }
+    const bool simple_ok = N % 128 == 0 && K % 64 == 0;
+    bool ok;
+    switch (x->kernel) {
+        case 0: ok = simple_ok || (epi != EPI_MU_BIAS_RELU_F32 && gemm_ring_ok(g)); break;
+        case 1: ok = simple_ok; break;
+        case 2: ok = epi != EPI_MU_BIAS_RELU_F32 && gemm_ring_ok(g); break;
+        case 3: ok = gemm_duo_ok(epi, g); break;
+        case 4: ok = epi != EPI_MU_BIAS_RELU_F32 && gemm_ring2_ok(g); break;
+        default: return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: kernel must be 0 .. 4");
+    }
+    if (!ok) return fail(c, HG_ERR_INVALID, "hg_test_gemm_ex: the shape or epilogue is not eligible for kernel %d", x->kernel);
+    const size_t Mp = rup(M, 256);
+    int rc = ensure(c, c->h, Mp * lda * 2);
+    if (!rc) rc = ensure(c, c->att, (size_t)N * K * 2);
+    if (!rc && f16out) rc = ensure(c, c->qkv, Mp * ldc * 2);
+    if (!rc && f16out) rc = ensure(c, c->cq, (size_t)M * N * 2);
+    if (!rc && f16out) rc = ensure(c, c->fc, (size_t)M * N * 4);
+    if (rc) return rc;
+    HG_HIP(launch_f32_to_f16(x->a, (half_t*)c->h.p, (size_t)M * lda, s));
+    HG_HIP(launch_f32_to_f16(x->w, (half_t*)c->att.p, (size_t)N * K, s));
+    g.A = (const half_t*)c->h.p; g.W = (const half_t*)c->att.p;
+    if (f16out) g.out = c->qkv.p;
+    hipError_t e;
+    {
+        ProfScope ps(c, s, epi, M, N, K);
+        if (x->kernel == 1) e = launch_gemm_simple(epi, g, s);
+        else if (x->kernel == 2) e = launch_gemm_ring(epi, g, s);
+        else if (x->kernel == 3) e = launch_gemm_duo(epi, g, s);
+        else if (x->kernel == 4) e = launch_gemm_ring2(epi, g, s);
+        else e = launch_gemm(epi, g, s);
+    }
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test gemm (ex) launch failed: %s", hipGetErrorString(e));
+    if (f16out) {      // the fp16 rows (stride ldc) -> dense -> fp32 -> the caller's rows (stride ldc): columns >= N of `out` stay untouched
+        HG_HIP(hipMemcpy2DAsync(c->cq.p, (size_t)N * 2, c->qkv.p, (size_t)ldc * 2, (size_t)N * 2, M, hipMemcpyDeviceToDevice, s));
+        HG_HIP(launch_f16_to_f32((const half_t*)c->cq.p, (float*)c->fc.p, (size_t)M * N, s));
+        HG_HIP(hipMemcpy2DAsync(x->out, (size_t)ldc * 4, c->fc.p, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyDeviceToDevice, s));
+    }
     return HG_OK;
 }
 

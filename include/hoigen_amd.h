@@ -323,9 +323,46 @@ int hg_profile_begin(hg_ctx*, int kind, int max_launches);
 int hg_profile_end(hg_ctx*, hg_prof_rec* recs, int max_recs, int32_t* n_recs);
 /* Test hook for the GEMM kernels: out[M,N] fp32 = epilogue(fp16(a[M,K]) x fp16(w[N,K])^T) (for the residual
  * epilogue `out` is read-modify-written).  epi: 0 bias->f16, 1 bias+QuickGELU->f16, 2 bias+ReLU->f16,
- * 3 bias+residual(f32), 4 bias->f32, 6 bias+ReLU->f32.  kernel: 0 auto, 1 simple 128x128, 2 persistent ring. */
+ * 3 bias+residual(f32), 4 bias->f32, 6 bias+ReLU->f32.  kernel: 0 auto, 1 simple 128x128, 2 persistent ring family,
+ * 3 two-workgroups-per-CU (duo) kernel; a shape the chosen kernel does not take is an error. */
 int hg_test_gemm(hg_ctx*, const float* a, const float* w, const float* bias, float* out, int M, int N, int K,
                  int epi, int kernel, void* stream);
+/* Test hook: ONE GEMM launch with the arguments hg_test_gemm / hg_test_gemm_ln cannot set.  All pointers are device fp32; a and w
+ * are rounded to fp16 inside, fp16 outputs (epi 0, 1, 2) come back as fp32.  Only columns < N of a row of `out` are written.
+ *   a [M, lda] (lda >= K), w [N, K], bias [N] or NULL, out [rows, ldc] (ldc >= N); lda and ldc multiples of 8
+ *   epi 0 .. 4, 6 as hg_test_gemm; with out_hi (epi 4 / 6): columns n >= n_split go to out_hi[m * ldc + n - n_split] (n_split % 16 == 0),
+ *          and ldc only has to hold the wider half
+ *   epi 5  patch embedding: row m = (b, t) of a, t < G, goes to out row b * L + 1 + t (+ pos[1 + t] when pos [L, N] is given);
+ *          out has (M / G) * L rows, the rows b * L are not written
+ *   epi 7  out += (acc + bias) * scale[n]
+ *   epi 11 out = relu(acc + mu[m] * cs[n] + bias[n]); with n_split > 0 the columns >= n_split stay linear (simple kernel only)
+ *   epi 10 (kernel 4 only) x [M, ldc] in `out` += acc + bias through gemm_ring2 + finalize_stats: mu [M] the copy's centre, out2 [M, ld2]
+ *          and out3 [M, ld3] (0 = ldc; whole rows come back, the columns behind N as 203.25), mr_out [M][2], mu_out [M] as hg_test_gemm_ln.
+ *          gamma [N] or NULL: the copy times gamma.  chain = 0: one launch on the fp32 stream (hl 0; out2 = the copy, scaled if gamma).
+ *          chain = 2 .. 16: launches planned with the stream as centre + hi + lo between them (hl 1, 2 .., 3), of which the first `stop`
+ *          are made: after a launch with hl 1 / 2 `out` is not written, out2 is the stream's unscaled hi half and out3 (gamma
+ *          given) the scaled copy; after the last (hl 3) `out` is the fp32 stream and out2 the copy, scaled if gamma
+ *   kernel 0 dispatcher, 1 simple 128x128, 2 ring family as the dispatcher enters it, 3 duo, 4 ring2 (128x256) directly
+ * HG_ERR_INVALID, and nothing launched, where the chosen kernel's own eligibility test (gemm_ring_ok, gemm_ring2_ok, gemm_duo_ok, the
+ * simple kernel's N % 128 and K % 64) refuses the call. */
+typedef struct {
+    const float* a;
+    const float* w;
+    const float* bias;
+    float* out;
+    float* out_hi;
+    const float* pos;
+    const float* scale;
+    const float* mu;
+    const float* cs;
+    const float* gamma;
+    float* out2;
+    float* out3;
+    float* mr_out;
+    float* mu_out;
+    int32_t M, N, K, lda, ldc, epi, kernel, G, L, n_split, ld2, ld3, chain, stop;
+} hg_test_gemm_ex_args;
+int hg_test_gemm_ex(hg_ctx*, const hg_test_gemm_ex_args* args, void* stream);
 /* Test hook for the LayerNorm-folded / statistics-emitting epilogues the vision tower actually runs:
  *   epi 8 / 9  (ring):  out = fp16( rstd[m] * (acc - mean[m] * cs[n]) + bias[n] ) [9: QuickGELU first], mr = [M][2] (mean, rstd)
  *   epi 10     (ring2 / duo): x[M,N] (in `out`, read-modify-written) += acc + bias; out2 = fp16(x' - mu[m]);
