@@ -45,10 +45,26 @@ __device__ __forceinline__ f32x4 quick_gelu4(f32x4 v, f32x4 kk) {
     return o;
 }
 
+// exp(t) = 2^E 2^a with E = rint(t log2 e) and a = t log2 e - E, log2 e held as the two floats c + cc: a is right to 2^-26, which leaves
+// the hardware exp2's 1 ulp as all of the error.  The expansion the compiler itself makes of expf, written out - because the library is
+// built with -ffp-contract=fast, under which the backend contracts that expansion too: (fl(t c) - E) becomes fma(t, c, -E), the residual
+// of the product (added on purpose, one line later) is then counted twice, and the result is off by ln 2 ulp(t log2 e) / 2 relative - 2.8
+// ulp at |t| = 8, growing with |t| (tests/test_gpu_vae_bound.py found it on log_var = +-16).  Here the product is made an opaque rounded
+// fp32 value first.  Beyond +-128 ln 2 the result saturates to inf / 0 through v_ldexp_f32; NaN stays NaN (the clamp keeps E an integer,
+// a carries the NaN).
+__device__ __forceinline__ float exp_f32(float t) {
+    constexpr float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;
+    float ph = t * c;
+    asm volatile("" : "+v"(ph));
+    const float e = fminf(fmaxf(rintf(ph), -300.0f), 300.0f);
+    const float a = (ph - e) + __builtin_fmaf(t, cc, __builtin_fmaf(t, c, -ph));
+    return ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
+}
+
 // z = exp(0.5 * log_var) * eps + mean (main_coop_vae.py:445-447), one expression for the stand-alone kernel and the GEMM
 // epilogue (a row's z must not depend on which of the two its chunk size selects)
 __device__ __forceinline__ float reparam1(float mean, float log_var, float eps) {
-    return __builtin_fmaf(expf(0.5f * log_var), eps, mean);
+    return __builtin_fmaf(exp_f32(0.5f * log_var), eps, mean);
 }
 
 template <int EPI>

@@ -182,7 +182,9 @@ struct VaeFusedArgs {
     int mode = 0;                    // 0 Encoder + Generator, 1 Encoder only, 2 Generator only
     bool has_enc = true;             // wp starts with the two encoder passes (mode 2 skips them)
 };
-bool vae_fused_ok(int dim, int eh, int gh);          // dim == 512, hidden widths multiples of 32 up to 4096
+// dim == 512, hidden widths (0: that net is absent) multiples of 32 up to 4096 - what the kernel can walk.  What loads is narrower: hg_load_vae
+// accepts hidden widths that are multiples of 128 only (the GEMM path's tiles), so 128, 256, ... 4096 are the widths that ever reach it.
+bool vae_fused_ok(int dim, int eh, int gh);
 size_t vae_fused_pass_bytes(int hidden);
 int vae_fused_rows_per_item();                        // 128
 inline size_t vae_fused_park_bytes(int R) { return (size_t)((R + 127) / 128) * 4 * 16 * 1024; }

@@ -274,7 +274,7 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *   "qkv_attn_c"      [HG_QKV_ATTN_C]      1 (default): also in the blocks whose instance adapter is folded into in_proj (variant C on the
  *                      hi / lo stream: the same kernel summing over D + 64 columns); 0: those blocks keep the two kernels.  Bit-identical.
  *   "vae_fused"       [HG_VAE_FUSED]       1: hg_vae_forward / hg_generator run Encoder -> reparameterise -> Generator as ONE kernel
- *                      (hoigen_amd/csrc/hg_vae_fused.hip: both hidden layers and z stay on chip; dim 512, hidden widths multiples of 32
+ *                      (hoigen_amd/csrc/hg_vae_fused.hip: both hidden layers and z stay on chip; dim 512, hidden widths multiples of 128
  *                      up to 4096) for the leading rows that fill whole rounds of its 128-row work items over the CUs, the GEMM path for
  *                      the rest (and for calls too small to fill 70 % of one round); 2: the one kernel for every row; 0: GEMM path only.
  *                      Same fp16 operand roundings on both paths; results differ by fp32 summation order.
