@@ -8,7 +8,7 @@
 // of 32, FFN 64-128-64, two LayerNorms) is 1.7 % of a block's FLOPs and runs in fp32 on the VALU:
 // one lane per token, the token's activations in a private LDS row, weights fetched with wave-uniform
 // (scalar-cache) loads so every FMA takes an SGPR weight operand.
-#include "hg_kernels.h"
+#include "hg_adapter_dev.h"
 
 namespace hg {
 
@@ -187,106 +187,8 @@ __global__ __launch_bounds__(64) void adapter_decoder_kernel(const float* __rest
 // token across the lane's registers and its four lane rows, and P . V with the probabilities used as the B operand
 // exactly where the score accumulators left them (key order inside a 32-key block permuted; V^T is stored in LDS in
 // that order).  Residual stream of the layer, LayerNorm statistics and softmax stay in fp32.
-struct DecW16 {
-    const half_t *Wq, *Wk, *Wv, *Wo, *W1, *W2;      // fp16 [out][in]: 64x64 (x4), 128x64, 64x128
-    const float *bq, *bk, *bv, *bo, *b1, *b2, *norms;   // norms = {norm2.w, norm2.b, norm3.w, norm3.b}
-};
-
-static constexpr int XP = 136;      // halfs per row of a wave's activation buffer (64 or 128 features + pad)
-static constexpr int KP = 72;       // halfs per row of K [key][64]
-static constexpr int NKMAX = ADAPTER_MAX_L;   // keys: 14 tiles of 16 (L <= 224)
-static constexpr int VP = NKMAX + 8;   // halfs per row of V^T [feature][key slot]
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float max_rows(float x) {      // max over the four 16-lane rows
-    x = fmaxf(x, __shfl_xor(x, 16, 64));
-    return fmaxf(x, __shfl_xor(x, 32, 64));
-}
-__device__ __forceinline__ float sum_rows4(float x) {
-    x += __shfl_xor(x, 16, 64);
-    return x + __shfl_xor(x, 32, 64);
-}
-
-// t[f][g] (+)= W[16g.., :] . X[16f.., :]^T over K = 32 * KS features; W global fp16 [.][ldw], X = LDS rows of pitch XP
-template <int G, int KS, int F>
-__device__ __forceinline__ void linear_T(f32x4 (&t)[F][G], const half_t* __restrict__ W, int ldw, const half_t* X, int lane) {
-    const int r = lane & 15, q = lane >> 4;
-    half8 xf[F][KS];
-#pragma unroll
-    for (int f = 0; f < F; ++f)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) xf[f][ks] = *reinterpret_cast<const half8*>(X + (16 * f + r) * XP + 32 * ks + 8 * q);
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const half8 wf = *reinterpret_cast<const half8*>(W + (size_t)(16 * g + r) * ldw + 32 * ks + 8 * q);
-#pragma unroll
-            for (int f = 0; f < F; ++f) t[f][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xf[f][ks], t[f][g], 0, 0, 0);
-        }
-}
-template <int G, int F>
-__device__ __forceinline__ void init_bias(f32x4 (&t)[F][G], const float* __restrict__ b, int lane) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(b + 16 * g + 4 * (lane >> 4));
-#pragma unroll
-        for (int f = 0; f < F; ++f) t[f][g] = bv;
-    }
-}
-template <int G, int F>
-__device__ __forceinline__ void store_T(const f32x4 (&t)[F][G], half_t* X, int lane) {
-    const int r = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int f = 0; f < F; ++f)
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            half4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h[e] = (half_t)t[f][g][e];
-            *reinterpret_cast<half4*>(X + (16 * f + r) * XP + 16 * g + 4 * q) = h;
-        }
-}
-// LayerNorm over the 64 features of every token (eps 1e-5, biased variance), in place; AFFINE = false: normalised values only
-template <bool AFFINE = true, int F>
-__device__ __forceinline__ void layer_norm_T(f32x4 (&t)[F][4], const float* __restrict__ w, const float* __restrict__ b, int lane) {
-    const int q = lane >> 4;
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) s += (t[f][g][0] + t[f][g][1]) + (t[f][g][2] + t[f][g][3]);
-        const float mean = sum_rows4(s) * (1.0f / 64.0f);
-        float v = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = t[f][g][e] - mean;
-                v = fmaf(d, d, v);
-            }
-        const float rstd = 1.0f / sqrtf(sum_rows4(v) * (1.0f / 64.0f) + 1e-5f);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            if constexpr (AFFINE) {
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + 16 * g + 4 * q), bv = *reinterpret_cast<const f32x4*>(b + 16 * g + 4 * q);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t[f][g][e] = (t[f][g][e] - mean) * rstd * wv[e] + bv[e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t[f][g][e] = (t[f][g][e] - mean) * rstd;
-            }
-        }
-    }
-}
-
-// key index -> slot inside the V^T rows: within a block of 32 keys, key 16*kt + 4*q + r sits at 8*q + 4*kt + r, which is
-// where the score accumulators of key tiles (2b, 2b+1) put it when they are packed as the P.V B operand
-__device__ __forceinline__ int key_slot(int key) {
-    const int w = key & 31;
-    return (key & ~31) + 8 * ((w & 15) >> 2) + 4 * (w >> 4) + (w & 3);
-}
+// The weight set DecW16, the LDS pitches XP / KP / VP and the register-tile helpers (linear_T, init_bias, store_T, layer_norm_T,
+// key_slot, max_rows, sum_rows4) are shared with the decoder of longer sequences (hg_adapter_long.hip): hg_adapter_dev.h.
 
 // F = 16-token tiles per wave: the workgroup has ceil(L / 16F) waves (F = 2: seven waves of 32 tokens at L = 197 - two
 // waves per SIMD hide each other's LDS round trips and weight fetches; F = 4: four waves of 64)
@@ -672,6 +574,11 @@ hipError_t launch_adapter_decoder(const float* down32, const AdapterDev& ad, con
     const int Nmem = priors ? N : L;
     const int n_rows = B * Nmem;
     if (n_rows <= 0) return hipSuccess;
+    // more than NKMAX tokens (option adapter_long): the chunked MFMA decoder of hg_adapter_long.hip - no folded mode, no down_proj inside
+    if (adapter_decoder_long_ok(ad, priors != nullptr, L, N)) {
+        if (F.mr || dn) return hipErrorInvalidValue;
+        return launch_adapter_decoder_long(down32, ad, priors, mask, B, L, N, kv, out16, s, chain32, ld16);
+    }
     if (adapter_decoder_mfma_ok(ad, priors != nullptr, L, N)) {
         const half_t* const* w = ad.w16[which];
         DecW16 Wd{w[0], w[1], w[2], w[3], w[4], w[5], dl[3], dl[4], dl[5], dl[7], dl[10], dl[11] + (size_t)2 * AD * AD, dl[8]};

@@ -18,6 +18,7 @@ const Option OPTIONS[] = {
     {"adapter_fuse", "HG_ADAPTER_FUSE", &hg_ctx::opt_adapter_fuse, true},
     {"adapter_fold", "HG_ADAPTER_FOLD", &hg_ctx::opt_adapter_fold, true},
     {"stream_hilo", "HG_STREAM_HILO", &hg_ctx::opt_stream_hilo, true},
+    {"adapter_long", "HG_ADAPTER_LONG", &hg_ctx::opt_adapter_long, true},
     {"qkv_attn", "HG_QKV_ATTN", &hg_ctx::opt_qkv_attn, false, 0, 2, "0, 1 or 2"},
     {"qkv_attn_text", "HG_QKV_ATTN_TEXT", &hg_ctx::opt_qkv_attn_text, false, 0, 2, "0, 1 or 2"},
     {"qkv_attn_min_seq", "HG_QKV_ATTN_MIN_SEQ", &hg_ctx::opt_qkv_attn_min_seq, false, 1, INT_MAX, ">= 1"},

@@ -348,6 +348,19 @@ hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t
     hipLaunchKernelGGL(f32_to_f16_kernel, dim3(grid), dim3(256), 0, s, in, out, n, vec);
     return hipGetLastError();
 }
+// lo of a weight held as hi + lo: 2^11 x fp16(w - fp16(w)) (weight-load time; the remainder itself would sit in fp16's subnormals)
+__global__ __launch_bounds__(256) void f16_remainder_kernel(const float* __restrict__ in, half_t* __restrict__ out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float x = in[i];
+        out[i] = (half_t)((x - (float)(half_t)x) * 2048.0f);
+    }
+}
+hipError_t launch_f16_remainder(const float* in, half_t* out, size_t n, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(f16_remainder_kernel, dim3(grid), dim3(256), 0, s, in, out, n);
+    return hipGetLastError();
+}
 hipError_t launch_f16_to_f32(const half_t* in, float* out, size_t n, hipStream_t s) {
     if (!n) return hipSuccess;
     const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;

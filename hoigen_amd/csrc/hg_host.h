@@ -47,6 +47,9 @@ struct BlockW {
     // rides in the activation copy (text tower, text_ln_fold = 1: hg_qkv_attn_text.hip); null elsewhere
     half_t* wpg_qkv;
     float* bcsg_qkv;
+    // c_proj as hi + lo on image towers beyond the short adapters' 224 tokens whose weights arrive in fp32: 2^11 x fp16(W - w_proj),
+    // used by calls that run instance adapters there (hg_load_vit; launch_mlp); null elsewhere
+    half_t* w_proj_lo;
 };
 
 struct AdapterW {
@@ -58,6 +61,8 @@ struct AdapterW {
     half_t* up_w = nullptr;    // [D, 64]
     float* up_b = nullptr;
     float* scale = nullptr;
+    half_t* up_w_lo = nullptr; // towers beyond 224 tokens, fp32 weights: 2^11 x fp16(W_up - up_w), and
+    float* scale_lo = nullptr; //   [D] 2^-11 x scale: the pass in front of up_proj that adds the remainder (run_adapter)
     // The adapter folded into the block's GEMMs altogether (hg_elem.hip adapter_q_kernel): a = Q e with e = the last decoder
     // layer's normalised output; [0] = prior path (last layer of the mhsa_layers chain), [1] = self path (mhsa)
     struct Fold {
@@ -83,6 +88,7 @@ struct Vit {
     half_t* w_projT = nullptr;
     half_t* w_projT_lo = nullptr;     // variant C of towers beyond the adapters' 224 tokens: 2^11 x the fp16 remainder of proj (hg_load_vit)
     float* proj_lo_scale = nullptr;   // [E] 2^-11, and [E] zeros behind it (the second pass's bias)
+    float* lo_scale = nullptr;        // the same for the blocks' width: [D] 2^-11, [D] zeros (BlockW::w_proj_lo, AdapterW::up_w_lo)
     std::vector<BlockW> blocks;
     std::vector<AdapterW> adapters;
     std::vector<void*> owned, owned_adapters;
@@ -157,6 +163,8 @@ struct hg_ctx {
     int opt_text_ln_fold = 1;    // text tower: 1 (default) LayerNorm folded into its GEMMs with the LayerNorm weight in the ACTIVATION copy (GemmArgs::gamma:
                                  // the GEMMs keep the layer's own fp16 weights - closer to the reference than the separate kernels, 4 % faster);
                                  // 2 the weight folded into fp16(W * gamma) as in the vision tower (10 % faster, 7.6e-4 instead of 6.2e-4); 0 separate kernels
+    int opt_adapter_long = 0;    // instance adapters on towers of 225 .. 640 tokens (hg_adapter_long.hip): 0 refuses them as before (at most 224 tokens),
+                                 // 1 accepts them - read at hg_load_vit, hg_update_adapters, the image entry points and hg_test_adapter
     int opt_qkv_attn_text = 0;   // text tower: in_proj + causal attention as one kernel for L <= 80 (hg_qkv_attn_text.hip; folded blocks): 0 two kernels,
                                  // 1 where it measured faster (qkv_attn_text_pays: profiles/qkv_attn_text.txt), 2 wherever the shapes allow
     int opt_qkv_attn_c = 1;      // ... also in the blocks that carry a folded adapter (variant C on the hi / lo stream: K = D + 64)
@@ -230,6 +238,11 @@ struct DevGuard {
     DevGuard dev_guard_(c);                                                                             \
     if (dev_guard_.err != hipSuccess)                                                                   \
         return fail(c, HG_ERR_HIP, "hipSetDevice(%d) failed: %s", (c)->device, hipGetErrorString(dev_guard_.err))
+// tokens per image a tower with instance adapters may have (option adapter_long), and what a refusal adds while the option could help
+inline int adapter_max_tokens(const hg_ctx* c) { return c->opt_adapter_long ? hg::ADAPTER_LONG_MAX_L : hg::ADAPTER_MAX_L; }
+inline const char* adapter_long_hint(const hg_ctx* c, int L) {
+    return !c->opt_adapter_long && L <= hg::ADAPTER_LONG_MAX_L ? "; set option adapter_long = 1 (up to 640 tokens)" : "";
+}
 // first failing status wins (OR-ing negative codes can turn OOM into another code)
 inline void keep_first(int& rc, int r) {
     if (!rc) rc = r;

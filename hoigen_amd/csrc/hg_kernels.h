@@ -222,6 +222,8 @@ hipError_t launch_clamp_eot(const int32_t* in, int n, int Leff, int32_t* out, in
 hipError_t launch_poison_if_flag(float* out, size_t n, const int32_t* flag, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);
 hipError_t launch_f16_to_f32(const half_t* in, float* out, size_t n, hipStream_t s);
+// out = 2^11 x fp16(in - fp16(in)): the lo operand of a weight held as hi + lo
+hipError_t launch_f16_remainder(const float* in, half_t* out, size_t n, hipStream_t s);
 // out[c][r] = in[r][c]  (fp32 or fp16 in -> fp16 out), used for `proj` / `text_projection` [in,out]
 hipError_t launch_transpose_to_f16(const void* in, int in_dtype, half_t* out, int rows, int cols, hipStream_t s);
 hipError_t launch_l2_normalize(const float* x, float* out, int R, int D, hipStream_t s);
@@ -282,6 +284,9 @@ hipError_t launch_roi_align(const float* feat, int C, int H, int W, const float*
 // ---- adapter (variant C) --------------------------------------------------------------------
 // tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
 static constexpr int ADAPTER_MAX_L = 224;
+// ... unless option adapter_long is on: up to 640 tokens on the decoder of hg_adapter_long.hip (query chunks of at most 224 tokens,
+// K and V of a sequence that is its own memory streamed through the same LDS area in key chunks); not folded into the block's GEMMs
+static constexpr int ADAPTER_LONG_MAX_L = 640;
 struct AdapterDev {      // device pointers, all fp32 except the two MFMA operands
     const half_t* down_w;   // [d, D] fp16
     const float* down_b;    // [d]
@@ -329,6 +334,11 @@ hipError_t launch_adapter_decoder(const float* down32, const AdapterDev& ad, con
                                   const AdapterDownDev* dn = nullptr);
 bool adapter_decoder_mfma_ok(const AdapterDev& ad, bool priors, int L, int N);
 bool adapter_decoder_fused_down_ok(const AdapterDev& ad, bool priors, int L, int N);
+// 224 < L <= 640 (hg_adapter_long.hip; launch_adapter_decoder goes there by itself): fp16 weights present and, with priors, N <= 32.
+// kv16 = the same scratch as `kv`, read as fp16 K [B][Lp][64] and V^T [B][64][Lp], Lp = L rounded up to 32 (self memory only)
+bool adapter_decoder_long_ok(const AdapterDev& ad, bool priors, int L, int N);
+hipError_t launch_adapter_decoder_long(const float* down32, const AdapterDev& ad, const float* priors, const uint8_t* mask, int B, int L,
+                                       int N, void* kv16, half_t* out16, hipStream_t s, float* chain32, int ld16);
 // weight-load time: Q (scratch q32 [D][64]) and the operands that carry it: down2 [128, D], wk_out [D, D+64] = [w_out | Q],
 // wq_cat [3D, D+64] = [wf_qkv | wf_qkv Q], qm [64], g16 [64][64]; norms = the last decoder layer's {norm2.w, norm2.b, norm3.w, norm3.b}
 hipError_t launch_adapter_fold(const half_t* up_w, const float* up_b, const float* scale, const float* norms,

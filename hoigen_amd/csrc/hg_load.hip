@@ -262,6 +262,16 @@ int load_adapters(hg_ctx* c, const hg_adapter_weights* src, int layers) {
         keep_first(rc, as_f32(c, own, s.up_proj_bias, D, &a.up_b, "adapter up_proj.bias"));
         keep_first(rc, as_f32(c, own, s.scale, D, &a.scale, "adapter scale"));
         if (rc) return rc < 0 ? rc : HG_ERR_INVALID;
+        if (v.lo_scale && s.up_proj_weight.dtype == HG_F32) {      // up_proj as hi + lo (hg_load_vit)
+            std::vector<float> sc_lo;
+            rc = to_host_f32(c, s.scale, D, sc_lo, "adapter scale");
+            for (float& f : sc_lo) f *= 1.0f / 2048.0f;
+            if (!rc) rc = upload_f32(c, own, sc_lo, &a.scale_lo);
+            if (!rc) rc = dev_alloc(c, own, (size_t)D * d * 2, (void**)&a.up_w_lo);
+            if (!rc && launch_f16_remainder((const float*)s.up_proj_weight.ptr, a.up_w_lo, (size_t)D * d, 0) != hipSuccess)
+                rc = fail(c, HG_ERR_HIP, "splitting adapter up_proj.weight into hi + lo failed");
+            if (rc) return rc;
+        }
         rc = load_decoder_layer(c, own, s.prior_layer, d, a.dl[0], a.w16[0]);
         if (rc) return rc;
         rc = load_decoder_layer(c, own, s.self_layer, d, a.dl[1], a.w16[1]);
@@ -273,7 +283,8 @@ int load_adapters(hg_ctx* c, const hg_adapter_weights* src, int layers) {
             rc = load_decoder_layer(c, own, s.extra_prior_layers[z], d, a.extra[z].dl, a.extra[z].w16);
             if (rc) return rc;
         }
-        if ((int)v.blocks.size() > i && v.blocks[i].w_out && v.blocks[i].wf_qkv) {
+        // (the adapter is folded into the block's GEMMs on towers of at most 224 tokens only: a longer one packs no folded operands)
+        if (v.L <= ADAPTER_MAX_L && (int)v.blocks.size() > i && v.blocks[i].w_out && v.blocks[i].wf_qkv) {
             std::vector<void*> sc;
             float* q32 = nullptr;
             keep_first(rc, dev_alloc(c, sc, (size_t)D * d * 4, (void**)&q32));
@@ -356,11 +367,12 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
     v.grid = v.res / p; v.L = v.grid * v.grid + 1; v.E = w->output_dim; v.Kp = im2col_kp(p);
     if (v.L > ATTN_LONG_MAX_L)
         return fail(c, HG_ERR_INVALID, "at most %d tokens per image supported (got %d)", ATTN_LONG_MAX_L, v.L);
-    if (v.L > ADAPTER_MAX_L)
+    if (v.L > adapter_max_tokens(c))
         for (int i = 0; w->adapters && i < w->layers; ++i)
             if (w->adapters[i].present)
                 return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d (patch %d, resolution "
-                                               "%d); load it without adapter weights (use_adapter=False)", ADAPTER_MAX_L, v.L, p, v.res);
+                                               "%d); load it without adapter weights (use_adapter=False)%s", adapter_max_tokens(c), v.L, p, v.res,
+                            adapter_long_hint(c, v.L));
     int rc = 0;
     const int K0 = 3 * p * p;
     if (v.Kp == K0) {
@@ -424,6 +436,25 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
     if (rc) return rc < 0 ? rc : HG_ERR_INVALID;
     rc = load_blocks(c, v.owned, w->blocks, v.layers, D, v.blocks, true);
     if (rc) return rc;
+    // The same remedy as proj's above where instance adapters run on such a tower (option adapter_long): the two GEMMs that write
+    // the residual stream from an operand with a mean far from zero - c_proj (QuickGELU's output) and the adapter's up_proj (a
+    // LayerNorm output with its bias) - get their weight as hi + lo.  The rounding of a weight column times the operand's mean is
+    // common to all tokens: of the 1.9e-3 by which fp16 weights move the sum of the local map of ViT-L/14@336px with adapters (fp32
+    // oracle, the sequence as memory), c_proj's rounding alone is 1.1e-3 and up_proj's 5e-4; in_proj, c_fc and out_proj together
+    // 3.5e-4.  Calls without adapters do not run the extra pass and keep their bits.
+    if (v.L > ADAPTER_MAX_L) {
+        std::vector<float> sb((size_t)2 * D, 0.f);
+        for (int d = 0; d < D; ++d) sb[d] = 1.0f / 2048.0f;
+        rc = upload_f32(c, v.owned, sb, &v.lo_scale);
+        for (int i = 0; i < v.layers && !rc; ++i) {
+            const hg_tensor& t = w->blocks[i].c_proj_weight;
+            if (t.dtype != HG_F32) continue;
+            rc = dev_alloc(c, v.owned, (size_t)4 * D * D * 2, (void**)&v.blocks[i].w_proj_lo);
+            if (!rc && launch_f16_remainder((const float*)t.ptr, v.blocks[i].w_proj_lo, (size_t)4 * D * D, 0) != hipSuccess)
+                rc = fail(c, HG_ERR_HIP, "splitting mlp.c_proj.weight into hi + lo failed");
+        }
+        if (rc) return rc < 0 ? rc : HG_ERR_OOM;
+    }
     rc = load_adapters(c, w->adapters, v.layers);
     if (rc) return rc;
     HG_HIP(hipDeviceSynchronize());
@@ -434,11 +465,11 @@ int hg_load_vit(hg_ctx* c, const hg_vit_weights* w) {
 int hg_update_adapters(hg_ctx* c, const hg_adapter_weights* adapters, int layers) {
     if (!c) return HG_ERR_INVALID;
     if (!c->vit.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_vit first");
-    if (c->vit.L > ADAPTER_MAX_L)
+    if (c->vit.L > adapter_max_tokens(c))
         for (int i = 0; adapters && i < layers; ++i)
             if (adapters[i].present)
-                return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d", ADAPTER_MAX_L,
-                            c->vit.L);
+                return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d%s", adapter_max_tokens(c),
+                            c->vit.L, adapter_long_hint(c, c->vit.L));
     HG_ON_DEVICE(c);
     HG_HIP(hipDeviceSynchronize());
     return load_adapters(c, adapters, layers);

@@ -74,8 +74,10 @@ struct TowerCall {
 // `cat`: the adapter folded into the block's GEMMs altogether - nothing but down_proj and the decoder runs here; the
 // centred fp16 copy of the stream is expected in columns 0..D-1 of c->att (row stride D + 64), the decoder writes e beside it and
 // turns c->mr into the statistics of x + a; the block's QKV GEMM then takes [x16 | e] x [W'_qkv | W'_qkv Q].  Workspace: plan_tower
+// `up_lo`: up_proj as hi + lo where the adapter carries the remainder (towers of more than 224 tokens, hg_load_vit): the tower's calls;
+// hg_test_adapter launches the decoder and the one-pass up_proj its float64 check restates
 int run_adapter(hg_ctx* c, const AdapterW& a, int n_seq, int L, int D, const AdapterCall& ac, hipStream_t s, bool fused,
-                bool cat, half_t* e2) {
+                bool cat, half_t* e2, bool up_lo) {
     const int M = n_seq * L;
     float* x = (float*)c->x.p;
     half_t* h = (half_t*)c->h.p;
@@ -107,7 +109,7 @@ int run_adapter(hg_ctx* c, const AdapterW& a, int n_seq, int L, int D, const Ada
     const int n_chain = ac.priors ? 1 + (int)a.extra.size() : 1;
     // chained layers exist only in the MFMA decoder (one workgroup per sequence, <= 32 prior tokens): say so up front
     // instead of failing inside the launch
-    if (n_chain > 1 && !adapter_decoder_mfma_ok(ad, true, L, ac.N))
+    if (n_chain > 1 && !adapter_decoder_mfma_ok(ad, true, L, ac.N) && !adapter_decoder_long_ok(ad, true, L, ac.N))
         return fail(c, HG_ERR_INVALID, "adapter_num_layers > 1 needs the MFMA decoder path: at most 32 prior tokens (got %d)", ac.N);
     for (int z = 0; z < n_chain; ++z) {
         if (z > 0)
@@ -133,6 +135,11 @@ int run_adapter(hg_ctx* c, const AdapterW& a, int n_seq, int L, int D, const Ada
     // x += up_proj(.) * scale   (adapter...:201-202, :456)
     GemmArgs g = gemm_args((const half_t*)c->ad16.p, 64, a.up_w, a.up_b, x, D, M, D, 64);
     g.pos = a.scale;
+    if (up_lo && a.up_w_lo) {      // x += ad16 x lo^T * (2^-11 scale), in front of the pass that re-emits the copy
+        GemmArgs lo = gemm_args((const half_t*)c->ad16.p, 64, a.up_w_lo, c->vit.lo_scale + D, x, D, M, D, 64);
+        lo.pos = a.scale_lo;
+        HG_HIP(gemm(c, EPI_SCALE_RESID_F32, lo, s));
+    }
     if (fused) {       // ... and re-emit the fp16 copy + row statistics of the updated stream for the folded ln_1
         const int sld = 4 * (D / 256);
         g.out2 = h; g.stats = (float*)c->stats.p; g.stats_ld = sld; g.mu = (const float*)c->mu.p;
@@ -449,6 +456,13 @@ int launch_mlp(hg_ctx* c, const TowerCall& t, const TowerPlan& p, const std::vec
                                c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, c->opt_mlp_pair_fault));
     } else {
         HG_HIP(gemm(c, p.fuse ? EPI_LN_BIAS_QGELU_F16 : EPI_BIAS_QGELU_F16, fc, s));
+        // c_proj as hi + lo (hg_load_vit) behind adapters on a tower of more than 224 tokens: x += fc x lo^T * 2^-11 on the fp32 stream
+        // (no adapter is folded there, so the stream is never hi + lo), in FRONT of the pass that emits the next LayerNorm's copy
+        if (w.w_proj_lo && b.adapter && !p.hilo) {
+            GemmArgs lo = gemm_args(p.fc, 4 * D, w.w_proj_lo, c->vit.lo_scale + D, p.x, D, p.M, D, 4 * D);
+            lo.pos = c->vit.lo_scale;
+            HG_HIP(gemm(c, EPI_SCALE_RESID_F32, lo, s));
+        }
         HG_HIP(gemm(c, b.emits ? EPI_RESID_LN_F32 : EPI_BIAS_RESID_F32, proj, s));
     }
     if (b.emits) HG_HIP(launch_finalize_stats(p.stats, p.mr, p.mu, p.M, p.sld, 64, s, p.muc, false, c->range_flag));
@@ -504,7 +518,7 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, const TowerCall& t)
     for (size_t i = 0; i < blocks.size(); ++i) {
         const BlockPlan& b = p.blocks[i];
         int rc = HG_OK;
-        if (b.adapter) rc = run_adapter(c, *b.adapter, t.n_seq, t.L, D, *t.ac, s, p.fuse, b.fold != nullptr, p.hilo_c ? p.att_o + D : nullptr);
+        if (b.adapter) rc = run_adapter(c, *b.adapter, t.n_seq, t.L, D, *t.ac, s, p.fuse, b.fold != nullptr, p.hilo_c ? p.att_o + D : nullptr, true);
         if (!rc) rc = launch_in_proj_attention(c, t, p, blocks[i], b);
         if (!rc && b.row0) return launch_row0_block(c, t, p, blocks[i], t.trace ? t.trace + (i + 1) * (size_t)t.trace_stride : nullptr);
         if (!rc) rc = launch_out_proj(c, t, p, blocks[i], b);
@@ -547,6 +561,11 @@ int encode_image_impl(hg_ctx* c, const float* x_nchw, const float* priors, const
     if (priors && (N <= 0 || !mask)) return fail(c, HG_ERR_INVALID, "priors given but N <= 0 or mask == NULL");
     HG_ON_DEVICE(c);
     const int D = v.D, L = v.L, G = L - 1, E = v.E;
+    if (variant_c && L > adapter_max_tokens(c))      // (a tower loaded with option adapter_long = 1, the option taken back since)
+        for (const AdapterW& a : v.adapters)
+            if (a.present)
+                return fail(c, HG_ERR_INVALID, "instance adapters support at most %d tokens per image: this tower has %d%s", adapter_max_tokens(c),
+                            L, adapter_long_hint(c, L));
     const size_t img = (size_t)3 * v.res * v.res;
     const int chunk = image_chunk(c, L);
     for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -727,7 +746,10 @@ int hg_test_adapter(hg_ctx* c, int block, int mode, const float* x, const float*
         return fail(c, HG_ERR_INVALID, "hg_test_adapter: block %d carries no adapter", block);
     if (mode < 0 || mode > 2) return fail(c, HG_ERR_INVALID, "hg_test_adapter: mode must be 0, 1 or 2 (got %d)", mode);
     if (!x || !out || n_seq < 1 || L < 1) return fail(c, HG_ERR_INVALID, "hg_test_adapter: x, out, n_seq >= 1 and L >= 1 are needed");
-    if (L > ADAPTER_MAX_L) return fail(c, HG_ERR_INVALID, "hg_test_adapter: the adapters serve at most %d tokens (got %d)", ADAPTER_MAX_L, L);
+    if (L > adapter_max_tokens(c))
+        return fail(c, HG_ERR_INVALID, "hg_test_adapter: the adapters serve at most %d tokens (got %d)%s", adapter_max_tokens(c), L, adapter_long_hint(c, L));
+    if (mode == 2 && L > ADAPTER_MAX_L)
+        return fail(c, HG_ERR_INVALID, "hg_test_adapter: the adapter folded into the block's GEMMs (mode 2) serves at most %d tokens (got %d)", ADAPTER_MAX_L, L);
     if (priors && N < 1) return fail(c, HG_ERR_INVALID, "hg_test_adapter: priors given but N <= 0");
     if (mode >= 1 && (!mr_out || !muc_out || (mode == 1 && !copy_out)))
         return fail(c, HG_ERR_INVALID, "hg_test_adapter: modes 1 and 2 return mr and muc (mode 1: the fp16 copy as well)");
@@ -739,6 +761,7 @@ int hg_test_adapter(hg_ctx* c, int block, int mode, const float* x, const float*
     AdapterDev ad{};
     for (int k = 0; k < 2; ++k) ad.w16[k][0] = a.w16[k][0];
     const bool mfma = adapter_decoder_mfma_ok(ad, priors != nullptr, L, N);
+    const bool mfma_long = adapter_decoder_long_ok(ad, priors != nullptr, L, N);
     const bool down_fused = mode == 2 && adapter_decoder_fused_down_ok(ad, priors != nullptr, L, N);
     if (mode >= 1 && D % 256) return fail(c, HG_ERR_INVALID, "hg_test_adapter: LayerNorm folding needs a width that is a multiple of 256 (got %d)", D);
     if (mode == 1) {      // plan_tower: folding stays on behind an adapter only where its up_proj can re-emit the copy and the statistics
@@ -778,8 +801,8 @@ int hg_test_adapter(hg_ctx* c, int block, int mode, const float* x, const float*
     if (mode == 2)      // ... in columns 0 .. D-1 of the in_proj operand buffer [x16 | e]
         HG_HIP(hipMemcpy2DAsync(c->att.p, (size_t)(D + 64) * 2, c->h.p, (size_t)D * 2, (size_t)D * 2, M, hipMemcpyDeviceToDevice, s));
     const AdapterCall ac{priors, priors ? mask : nullptr, N, true};
-    if (int r = run_adapter(c, a, n_seq, L, D, ac, s, mode >= 1, mode == 2, nullptr)) return r;
-    if (path) { path[0] = mfma ? 1 : 0; path[1] = down_fused ? 1 : 0; }
+    if (int r = run_adapter(c, a, n_seq, L, D, ac, s, mode >= 1, mode == 2, nullptr, false)) return r;
+    if (path) { path[0] = mfma_long ? 2 : mfma ? 1 : 0; path[1] = down_fused ? 1 : 0; }
     if (mode == 2) {
         HG_HIP(hipMemcpy2DAsync(c->ad16.p, 64 * 2, (const half_t*)c->att.p + D, (size_t)(D + 64) * 2, 64 * 2, M, hipMemcpyDeviceToDevice, s));
         HG_HIP(launch_f16_to_f32((const half_t*)c->ad16.p, out, (size_t)M * 64, s));

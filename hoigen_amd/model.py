@@ -451,7 +451,9 @@ class VisionTransformer(nn.Module):
         """Test hook (hg_test_adapter): the instance adapter in front of ``block`` on the stream ``x [n_seq, L, D]`` alone; ``centre [n_seq, L]``
         (modes 1 and 2): the centre of the fp16 copy the adapter reads, as a preceding block leaves it (default: the row's mean).
         Returns ``out`` (mode 0 / 1: the updated stream [n_seq*L, D]; mode 2: e [n_seq*L, 64]), in modes 1 and 2 ``mr`` and ``muc``,
-        in mode 1 ``copy``, in mode 2 ``q`` (Q as the device holds it), and ``mfma`` / ``down_fused``: the decoder that ran and whether down_proj ran inside it."""
+        in mode 1 ``copy``, in mode 2 ``q`` (Q as the device holds it), and ``mfma`` / ``down_fused``: the decoder that ran and whether down_proj ran inside it;
+        ``decoder``: 0 the fp32 one-lane-per-token kernels, 1 the MFMA decoder (at most 224 tokens), 2 the MFMA decoder of 225 .. 640 tokens
+        (option ``adapter_long``)."""
         _require_cuda(x, "stream")
         h = self._sync(x.device)
         n_seq, L, D = x.shape
@@ -485,7 +487,7 @@ class VisionTransformer(nn.Module):
         self._ctx.check(_lib.lib().hg_test_adapter(h, block, mode, xf.data_ptr(), None if cf is None else cf.data_ptr(), n_seq, L, D, pp, mp, N,
                                                    ptr("out"), ptr("copy"),
                                                    ptr("mr"), ptr("muc"), ptr("q"), path, _stream_ptr(x.device)), "hg_test_adapter")
-        res["mfma"], res["down_fused"] = bool(path[0]), bool(path[1])
+        res["mfma"], res["down_fused"], res["decoder"] = bool(path[0]), bool(path[1]), int(path[0])
         return res
 
 

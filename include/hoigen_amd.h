@@ -142,8 +142,9 @@ const char* hg_version(void);
  * size p that divides input_resolution (p = 16, 32: 8 pixels per thread; any other p, e.g. 14: one patch row per thread, the patch
  * GEMM's K = 3 p p padded with zeros to a multiple of 64, 588 -> 640); tokens per image L = (input_resolution / p)^2 + 1 <= 640
  * (ViT-B/16: 197, ViT-L/14: 257, ViT-L/14@336px: 577; L <= 224 and 225 .. 640 run different attention kernels).  Instance adapters
- * need L <= 224: adapter weights for a tower with more tokens are refused here and by hg_update_adapters (HG_ERR_INVALID, the
- * message says so); such a tower runs variants A and C-without-adapters (hg_encode_image_prior with priors == NULL). */
+ * need L <= 224, or L <= 640 with option "adapter_long" = 1 (set before the load): otherwise adapter weights for a tower with more
+ * tokens are refused here and by hg_update_adapters (HG_ERR_INVALID, the message says so); such a tower runs variants A and
+ * C-without-adapters (hg_encode_image_prior with priors == NULL). */
 int hg_load_vit(hg_ctx*, const hg_vit_weights*);
 int hg_load_text(hg_ctx*, const hg_text_weights*);
 int hg_load_vae(hg_ctx*, int slot, const hg_vae_weights*);
@@ -248,6 +249,14 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      form: "text_ln_fold"); 0: separate LayerNorm kernels everywhere
  *   "adapter_fuse"    [HG_ADAPTER_FUSE]    1: ... also around the instance adapters of variant C
  *   "adapter_fold"    [HG_ADAPTER_FOLD]    1: adapter update folded into the block's own GEMMs; 0: separate up_proj GEMM
+ *   "adapter_long"    [HG_ADAPTER_LONG]    0 (default): instance adapters need a tower of at most 224 tokens per image; 1: up to 640
+ *                      (ViT-L/14@336px: 577) on the decoder of hoigen_amd/csrc/hg_adapter_long.hip: a sequence in query chunks of at
+ *                      most 224 tokens, its K / V streamed in key chunks when it is its own memory; at most 32 prior tokens on MFMA
+ *                      (more: the fp32 one-lane-per-token kernels, adapter_num_layers = 1 only); never folded into the block's GEMMs.
+ *                      Read by hg_load_vit, hg_update_adapters, hg_encode_image_prior and hg_test_adapter: back at 0, a tower loaded
+ *                      under 1 is refused again at its next call.  Towers of at most 224 tokens run exactly as with 0.  Calls with
+ *                      adapters on a longer tower whose weights arrive in fp32 run c_proj and the adapters' up_proj as hi + lo fp16
+ *                      (a second GEMM pass each; hg_test_adapter launches the one-pass up_proj).
  *   "stream_hilo"     [HG_STREAM_HILO]     1: between the LayerNorm-folded blocks of variant A, of the text tower (and of variant C when every
  *                      block's adapter is folded into its GEMMs) the residual stream is held as
  *                      centre + hi + lo (the centred fp16 copy the GEMMs read + its remainder as bf8: read-only option
@@ -413,7 +422,7 @@ int hg_test_text_stream(hg_ctx*, const int32_t* ids, int T, int L, int trunc, fl
 
 /* Test hook for the instance adapter in front of block `block` of a vision tower loaded with adapters (variant C;
  * CLIP_models_adapter_prior2.py:183-203, :456): ONE call of the routine the tower runs there, on the caller's stream x [n_seq*L, D]
- * fp32 (device; D must be the tower's width), 1 <= L <= 224 whatever the tower's own length; priors [n_seq, N, 64] fp32 and mask
+ * fp32 (device; D must be the tower's width), 1 <= L <= 224 (640 with option adapter_long = 1: modes 0 and 1) whatever the tower's own length; priors [n_seq, N, 64] fp32 and mask
  * [n_seq, N] bytes (non-zero = pad) or NULL (memory = the sequence itself; mask alone may be NULL).  The workspace is prepared as a
  * tower call leaves it in front of the block.  In modes 1 and 2 that is the centred fp16 copy of x, its centre muc, mu = the row mean
  * and mr = (mean - muc, rstd): with centre == NULL as ln_pre leaves them in front of block 0 (muc = the mean, mr[.][0] = 0), with
@@ -427,8 +436,9 @@ int hg_test_text_stream(hg_ctx*, const int32_t* ids, int T, int L, int trunc, fl
  *           decoder from L = 161 on.  Any number of rows: a tower folds the adapter from 512 rows on, but nothing this mode launches
  *           depends on the row count (one workgroup per sequence; down_proj on the simple GEMM or inside the decoder).  The second
  *           operand buffer of the hi / lo stream (a second store of e) is not written.
- * path (host, may be NULL): path[0] = 1 MFMA decoder / 0 the fp32 one-lane-per-token kernels (N > 32), path[1] = 1 when down_proj ran inside
- * the decoder.  HG_ERR_INVALID for what run_adapter has no path for or a tower refuses at load: L > 224, D other than the tower's, a
+ * path (host, may be NULL): path[0] = 1 MFMA decoder / 2 the MFMA decoder of 225 .. 640 tokens / 0 the fp32 one-lane-per-token kernels
+ * (N > 32), path[1] = 1 when down_proj ran inside the decoder.  HG_ERR_INVALID for what run_adapter has no path for or a tower refuses
+ * at load: L > 224 (option adapter_long = 1: L > 640, and mode 2 at L > 224), D other than the tower's, a
  * width that is no multiple of 256 in modes 1 and 2, N > 32 in mode 2 or with adapter_num_layers > 1, fewer than 512 rows in mode 1,
  * a centre in mode 0. */
 int hg_test_adapter(hg_ctx*, int block, int mode, const float* x, const float* centre, int n_seq, int L, int D, const float* priors,

@@ -3,6 +3,7 @@
 kernel next to torch's scaled_dot_product_attention.  One JSON line on stdout; human-readable tables on stderr.
 
     python tools/bench_vitl336.py [--batch 64] [--steps 20] [--warmup 5] [--attn-batch 32] [--repeats 5]
+    python tools/bench_vitl336.py --adapters [--batch 64] [--steps 10] [--warmup 3] [--repeats 5]
 
 * `every_row` (option last_block_row0 = 0: every row of every block) and `class_rows` (the default: the last block on the class
   rows only): warm-up steps, then timed steps with a hipEvent on the compute stream between them (as bench.py); crops/s from the
@@ -14,6 +15,11 @@ kernel next to torch's scaled_dot_product_attention.  One JSON line on stdout; h
   torch.nn.functional.scaled_dot_product_attention on the same values, alternating, `--repeats` times each.  Both legs are timed
   between a hipEvent pair around the one launch, queued behind the same fp32 -> fp16 conversion of qkv (so that the host's launch
   latency falls into the conversion's run time for both).
+* `--adapters` (instead of all of the above): the detector's tower - variant C with instance adapters in front of every block, option
+  adapter_long = 1 (hg_adapter_long.hip) - with priors (N = 14) and with the sequence as the adapters' memory, beside variant C
+  without adapters: the three alternating `--repeats` times in one process, `--steps` timed steps each time; the median over the
+  repeats' median steps, min .. max beside it.  Under `rocprofv3 --kernel-trace --stats` the same run gives the decoder kernels' own
+  times (`--batch 99`: one full pass of 99 x 577 rows).
 """
 import argparse
 import json
@@ -56,6 +62,37 @@ def summary(per_step, batch):
             "frac_of_peak": round(cps * GFLOP_PER_CROP / 1e3 / MFMA_PEAK_TFLOPS, 4)}
 
 
+def bench_adapters(args):
+    dev = torch.device("cuda:0")
+    raw = synth.clip_state_dict(synth.VIT_L14_336, 0)
+    plain = build_model(synth.to_torch(raw), use_adapter=False).to(dev).visual
+    raw.update(synth.adapter_state_dict(synth.VIT_L14_336, 1))
+    adapted = build_model(synth.to_torch(raw), use_adapter=True).to(dev).visual
+    adapted.set_option("adapter_long", 1)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    x = torch.randn(args.batch, 3, 336, 336, device=dev, generator=gen)
+    pri, mask = synth.priors(args.batch, n=14, dim=64, n_pad=4, seed=99)
+    prior = (torch.from_numpy(pri).to(dev), torch.from_numpy(mask).to(dev))
+    legs = {"c_without_adapters": lambda: plain(x, None), "c_adapters_priors": lambda: adapted(x, prior),
+            "c_adapters_self": lambda: adapted(x, None)}
+    meds = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for k, fn in legs.items():
+            meds[k].append(statistics.median(timed_steps(fn, args.steps, args.warmup)))
+    res = {"metric": "vitl14_336_variant_c_adapters", "batch": args.batch, "steps": args.steps, "warmup": args.warmup,
+           "repeats": args.repeats, "device": torch.cuda.get_device_name(0)}
+    for k, v in meds.items():
+        res[k] = {"ms_per_step": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3),
+                  "crops_per_s": round(args.batch / statistics.median(v) * 1e3, 1)}
+        print(f"{k:22s} {res[k]['ms_per_step']:9.3f} ms ({res[k]['min']:.3f} .. {res[k]['max']:.3f})  {res[k]['crops_per_s']:8.1f} crops/s",
+              file=sys.stderr)
+    base = res["c_without_adapters"]["ms_per_step"]
+    for k in ("c_adapters_priors", "c_adapters_self"):
+        res[k]["over_without"] = round(res[k]["ms_per_step"] / base, 4)
+        res[k]["ms_per_adapter"] = round((res[k]["ms_per_step"] - base) / LAYERS, 4)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -63,8 +100,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--attn-batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--adapters", action="store_true", help="variant C with instance adapters (option adapter_long) beside variant C without")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
+    if args.adapters:
+        return bench_adapters(args)
     dev = torch.device("cuda:0")
     model = build_model(synth.to_torch(synth.clip_state_dict(synth.VIT_L14_336, 0))).to(dev)
     vis = model.visual
