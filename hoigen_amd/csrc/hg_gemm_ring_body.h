@@ -22,7 +22,11 @@ namespace hg {
 #define SEG_E(k) do {} while (0)
 #endif
 
-template <int MF, int EPI, bool PH2, class SCHED>
+// HL (EPI_RESID_LN_F32 at MF = 4, four phases; GemmArgs::hl): the residual stream as centre + hi + lo, in the very bytes the 128 x 256
+// kernel reads and writes (hg_gemm_ring2_body.h): 2 = hi + lo in, hi + lo out; 3 = hi + lo in, fp32 out.  SCHED::CONSUME: the A operand
+// is written by other workgroups of this launch on the same XCD (hg_mlp_pair256.hip): it is fetched past this CU's vector L1 (sc1); the
+// caller has waited for the row panel and runs the body on ONE tile per call, so the operand ring never reaches into a panel early.
+template <int MF, int EPI, bool PH2, int HL = 0, class SCHED>
 __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned a_bytes, const int mode, const SCHED& sc) {
 #if defined(__HIP_DEVICE_COMPILE__)   // device-only builtins (buffer resources, LDS DMA): host sees just the stub
     // mode >> 8: the start stagger's estimated cycles per K-tile (0 = off)
@@ -39,7 +43,10 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     // the next tile pass before its operands have landed)
     constexpr bool F16_STORES = (EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_QGELU_F16 || EPI == EPI_BIAS_RELU_F16 ||
                                  EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_QGELU_F16);
-    constexpr int E_RAW = RLN ? 8 * MF + 4 * MF + 2 * MF : (F16_STORES ? 4 * MF : 8 * MF);
+    constexpr bool IN_HL = (HL == 2 || HL == 3), OUT_HL = (HL == 2);
+    static_assert(HL == 0 || (IN_HL && RLN && MF == 4 && !PH2), "hi / lo stream: EPI_RESID_LN_F32 on 256 rows, four phases, hl 2 or 3");
+    // (HL: per pair of row tiles 4 copy + 2 statistics stores and 4 lo or 16 fp32 stores, four pairs)
+    constexpr int E_RAW = IN_HL ? (OUT_HL ? 40 : 88) : RLN ? 8 * MF + 4 * MF + 2 * MF : (F16_STORES ? 4 * MF : 8 * MF);
     constexpr int E = E_RAW > 52 ? 52 : E_RAW;
     // RESID at MF = 2: the residual rows are fetched one K-tile before the epilogue (64 spare VGPRs)
     constexpr bool XPRE = RESID && MF == 2;
@@ -50,7 +57,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     // dead by then, the accumulators die chunk by chunk)
     constexpr bool ROLL = RESID && MF == 4;
     constexpr int ROLL_W = RLN ? 6 : 8;               // 8 with the LayerNorm extras spills 3 VGPRs
-    constexpr int R = XPRE ? E : (ROLL ? ROLL_W + (RLN ? 1 : 0) : 0);   // prefetch loads per wave in the last K-tile
+    // (HL: the first pair of row tiles' 4 hi + 4 lo pieces and their 2 + 2 centres)
+    constexpr int R = XPRE ? E : (IN_HL ? 12 : ROLL ? ROLL_W + (RLN ? 1 : 0) : 0);   // prefetch loads per wave in the last K-tile
     // PUB (SCHED::PUBLISH, the MLP pair kernel's c_fc): the output tile is handed to OTHER workgroups of this launch, all of them ON THE
     // SAME XCD (the schedule deals a row panel's producers and consumers to one hardware XCC id, hg_mlp_pair.hip): plain stores.  Every
     // wave's stores of tile r have retired, i.e. are in that XCD's L2, once it has passed the counted wait of the first phase of the
@@ -159,7 +167,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     auto dma_A = [&](int h, auto I) {
         constexpr int i = decltype(I)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (HG_LDS void*)(smem + ld_buf + h * AH + wave * GA * 1024), 16,
-                                                 voffA[h][i], ld_sA + ld_kt * (BK * 2), i * 1024, 0);
+                                                 voffA[h][i], ld_sA + ld_kt * (BK * 2), i * 1024, SCHED::CONSUME ? 16 /* sc1 */ : 0);
     };
     auto dma_W = [&](int h, auto I) {
         constexpr int i = decltype(I)::value;
@@ -314,8 +322,41 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
         f32x4 xres[XPRE ? 2 : 1][XPRE ? 2 : 1][XPRE ? MF : 1][XPRE ? 2 : 1];
         // rolling residual window (ROLL): chunk c = ((ha * MF + f) * 2 + hb) * 2 + g2 is this lane's f32x4 of row
         // m0 + ha*BM/2 + wm*MF*16 + f*16 + (lane&15), columns n0 + hb*128 + wn*32 + g2*16 + 4*(lane>>4)
-        f32x4 xw[ROLL ? ROLL_W : 1];
+        f32x4 xw[ROLL && !IN_HL ? ROLL_W : 1];
         float muw[RLN ? 2 : 1];
+        // (HL) the stream comes in as in the 128 x 256 kernel, whose tile (2 tm + ha, tn) a half ha of this tile is: a pair of row tiles
+        // f = 2 fp, 2 fp + 1 of this wave is what that kernel's wave fp * 4 + wn holds in its half wm.  Unit u = ha * 2 + fp: hi as
+        // paired 16-byte pieces of the row-major copy, lo as that wave's own pieces, the rows' old and new centres.  One unit is held
+        // at a time: the first is fetched in the last K-tile, the next one while a unit is worked on.
+        typedef unsigned u32x4_hl __attribute__((ext_vector_type(4)));
+        typedef unsigned u32x2_hl __attribute__((ext_vector_type(2)));
+        u32x4_hl xhi[IN_HL ? 2 : 1][IN_HL ? 2 : 1];      // [hb][g2]
+        u32x2_hl xlo[IN_HL ? 2 : 1][IN_HL ? 2 : 1];
+        float muv[IN_HL ? 2 : 1], mucv[IN_HL ? 2 : 1];  // [f & 1]
+        const int tiles_n = p.N / 256;
+        auto lo_ptr = [&](int u, int hb, int g2) {
+            return p.lo + ((((size_t)(2 * tm + (u >> 1)) * tiles_n + tn) * 8 + ((u & 1) * 4 + wn)) * 8 + (wm * 4 + hb * 2 + g2)) * 256 + lane * 4;
+        };
+        auto unit_load = [&](int u) {
+            const int qq = lane >> 4;
+            const int mb = m0 + (u >> 1) * (BM / 2) + wm * MF * 16 + (u & 1) * 32 + (lane & 15);
+            int mp = mb + ((qq & 1) ? 16 : 0);
+            mp = mp < p.M ? mp : p.M - 1;
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                for (int g2 = 0; g2 < 2; ++g2) {
+                    xhi[hb][g2] = *reinterpret_cast<const u32x4_hl*>(p.out2 + (size_t)mp * p.ld2 + n0 + hb * 128 + wn * 32 + g2 * 16 + 4 * (qq & ~1));
+                    xlo[hb][g2] = *reinterpret_cast<const u32x2_hl*>(lo_ptr(u, hb, g2));
+                }
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                int m = mb + f * 16;
+                m = m < p.M ? m : p.M - 1;
+                muv[f] = p.mu[m];
+                mucv[f] = p.muc[m];
+            }
+        };
         auto chunk_row = [&](int rg) {
             int m = m0 + (rg / MF) * (BM / 2) + wm * MF * 16 + (rg % MF) * 16 + (lane & 15);
             return m < p.M ? m : p.M - 1;
@@ -443,7 +484,9 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
                                                              (m0 + wave * (BM / 8)) * 8, 0, 0);
             }
             if (g + 1 < S) issue_A(1, 0, GA);     // A1 of position g+1 (ld state already at g+1)
-            if constexpr (ROLL) {
+            if constexpr (IN_HL) {
+                if (xl) unit_load(0);
+            } else if constexpr (ROLL) {
                 if (xl) {      // first ROLL_W residual chunks (+ the first row group's centre) of this tile
 #pragma unroll
                     for (int c = 0; c < ROLL_W; ++c) xw[c] = chunk_load(c);
@@ -586,6 +629,122 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             };
             if (m0 + BM <= p.M) f16_epilogue(std::true_type{});
             else f16_epilogue(std::false_type{});
+        } else if constexpr (IN_HL) {
+            // the 128 x 256 kernel's epilogue (hg_gemm_ring2_body.h), unit by unit: the same expressions in the same order on the same
+            // accumulator bits, so a row leaves with the bits that kernel gives it - stream, copy, partial statistics and lo bytes
+            const int q = lane >> 4;
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            const int sg = tn * 4 + wn;                     // column group of this wave
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int ha = u >> 1, fp = u & 1;
+                if (m0 + ha * (BM / 2) >= p.M) break;      // (the chip's last panel may have one 128-row half only: no such tile, no lo bytes)
+                half4 hin[2][2][2];                        // [f][hb][g2]
+                u32x2 lraw[2][2];
+                float mu_u[2], muc_u[2];
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                    for (int g2 = 0; g2 < 2; ++g2) {
+                        const u32x4 o = xhi[hb][g2];
+                        const auto s0 = __builtin_amdgcn_permlane16_swap(o[0], o[2], false, false);
+                        const auto s1 = __builtin_amdgcn_permlane16_swap(o[1], o[3], false, false);
+                        hin[0][hb][g2] = __builtin_bit_cast(half4, u32x2{(unsigned)s0[0], (unsigned)s1[0]});
+                        hin[1][hb][g2] = __builtin_bit_cast(half4, u32x2{(unsigned)s0[1], (unsigned)s1[1]});
+                        lraw[hb][g2] = xlo[hb][g2];
+                    }
+#pragma unroll
+                for (int f = 0; f < 2; ++f) { mu_u[f] = muv[f]; muc_u[f] = mucv[f]; }
+                __builtin_amdgcn_sched_barrier(0);
+                if (u + 1 < 4 && m0 + ((u + 1) >> 1) * (BM / 2) < p.M) unit_load(u + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                half4 h16[2][2][2];                         // [f][hb][g2]: the new copy (hi)
+                unsigned l8[OUT_HL ? 2 : 1][OUT_HL ? 2 : 1][OUT_HL ? 2 : 1];      // the remainder as four bf8 (e5m2)
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    const int m = m0 + ha * (BM / 2) + wm * MF * 16 + fp * 32 + f * 16 + (lane & 15);
+                    f32x4 v[2][2];
+                    float sum = 0.f;
+#pragma unroll
+                    for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                        for (int g2 = 0; g2 < 2; ++g2) {
+                            const int n = n0 + hb * 128 + wn * 32 + g2 * 16 + 4 * q;
+                            f32x4 xin, lin;
+                            {
+                                const auto a = __builtin_amdgcn_cvt_pk_f32_bf8((int)lraw[hb][g2][f], false);
+                                const auto b = __builtin_amdgcn_cvt_pk_f32_bf8((int)lraw[hb][g2][f], true);
+                                lin = f32x4{a[0], a[1], b[0], b[1]};
+                            }
+                            const f32x2 mc2 = {muc_u[f], muc_u[f]};
+#pragma unroll
+                            for (int e2 = 0; e2 < 2; ++e2) {      // (centre + hi) + lo, two elements per instruction
+                                const half2v h2 = {hin[f][hb][g2][2 * e2], hin[f][hb][g2][2 * e2 + 1]};
+                                const f32x2 ls2 = {1.0f / HG_LO_SCALE, 1.0f / HG_LO_SCALE};
+                                const f32x2 x2 = f32x2{lin[2 * e2], lin[2 * e2 + 1]} * ls2 + (mc2 + __builtin_convertvector(h2, f32x2));
+                                xin[2 * e2] = x2[0];
+                                xin[2 * e2 + 1] = x2[1];
+                            }
+                            v[hb][g2] = xin + (acc[ha][hb][2 * fp + f][g2] + *reinterpret_cast<const f32x4*>(smem + BIAS_OFF + n * 4));
+                            sum += (v[hb][g2][0] + v[hb][g2][1]) + (v[hb][g2][2] + v[hb][g2][3]);
+                            if constexpr (!OUT_HL) {
+                                if (m < p.M)
+                                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.ldc + n) = v[hb][g2];
+                            }
+                            const f32x2 mu2 = {mu_u[f], mu_u[f]};
+                            float rem[4];
+#pragma unroll
+                            for (int e2 = 0; e2 < 2; ++e2) {
+                                const f32x2 d = f32x2{v[hb][g2][2 * e2], v[hb][g2][2 * e2 + 1]} - mu2;
+                                const half2v hh = __builtin_convertvector(d, half2v);
+                                h16[f][hb][g2][2 * e2] = hh[0];
+                                h16[f][hb][g2][2 * e2 + 1] = hh[1];
+                                if constexpr (OUT_HL) {
+                                    const f32x2 r = d - __builtin_convertvector(hh, f32x2);
+                                    const f32x2 rs = r * f32x2{HG_LO_SCALE, HG_LO_SCALE};
+                                    rem[2 * e2] = rs[0];
+                                    rem[2 * e2 + 1] = rs[1];
+                                }
+                            }
+                            if constexpr (OUT_HL) {
+                                int w8 = __builtin_amdgcn_cvt_pk_bf8_f32(rem[0], rem[1], 0, false);
+                                w8 = __builtin_amdgcn_cvt_pk_bf8_f32(rem[2], rem[3], w8, true);
+                                l8[f][hb][g2] = (unsigned)w8;
+                            }
+                        }
+                    sum = sum_rows(sum);
+                    const float gm = sum * (1.0f / 64.0f);
+                    float m2 = 0.f;
+#pragma unroll
+                    for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                        for (int g2 = 0; g2 < 2; ++g2)
+#pragma unroll
+                            for (int e2 = 0; e2 < 2; ++e2) {
+                                const f32x2 d = f32x2{v[hb][g2][2 * e2], v[hb][g2][2 * e2 + 1]} - f32x2{gm, gm};
+                                m2 = fmaf(d[0], d[0], m2);
+                                m2 = fmaf(d[1], d[1], m2);
+                            }
+                    m2 = sum_rows(m2);
+                    if (q == 0 && m < p.M) *reinterpret_cast<f32x2*>(p.stats + ((size_t)m * p.stats_ld + sg) * 2) = f32x2{sum, m2};
+                }
+                // fp16 copy: pair the row tiles f = 0, 1 through v_permlane16_swap -> 16-byte stores
+                const int m = m0 + ha * (BM / 2) + wm * MF * 16 + fp * 32 + (lane & 15) + ((q & 1) ? 16 : 0);
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                    for (int g2 = 0; g2 < 2; ++g2) {
+                        const int nb = n0 + hb * 128 + wn * 32 + g2 * 16;
+                        const u32x2 ux = __builtin_bit_cast(u32x2, h16[0][hb][g2]), uy = __builtin_bit_cast(u32x2, h16[1][hb][g2]);
+                        const auto s0 = __builtin_amdgcn_permlane16_swap(ux[0], uy[0], false, false);
+                        const auto s1 = __builtin_amdgcn_permlane16_swap(ux[1], uy[1], false, false);
+                        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+                        if (m < p.M) *reinterpret_cast<u32x4*>(p.out2 + (size_t)m * p.ld2 + nb + 4 * (q & ~1)) = o;
+                        if constexpr (OUT_HL) *reinterpret_cast<u32x2*>(lo_ptr(u, hb, g2)) = u32x2{l8[0][hb][g2], l8[1][hb][g2]};
+                    }
+            }
         } else if constexpr (ROLL) {
             // residual epilogue through the rolling window: chunk c is consumed, stored, and its window slot is
             // refilled with chunk c + ROLL_W (the sched_barrier keeps the compiler from hoisting the refills)

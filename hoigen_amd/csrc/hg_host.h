@@ -174,6 +174,14 @@ struct hg_ctx {
                                  // counters between its tiles (hg_mlp_pair.hip; both towers, variant A); bit-identical to the two launches
     int opt_mlp_pair_chunk = 32; // ... 256-row panels of an XCD per chunk
     int opt_mlp_pair_fc_slots = 32;  // ... workgroups per XCD that run c_fc tiles (the rest start with c_proj)
+    int opt_mlp_pair256 = 1;     // ... with c_proj on 256 x 256 tiles (hg_mlp_pair256.hip) where mlp_pair256_ok holds; 0: hg_mlp_pair.hip's 128-row tiles.  Same bits
+    int opt_mlp_pair256_min_m = 25000; // ... from this many rows on: 25 216 rows (128 crops) is the smallest measured call it wins, 18 912 (96) loses (profiles/mlp_pair256.txt)
+    int opt_mlp_pair256_chunk = 6;     // ... 256-row panels of an XCD per chunk of ITS c_fc order (small, so that the slots that reach c_proj first find whole
+                                       // panels; 6 measured best of 1 .. 32 on the headline step: profiles/mlp_pair256.txt)
+    int opt_mlp_pair256_ratio = 4;     // ... c_fc tile times a 256 x 256 c_proj tile takes, what its dealing balances with: 166-176 k against 43-44 k ticks per
+                                       // tile in the per-slot stamps (profiles/mlp_pair256.txt)
+    int n_pair256_launches = 0;  // ... launches of that kernel so far (option "mlp_pair256_launches": read it; setting it restarts the count; the profiler
+                                 // record is the pair launch's, so this is how a caller tells which kernel ran)
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
     int n_cu = 256;
     // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became

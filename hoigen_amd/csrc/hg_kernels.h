@@ -104,6 +104,10 @@ bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu);
 size_t mlp_pair_ready_words(int M);
 hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int fc_slots, int n_cu, hipStream_t s,
                            int grid_short = 0);      // grid_short (fault injection: hg_api.hip option mlp_pair_fault): workgroups NOT launched
+// ... with c_proj on 256 x 256 tiles (hg_mlp_pair256.hip): the same arguments, ready words, error word and bits; no text-tower (gamma) form
+bool mlp_pair256_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu, int min_m);
+hipError_t launch_mlp_pair256(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int ratio, int n_cu,
+                              hipStream_t s, int grid_short = 0);      // ch: panels per chunk of the c_fc order; ratio: c_fc tile times per c_proj tile
 // two 4-wave workgroups per CU, 128x256 tiles, free-running (hg_gemm_duo.hip): residual GEMMs and fp16/fp32 outputs
 bool gemm_duo_ok(int epi, const GemmArgs& a);
 hipError_t launch_gemm_duo(int epi, const GemmArgs& a, hipStream_t s);

@@ -38,23 +38,9 @@
 
 #include "hg_gemm_ring_body.h"
 #include "hg_gemm_ring2_body.h"
+#include "hg_mlp_pair_dev.h"
 
 namespace hg {
-
-constexpr int MLP_SPIN_LIMIT = 1 << 20;    // polls of a ready counter (~0.5 us each: s_sleep 16) before giving up
-constexpr int MLP_NX = 8;                  // XCDs (HW_REG_XCC_ID 0 .. 7)
-constexpr int MLP_CENSUS = 16;             // words in front of the ready counters: [0, 8) work slots taken per XCD
-
-struct MlpGeom {      // where this workgroup works: its XCD (hardware id), its work slot there, slots per XCD (all / those that run c_fc), panels per chunk
-    int xcd, cu, cpx, fcs, ch;
-    int wave;         // this wave's index in the workgroup (the bodies rebuild their thread id from it: see thread_id())
-};
-// threadIdx.x without keeping v0 alive: wave index (scalar) * 64 + lane (v_mbcnt), opaque so that nothing derived from it outlives a segment
-__device__ __forceinline__ int mlp_thread_id(int wave) {
-    int t = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    asm volatile("" : "+v"(t));
-    return t;
-}
 
 // ---- c_fc: the XCD's list = its chunks one after the other (inside a chunk: column group, panel, column in the group); the first `fcs`
 // slots of the XCD deal it among themselves (items cu, cu + fcs, ...); a segment is the item range [e0, e0 + n) of this slot.  fcs < the
@@ -166,22 +152,6 @@ struct MlpProjSched {
     __device__ __forceinline__ void poll_blocking(int r) const { spin(counter(r)); }
 };
 
-// Kernel arguments: only what the two bodies read (a GemmArgs each would be 2 x 47 dwords of scalar registers: see the kernel's note)
-struct MlpFcArgs {
-    const half_t* A; const half_t* W; const float* bias; half_t* out; const float* cs; const float* mr;
-    int lda, ldc, M, N, K;
-    unsigned a_bytes;
-};
-struct MlpProjArgs {
-    const half_t* A; const half_t* W; const float* bias; float* out; const float* mu; half_t* out2; float* stats; half_t* lo;
-    const float* muc;
-    int lda, ldc, ld2, M, N, K, stats_ld;
-    unsigned a_bytes;
-    // GS instances (the text tower: the next LayerNorm's weight rides in the activation copy, GemmArgs::gamma)
-    const float* gamma;
-    half_t* out3;
-    int ld3;
-};
 struct MlpPairArgs {
     MlpFcArgs fc;
     MlpProjArgs proj;
@@ -204,25 +174,8 @@ struct MlpPairArgs {
 // c_proj's arguments are read from the kernel-argument segment BEHIND the c_fc body (as kernel arguments proper they are loaded at the
 // kernel's entry and sit in 30 scalar registers all through c_fc: with the text tower's three more - gamma, out3, ld3 - that is what
 // tips the allocator over, see above).  Read back as integers the pointers have lost their address space; a cast of the BITS to an
-// address-space-1 pointer gives it back (a cast of the generic pointer there and back is folded away and leaves flat_ accesses).
-template <class T>
-__device__ __forceinline__ T load_kernarg(unsigned offset) {
-    static_assert(sizeof(T) % 4 == 0, "dword-sized arguments");
-    const __attribute__((address_space(4))) char* ka = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    const __attribute__((address_space(4))) unsigned* w = reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(ka + offset);
-    unsigned t[sizeof(T) / 4];
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; ++i) t[i] = w[i];
-    T o;
-    __builtin_memcpy(&o, t, sizeof(T));
-    return o;
-}
-template <class T>
-__device__ __forceinline__ T* global_bits(T* p) {
-    return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
-}
-
+// address-space-1 pointer gives it back (a cast of the generic pointer there and back is folded away and leaves flat_ accesses):
+// load_kernarg, global_bits (hg_mlp_pair_dev.h).
 template <int HL, bool GS>
 __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -184,6 +184,7 @@ struct BlockPlan {
     bool row0 = false;       // the tower's last block, on the selected rows only
     bool emits = false;      // c_proj emits the next block's ln_1 copy and statistics (every folded block but the tower's last)
     bool pair = false;       // c_fc -> QuickGELU -> c_proj as ONE persistent launch (hg_mlp_pair.hip)
+    bool pair256 = false;    // ... with c_proj on 256 x 256 tiles (hg_mlp_pair256.hip)
     int hl_out = 0, hl_proj = 0;      // GemmArgs::hl of out-proj / c_proj
     bool x_hilo = false;     // behind this block the stream lives in (h, xlo, muc), not in x
     half_t* x16 = nullptr;   // the centred fp16 copy of the stream entering the block (on the hi / lo stream: its hi half), row stride ldx:
@@ -354,9 +355,14 @@ int plan_tower(hg_ctx* c, const std::vector<BlockW>& blocks, const TowerCall& t,
         b.in_proj = !p.fuse ? InProj::separate : b.fold ? (qa ? InProj::qkv_attn_cat : InProj::cat) :
                     qa ? InProj::qkv_attn : qat ? InProj::qkv_attn_text : InProj::folded;
     }
-    for (size_t i = 0; p.pair_on && i + 1 < nb; ++i)      // (the arguments name the next block's copy: behind the loop above)
-        p.blocks[i].pair = mlp_pair_ok(fc_args(p, blocks[i], p.blocks[i], D),
-                                       proj_args(p, blocks[i], p.blocks[i], D, &p.blocks[i + 1], blocks[i + 1].ln1_w), c->n_cu);
+    for (size_t i = 0; p.pair_on && i + 1 < nb; ++i) {    // (the arguments name the next block's copy: behind the loop above)
+        const GemmArgs fc = fc_args(p, blocks[i], p.blocks[i], D);
+        const GemmArgs proj = proj_args(p, blocks[i], p.blocks[i], D, &p.blocks[i + 1], blocks[i + 1].ln1_w);
+        p.blocks[i].pair = mlp_pair_ok(fc, proj, c->n_cu);
+        // (the text tower keeps the 128-row kernel in either text_ln_fold form: the 256-row one has no gamma instance and has not been
+        // measured at width 512)
+        p.blocks[i].pair256 = p.blocks[i].pair && c->opt_mlp_pair256 && !t.causal && mlp_pair256_ok(fc, proj, c->n_cu, c->opt_mlp_pair256_min_m);
+    }
     p.pre16 = !t.pre_w ? (p.gs ? p.hg : p.h) : nb ? p.blocks[0].x16 : p.h;      // (rowstats_cast writes dense rows)
     p.pre_ld = t.pre_w && nb ? p.blocks[0].ldx : D;
     return HG_OK;
@@ -452,8 +458,12 @@ int launch_mlp(hg_ctx* c, const TowerCall& t, const TowerPlan& p, const std::vec
     if (b.pair) {
         PairGateScope gate(c->device, s);
         ProfScope ps(c, s, HG_PROF_MLP_PAIR, p.M, 4 * D, D);
-        HG_HIP(launch_mlp_pair(fc, proj, (unsigned*)c->pair_ready.p + i * (size_t)p.pair_panels, c->pair_err,
-                               c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, c->opt_mlp_pair_fault));
+        unsigned* ready = (unsigned*)c->pair_ready.p + i * (size_t)p.pair_panels;
+        if (b.pair256) ++c->n_pair256_launches;
+        if (b.pair256)
+            HG_HIP(launch_mlp_pair256(fc, proj, ready, c->pair_err, c->opt_mlp_pair256_chunk, c->opt_mlp_pair256_ratio, c->n_cu, s, c->opt_mlp_pair_fault));
+        else
+            HG_HIP(launch_mlp_pair(fc, proj, ready, c->pair_err, c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, c->opt_mlp_pair_fault));
     } else {
         HG_HIP(gemm(c, p.fuse ? EPI_LN_BIAS_QGELU_F16 : EPI_BIAS_QGELU_F16, fc, s));
         // c_proj as hi + lo (hg_load_vit) behind adapters on a tower of more than 224 tokens: x += fc x lo^T * 2^-11 on the fp32 stream

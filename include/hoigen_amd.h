@@ -298,6 +298,16 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      column group by column group, as in the stand-alone kernel; speed only)
  *   "mlp_pair_fc_slots" [HG_MLP_PAIR_FC_SLOTS] 1 .. 64: workgroups per XCD (of 32) that run c_fc tiles in that launch (default 32); the others start with
  *                      their c_proj tiles, i.e. sleep until the first row panels are complete (speed only)
+ *   "mlp_pair256"     [HG_MLP_PAIR256]     1 (default): where that launch runs on the fp32 or the hi / lo stream without the LayerNorm weight in the
+ *                      activation copy (the vision tower), its c_proj tiles are 256 x 256 instead of 128 x 256 (hoigen_amd/csrc/hg_mlp_pair256.hip:
+ *                      a third less global -> LDS traffic per flop, the work slots of an XCD share its tiles by work); the text tower's form and
+ *                      0: 128 x 256.  Bit-identical results in both; the same ready words, error word and profiler record.
+ *   "mlp_pair256_min_m" [HG_MLP_PAIR256_MIN_M] >= 2048: rows from which on "mlp_pair256" applies (default 25000: measured faster from 128 crops =
+ *                      25 216 rows on, slower at 96 crops and below, where a slot owns too few of the big tiles)
+ *   "mlp_pair256_chunk" [HG_MLP_PAIR256_CHUNK] 1 .. 64: 256-row panels of an XCD per chunk of that kernel's c_fc tile order (default 6; speed only)
+ *   "mlp_pair256_ratio" [HG_MLP_PAIR256_RATIO] 1 .. 8: c_fc tile times its dealing counts for a c_proj tile (default 4: measured 3.8 - 4.1; speed only)
+ *   "mlp_pair256_launches" [HG_MLP_PAIR256_LAUNCHES] a counter, not a switch: hg_get_option reads how many launches of that kernel the context has
+ *                      made (its profiler record is the pair launch's); setting it (>= 0) restarts the count from that value
  *   "mlp_pair_fault"  [HG_MLP_PAIR_FAULT]  test hook, default 0.  1: that launch goes out one workgroup short - a work slot nobody takes -, so that the
  *                      hand-off waits that depend on it meet their bound (~0.6 s), the results of the call are wrong and the NEXT call returns
  *                      HG_ERR_HIP (tests/test_gpu_scale.py exercises "an error, never a hang" with it, and the recovery once it is 0 again)
