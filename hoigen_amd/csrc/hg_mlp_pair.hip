@@ -33,100 +33,52 @@
 // minus the boundary: a workgroup with one c_fc tile fewer starts its c_proj tiles a tile time earlier, its first panels are long
 // complete.  (c_fc in two or three segments with the c_proj tiles of a segment's panels behind the next segment's c_fc - `fc` read back
 // sooner after it was written - was built and measured no faster in any chunking: profiles/r06_mlp_pair.txt.)
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "hg_gemm_ring_body.h"
 #include "hg_gemm_ring2_body.h"
 #include "hg_mlp_pair_dev.h"
 
 namespace hg {
 
-// ---- c_fc: the XCD's list = its chunks one after the other (inside a chunk: column group, panel, column in the group); the first `fcs`
-// slots of the XCD deal it among themselves (items cu, cu + fcs, ...); a segment is the item range [e0, e0 + n) of this slot.  fcs < the
-// number of slots leaves the other workgroups of the XCD idle (polling, asleep) until the first panels are complete: as in the
-// stand-alone kernel, 2364 tiles take ten rounds on 240 or on 256 workgroups, and the idle CUs' power buys clock for the others.
+// ---- c_fc: the XCD's list (MlpFcList), dealt among its first `fcs` slots (MlpFcDeal; hg_mlp_pair_deal.h).  fcs < the number of slots
+// leaves the other workgroups of the XCD idle (polling, asleep) until the first panels are complete: as in the stand-alone kernel,
+// 2364 tiles take ten rounds on 240 or on 256 workgroups, and the idle CUs' power buys clock for the others.
 struct MlpFcSched {
     static constexpr bool PUBLISH = true, CONSUME = false;
-    int x, cu, fcs, ch, tn, cg, wave;   // XCD, slot, slots that run c_fc, panels per chunk, column tiles, column tiles per group
-    int npx, nfc, last_pc, total;       // panels of this XCD, full chunks, panels of the partial chunk, items of this slot
-    int e0, n;
+    MlpFcList list;
+    MlpFcDeal deal;
+    int wave;
     unsigned* ready;
-    __device__ __forceinline__ MlpFcSched(const MlpGeom& g, int M, int N, unsigned* ready_) {
-        x = g.xcd; cu = g.cu; fcs = g.fcs; ch = g.ch; wave = g.wave; ready = ready_;
-        tn = N / 256;
-        cg = tn % 4 == 0 ? 4 : (tn % 3 == 0 ? 3 : tn);
-        const int pf = (M + 255) / 256;
-        npx = pf > x ? (pf - x + MLP_NX - 1) / MLP_NX : 0;
-        nfc = npx / ch;
-        last_pc = npx - nfc * ch;
-        total = count(npx * tn);
-        e0 = 0; n = 0;
+    __device__ __forceinline__ MlpFcSched(const MlpGeom& g, int M, int N, unsigned* ready_)
+        : list(g.xcd, g.ch, N / 256, mlp_panels((M + 255) / 256, g.xcd)), deal(list.size(), g.cu, g.fcs) {
+        wave = g.wave; ready = ready_;
     }
-    // items of this slot among the first `lim` list positions
-    __device__ __forceinline__ int count(int lim) const { return cu < fcs && cu < lim ? (lim - cu + fcs - 1) / fcs : 0; }
-    // items of the chunks 0 .. s
-    __device__ __forceinline__ int upto(int s) const {
-        const int pc = (s + 1) * ch;
-        return count((pc < npx ? pc : npx) * tn);
-    }
-    __device__ __forceinline__ int n_items() const { return n; }
-    // start stagger of the launch's first segment, as in the stand-alone kernel: slots that own one tile fewer than the fullest ones spend a
-    // pseudo-random fraction of a tile time before their first tile (de-phased epilogue bursts: -11 us per launch)
-    __device__ __forceinline__ int slack() const { return e0 == 0 ? (npx * tn + fcs - 1) / fcs - total : 0; }
-    __device__ __forceinline__ void tile(int r, int& tm, int& tn_) const {
-        const int L = cu + fcs * (e0 + r);          // position in the XCD's list
-        const int per_c = ch * tn;
-        int c = L / per_c, l = L - c * per_c, pc = ch;
-        if (c >= nfc) { c = nfc; l = L - nfc * per_c; pc = last_pc; }
-        const int per_g = pc * cg;                  // inside the chunk: column group, panel, column in the group
-        const int grp = l / per_g, rem = l - grp * per_g;
-        const int j = rem / cg;
-        tn_ = grp * cg + (rem - j * cg);
-        tm = x + MLP_NX * (c * ch + j);
-    }
+    __device__ __forceinline__ int n_items() const { return deal.total; }
+    // start stagger, as in the stand-alone kernel: slots that own one tile fewer than the fullest ones spend a pseudo-random fraction
+    // of a tile time before their first tile (de-phased epilogue bursts: -11 us per launch)
+    __device__ __forceinline__ int slack() const { return deal.slack(); }
+    __device__ __forceinline__ void tile(int r, int& tm, int& tn_) const { list.tile(deal.pos(r), tm, tn_); }
     __device__ __forceinline__ int thread_id() const { return mlp_thread_id(wave); }
     __device__ __forceinline__ void publish(int tm, int lane) const {
         if (lane == 0) __hip_atomic_fetch_add(ready + tm, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
 
-// ---- c_proj: items cu, cu + cpx, ... of the XCD's list (its panel k, 128-row half, column tile); a segment is the item range [e0, e0 + n)
+// ---- c_proj: this slot's items of the XCD's list (MlpProjDeal), each behind a wait for its panel
 struct MlpProjSched {
     static constexpr bool PUBLISH = false, CONSUME = true;
-    int x, cu, cpx, ch, tn, tx, total, wave;
-    int e0, n;
+    MlpProjDeal deal;
+    int wave;
     unsigned target;
     const unsigned* ready;
     int* err;
-    __device__ __forceinline__ MlpProjSched(const MlpGeom& g, int M, int N, int n_fc, const unsigned* ready_, int* err_) {
-        // (the list is dealt from the LAST slot down: the c_fc list's remainder goes to the first slots, this one's to the last ones - a slot
-        // owns 10 + 4, 9 + 5 or, two per XCD, 10 + 5 tiles instead of 10 + 5 for twelve: a c_proj tile takes 2.2 c_fc tile times)
-        x = g.xcd; cu = g.cpx - 1 - g.cu; cpx = g.cpx; ch = g.ch; wave = g.wave; ready = ready_; err = err_;
-        tn = N / 256;
-        const int pf = (M + 255) / 256, pq = (M + 127) / 128;
-        const int npx = pf > x ? (pf - x + MLP_NX - 1) / MLP_NX : 0;
-        // the chip's last panel may have one 128-row half only; it is the last panel of its XCD's list, its missing half the list's tail
-        tx = tn * (2 * npx - ((npx > 0 && x + MLP_NX * (npx - 1) == pf - 1 && (pq & 1)) ? 1 : 0));
-        total = cu < tx ? (tx - cu + cpx - 1) / cpx : 0;
+    __device__ __forceinline__ MlpProjSched(const MlpGeom& g, int M, int N, int n_fc, const unsigned* ready_, int* err_)
+        : deal(M, N / 256, g.xcd, g.cu, g.cpx) {
+        wave = g.wave; ready = ready_; err = err_;
         target = (unsigned)(n_fc / 256);      // one publish per c_fc tile of the panel
-        e0 = 0; n = 0;
     }
-    // items whose panel lies in the c_fc chunks 0 .. t
-    __device__ __forceinline__ int upto(int t) const {
-        int lim = 2 * tn * ch * (t + 1);
-        lim = lim < tx ? lim : tx;
-        return cu < lim ? (lim - cu + cpx - 1) / cpx : 0;
-    }
-    __device__ __forceinline__ int n_items() const { return n; }
+    __device__ __forceinline__ int n_items() const { return deal.total; }
     __device__ __forceinline__ int slack() const { return 0; }      // (the slots reach their c_proj tiles de-phased by their c_fc tiles)
-    __device__ __forceinline__ void tile(int r, int& tm, int& tn_) const {
-        const int i = cu + cpx * (e0 + r);
-        const int k = i / (2 * tn), rem = i - k * 2 * tn;
-        const int half = rem / tn;
-        tn_ = rem - half * tn;
-        tm = 2 * (x + MLP_NX * k) + half;
-    }
+    __device__ __forceinline__ void tile(int r, int& tm, int& tn_) const { deal.tile(deal.item(r), tm, tn_); }
     __device__ __forceinline__ int thread_id() const { return mlp_thread_id(wave); }
     __device__ __forceinline__ const unsigned* counter(int r) const {
         int tm, t2;
@@ -137,19 +89,10 @@ struct MlpProjSched {
     __device__ __forceinline__ unsigned poll_issue(int r) const {
         return __hip_atomic_load(counter(r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __device__ __forceinline__ void spin(const unsigned* ctr) const {
-        for (int it = 0; it < MLP_SPIN_LIMIT; ++it) {
-            if (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return;
-            __builtin_amdgcn_s_sleep(16);
-            // (a wait of this launch or an earlier one has already given up: the call is lost, do not sit out the bound tile after tile)
-            if ((it & 1023) == 1023 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) return;
-        }
-        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // never a hang: flag it and go on
-    }
     __device__ __forceinline__ void poll_finish(int r, unsigned v) const {
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) < target) spin(counter(r));
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) < target) mlp_wait_panel(counter(r), target, err);
     }
-    __device__ __forceinline__ void poll_blocking(int r) const { spin(counter(r)); }
+    __device__ __forceinline__ void poll_blocking(int r) const { mlp_wait_panel(counter(r), target, err); }
 };
 
 struct MlpPairArgs {
@@ -179,49 +122,29 @@ struct MlpPairArgs {
 template <int HL, bool GS>
 __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    // this workgroup's XCD (the hardware's word, not blockIdx's) and its work slot there
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpPairArgs& P = P_in;
     MlpGeom geo;
-    geo.xcd = (int)(__builtin_amdgcn_s_getreg(20 /* HW_REG_XCC_ID */ | (0 << 6) | ((4 - 1) << 11)) & (MLP_NX - 1));
-    geo.cpx = (gridDim.x + MLP_NX - 1) / MLP_NX;      // (slots per XCD; a grid launched short - the API's fault-injection option - leaves a slot untaken)
-    geo.wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    geo.ch = P.ch;
-    geo.fcs = P.fc_slots < geo.cpx ? P.fc_slots : geo.cpx;
-    if (threadIdx.x == 0)
-        *reinterpret_cast<int*>(smem + P.census_off) =
-            (int)__hip_atomic_fetch_add(P.ready + geo.xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    geo.cu = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + P.census_off));
-    if (geo.cu >= geo.cpx) return;      // more workgroups on this XCD than it has slots: the others own all of its work
+    if (!mlp_take_slot(geo, smem, P.ready, P.census_off, P.ch, P.fc_slots)) return;
 #ifdef HG_STAMPS
     unsigned long long t_stamp[4] = {__builtin_amdgcn_s_memtime(), 0, 0, 0};
 #endif
     {
         MlpFcSched sf(geo, P.fc.M, P.fc.N, P.ready + MLP_CENSUS);
-        sf.e0 = 0; sf.n = sf.total;
-        if (sf.n > 0) {
-            GemmArgs a{};
-            a.A = P.fc.A; a.W = P.fc.W; a.bias = P.fc.bias; a.out = P.fc.out; a.cs = P.fc.cs; a.mr = P.fc.mr;
-            a.lda = P.fc.lda; a.ldc = P.fc.ldc; a.M = P.fc.M; a.N = P.fc.N; a.K = P.fc.K;
+        if (sf.deal.total > 0) {
+            const GemmArgs a = mlp_fc_gemm_args(P.fc);
             gemm_ring_body<4, EPI_LN_BIAS_QGELU_F16, true>(a, P.fc.a_bytes, 3000 << 8, sf);
         }
 #ifdef HG_STAMPS
         t_stamp[1] = __builtin_amdgcn_s_memtime();
-        t_stamp[3] = (unsigned long long)sf.n;
+        t_stamp[3] = (unsigned long long)sf.deal.total;
 #endif
     }
     {
         const MlpProjArgs Q = load_kernarg<MlpProjArgs>((unsigned)__builtin_offsetof(MlpPairArgs, proj));      // (here, not at the kernel's entry)
         MlpProjSched sp(geo, Q.M, Q.N, Q.K, P.ready + MLP_CENSUS, P.err);
-        sp.e0 = 0; sp.n = sp.total;
-        if (sp.n > 0) {
-            GemmArgs a{};
-            a.A = global_bits(Q.A); a.W = global_bits(Q.W); a.bias = global_bits(Q.bias); a.out = global_bits(Q.out); a.mu = global_bits(Q.mu);
-            a.out2 = global_bits(Q.out2); a.stats = global_bits(Q.stats); a.lo = global_bits(Q.lo); a.muc = global_bits(Q.muc);
-            a.lda = Q.lda; a.ldc = Q.ldc; a.ld2 = Q.ld2; a.M = Q.M; a.N = Q.N; a.K = Q.K;
-            a.stats_ld = Q.stats_ld;
-            if constexpr (GS) { a.gamma = global_bits(Q.gamma); a.out3 = global_bits(Q.out3); a.ld3 = Q.ld3; }
+        if (sp.deal.total > 0) {
+            const GemmArgs a = mlp_proj_gemm_args<GS>(Q);
             __builtin_amdgcn_s_waitcnt(0xC07F);
             barrier_raw();      // every wave has left the c_fc body (its LDS image is dead)
             gemm_ring2_body<EPI_RESID_LN_F32, HL, GS>(a, a.N / 256, Q.a_bytes, 0, sp);
@@ -230,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in
         t_stamp[2] = __builtin_amdgcn_s_memtime();
         if (P.dbg && threadIdx.x == 0) {
             unsigned long long* d = P.dbg + (size_t)blockIdx.x * 8;
-            d[0] = t_stamp[0]; d[1] = t_stamp[1]; d[2] = t_stamp[2]; d[3] = t_stamp[3]; d[4] = (unsigned long long)sp.n;
+            d[0] = t_stamp[0]; d[1] = t_stamp[1]; d[2] = t_stamp[2]; d[3] = t_stamp[3]; d[4] = (unsigned long long)sp.deal.total;
             d[5] = (unsigned long long)(geo.xcd * 256 + geo.cu);
         }
 #endif
@@ -251,32 +174,18 @@ bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu) {
     return proj.hl == 0 || proj.hl == 2 || proj.hl == 3;
 }
 
-template <int HL, bool GS = false>
-static hipError_t launch_pair_t(const MlpPairArgs& a, int grid, int lds, hipStream_t s) {
-    static bool attr_set_d[HG_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_d[current_device_index()];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_pair_kernel<HL, GS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((mlp_pair_kernel<HL, GS>), dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-
 static hipError_t launch_pair_hl(const MlpPairArgs& a, int hl, bool gs, int grid, int lds, hipStream_t s) {
     if (gs) {
         switch (hl) {
-            case 2: return launch_pair_t<2, true>(a, grid, lds, s);
-            case 3: return launch_pair_t<3, true>(a, grid, lds, s);
+            case 2: return mlp_launch_instance<mlp_pair_kernel<2, true>>(a, grid, lds, s);
+            case 3: return mlp_launch_instance<mlp_pair_kernel<3, true>>(a, grid, lds, s);
             default: return hipErrorInvalidValue;
         }
     }
     switch (hl) {
-        case 0: return launch_pair_t<0>(a, grid, lds, s);
-        case 2: return launch_pair_t<2>(a, grid, lds, s);
-        case 3: return launch_pair_t<3>(a, grid, lds, s);
+        case 0: return mlp_launch_instance<mlp_pair_kernel<0, false>>(a, grid, lds, s);
+        case 2: return mlp_launch_instance<mlp_pair_kernel<2, false>>(a, grid, lds, s);
+        case 3: return mlp_launch_instance<mlp_pair_kernel<3, false>>(a, grid, lds, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -290,49 +199,21 @@ hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj_in, unsigned
     if (!mlp_pair_ok(fc, proj, n_cu) || !ready || !err || proj.ld2 % 8) return hipErrorInvalidValue;
     if (proj.hl && (!proj.lo || !proj.mu || ((proj.hl == 2 || proj.hl == 3) && !proj.muc))) return hipErrorInvalidValue;
     MlpPairArgs a{};
-    a.fc = MlpFcArgs{fc.A, fc.W, fc.bias, (half_t*)fc.out, fc.cs, fc.mr, fc.lda, fc.ldc, fc.M, fc.N, fc.K,
-                     (unsigned)((size_t)((fc.M + 255) / 256) * 256 * fc.lda * 2)};
-    a.proj = MlpProjArgs{proj.A, proj.W, proj.bias, (float*)proj.out, proj.mu, proj.out2, proj.stats, proj.lo, proj.muc,
-                         proj.lda, proj.ldc, proj.ld2, proj.M, proj.N, proj.K, proj.stats_ld,
-                         (unsigned)((size_t)((proj.M + 127) / 128) * 128 * proj.lda * 2), proj.gamma, proj.out3, proj.ld3};
+    mlp_pack_args(fc, proj, 128, a.fc, a.proj);
     a.ready = ready; a.err = err;
     a.ch = ch < 1 ? 1 : (ch > 64 ? 64 : ch);
     a.fc_slots = fc_slots < 1 ? 1 : fc_slots;
-    const int lds_fc = 2 * (2 * 4 * 4096 + 2 * 16384) + fc.N * 4 * 2 + 256 * 8;
-    const int lds_proj = 3 * 49152 + proj.N * 4 * (proj.gamma ? 2 : 1);
-    a.census_off = lds_fc > lds_proj ? lds_fc : lds_proj;      // (behind both bodies' LDS images: never overwritten)
-    const int lds = a.census_off + 16;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const int grid = n_cu - (grid_short > 0 && grid_short < MLP_NX ? grid_short : 0);
+    const int lds = mlp_pair_lds(fc.N, 3 * 49152 + proj.N * 4 * (proj.gamma ? 2 : 1), a.census_off);
+    if (!lds) return hipErrorInvalidValue;
+    const int grid = mlp_pair_grid(n_cu, grid_short);
+    auto launch = [&](unsigned long long* dbg) {
+        a.dbg = dbg;
+        return launch_pair_hl(a, proj.hl, proj.gamma != nullptr, grid, lds, s);
+    };
 #ifdef HG_STAMPS
-    if (getenv("HG_STAMPS")) {
-        unsigned long long* d = nullptr;
-        if (hipMalloc(&d, (size_t)grid * 64) != hipSuccess) return hipErrorOutOfMemory;
-        hipMemsetAsync(d, 0, (size_t)grid * 64, s);
-        a.dbg = d;
-        hipError_t e = launch_pair_hl(a, proj.hl, proj.gamma != nullptr, grid, lds, s);
-        hipStreamSynchronize(s);
-        unsigned long long* h = (unsigned long long*)malloc((size_t)grid * 64);
-        hipMemcpy(h, d, (size_t)grid * 64, hipMemcpyDeviceToHost);
-        // s_memtime is not synchronised across CUs: only differences inside a workgroup mean anything.  Group by (c_fc tiles, c_proj tiles).
-        for (int nf = 0; nf <= 12; ++nf)
-            for (int np = 0; np <= 8; ++np) {
-                double f = 0, q = 0, fmin = 1e30, fmax = 0, qmin = 1e30, qmax = 0; int n = 0;
-                for (int b = 0; b < grid; ++b) {
-                    if (!h[b * 8] || (int)h[b * 8 + 3] != nf || (int)h[b * 8 + 4] != np) continue;
-                    const double d1 = (double)(h[b * 8 + 1] - h[b * 8]), d2 = (double)(h[b * 8 + 2] - h[b * 8 + 1]);
-                    f += d1; q += d2; ++n;
-                    fmin = d1 < fmin ? d1 : fmin; fmax = d1 > fmax ? d1 : fmax; qmin = d2 < qmin ? d2 : qmin; qmax = d2 > qmax ? d2 : qmax;
-                }
-                if (n) fprintf(stderr, "[pair-dbg] %3d workgroups with %2d c_fc + %d c_proj tiles: c_fc phase mean %.0f (min %.0f max %.0f) = %.0f per tile | c_proj phase mean %.0f (min %.0f max %.0f) = %.0f per tile [s_memtime ticks]\n",
-                               n, nf, np, f / n, fmin, fmax, nf ? f / n / nf : 0.0, q / n, qmin, qmax, np ? q / n / np : 0.0);
-            }
-        free(h);
-        hipFree(d);
-        return e;
-    }
+    if (getenv("HG_STAMPS")) return mlp_launch_stamped("pair", grid, s, launch);
 #endif
-    return launch_pair_hl(a, proj.hl, proj.gamma != nullptr, grid, lds, s);
+    return launch(nullptr);
 }
 
 }  // namespace hg

@@ -10,6 +10,8 @@ import tempfile
 
 import pytest
 
+from asm_blocks import basic_blocks, kernel_body
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "hoigen_amd", "csrc")
 HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -137,20 +139,10 @@ def test_mlp_pair_kernel_codegen():
     names = re.findall(r"^(_ZN2hg15mlp_pair_kernel\S+):", txt, re.M)
     assert len(names) == 5, names      # stream fp32 / hi-lo / hi-lo -> fp32, and the text tower's two with gamma in the activation copy
     for name in names:
-        i = txt.index(name + ":")
-        body = txt[i:txt.index("s_endpgm", i)]
+        body = kernel_body(txt, name)
         assert "flat_" not in body, name
         assert "scratch_" not in body, name
-        blocks, cur = [], []
-        for line in body.split("\n"):
-            if re.match(r"^\.LBB\S+:", line):
-                blocks.append(cur)
-                cur = []
-            else:
-                ins = re.sub(r";.*", "", line).strip()
-                if ins and not ins.startswith("."):
-                    cur.append(ins)
-        blocks.append(cur)
+        blocks = basic_blocks(body)
         n_mfma = sum(1 for b in blocks for x in b if x.startswith("v_mfma"))
         assert n_mfma == 640, (name, n_mfma)      # c_fc: 6 K-tile kinds x 64; c_proj: 8 x 32
         epilogues = [b for b in blocks if sum(1 for x in b if x.startswith("v_exp_f32")) >= 64]

@@ -1,6 +1,6 @@
 """CPU checks of the MLP pair launch with c_proj on 256 x 256 tiles (hoigen_amd/csrc/hg_mlp_pair256.hip): the dealing of an XCD's tiles
-to its work slots, emulated on the host from the very header the kernel's schedules use, and the kernel's code as compiled for gfx950 -
-no GPU needed."""
+to its work slots - in both pair launches -, emulated on the host from the very header the kernels' schedules use, and the kernel's code
+as compiled for gfx950 - no GPU needed."""
 import os
 import re
 import shutil
@@ -8,6 +8,8 @@ import subprocess
 import tempfile
 
 import pytest
+
+from asm_blocks import basic_blocks, kernel_body
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "hoigen_amd", "csrc")
@@ -21,7 +23,11 @@ def test_pair256_dealing_deals_every_tile_once():
     {2048, 3072} (N_proj = N_fc / 4), chunks {1, 3, 8, 32}, work ratios 1 .. 6, 32 slots on each of 8 XCDs.  Every c_fc and every c_proj
     tile is dealt exactly once and nothing outside the grid; a slot is without a c_fc tile only where its XCD has fewer c_fc tiles than
     slots (M < 8 192 rows at width 768: a panel is 12 tiles; the first T slots then own one each); in every c_proj round the items of the
-    slots that own one c_proj tile more - and no more c_fc tiles than anyone - come first; loads differ by at most ratio + 1 tile times."""
+    slots that own one c_proj tile more - and no more c_fc tiles than anyone - come first; loads differ by at most ratio + 1 tile times.
+    And the launch with c_proj on 128-row tiles (hoigen_amd/csrc/hg_mlp_pair.hip, whose schedules run the same header): the same M and
+    N_fc, chunks {1, 3, 8, 32, 64}, 1, 24 or 32 of an XCD's 32 slots running c_fc tiles.  Every c_fc tile and every 128-row c_proj tile
+    is dealt exactly once and nothing outside the grid - at a half-panel edge the chip's last panel has one 128-row half only -, a
+    slot's c_fc positions and c_proj items lie in list order, and no slot's start stagger (slack) is negative."""
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "deal_check")
         r = subprocess.run([CXX, "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(REPO, "tools", "pair256_deal_check.cpp"), "-o", exe],
@@ -50,20 +56,10 @@ def test_mlp_pair256_kernel_codegen():
     names = re.findall(r"^(_ZN2hg18mlp_pair256_kernel\S+):", txt, re.M)
     assert len(names) == 3, names
     for name in names:
-        i = txt.index(name + ":")
-        body = txt[i:txt.index("s_endpgm", i)]
+        body = kernel_body(txt, name)
         assert "flat_" not in body, name
         assert "scratch_" not in body, name
-        blocks, cur = [], []
-        for line in body.split("\n"):
-            if re.match(r"^\.LBB\S+:", line):
-                blocks.append(cur)
-                cur = []
-            else:
-                ins = re.sub(r";.*", "", line).strip()
-                if ins and not ins.startswith("."):
-                    cur.append(ins)
-        blocks.append(cur)
+        blocks = basic_blocks(body)
         n_mfma = sum(1 for b in blocks for x in b if x.startswith("v_mfma_f32_16x16x32_f16"))
         assert n_mfma == 512, (name, n_mfma)
         epilogues = [b for b in blocks if sum(1 for x in b if x.startswith("v_exp_f32")) >= 64]
