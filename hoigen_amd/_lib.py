@@ -93,6 +93,10 @@ class hg_test_gemm_ex_args(C.Structure):
                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldc", "epi", "kernel", "G", "L", "n_split", "ld2", "ld3", "chain", "stop")]
 
 
+class hg_test_elem_args(C.Structure):
+    _fields_ = [("p", C.c_void_p * 9), ("n", C.c_uint64), ("i", C.c_int32 * 6)]
+
+
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 
 _P = C.c_void_p
@@ -136,6 +140,7 @@ SIGNATURES = {
     "hg_test_image_stream": (_I, [_P, _P, _I, _P, _P, _P]),
     "hg_test_text_stream": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "hg_test_adapter": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "hg_test_elem": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

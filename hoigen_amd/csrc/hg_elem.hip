@@ -1,6 +1,7 @@
 // Row / elementwise kernels (HBM-bound): LayerNorm, im2col, token embedding gather, prompt assembly,
 // reparameterisation, L2 normalisation, layout permutations, dtype conversion.  One wave per row
 // where a row reduction is needed; 16-byte accesses per lane.
+#include <climits>
 #include "hg_gemm_dev.h"
 
 namespace hg {
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int32_t* __rest
 hipError_t launch_embed_tokens(const int32_t* ids, int ld_ids, const float* table, const float* pos, float* x,
                                int T, int L, int D, int vocab, hipStream_t s) {
     if (T <= 0) return hipSuccess;
+    if (D % 4) return hipErrorInvalidValue;      // (16-byte chunks: the last D % 4 columns would stay unwritten)
     const size_t total = (size_t)T * L * (D / 4);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid), dim3(256), 0, s, ids, ld_ids, table, pos, x, T, L, D, vocab);
@@ -225,6 +227,7 @@ __global__ __launch_bounds__(256) void add_pos_kernel(const float* __restrict__ 
 hipError_t launch_add_pos(const float* prompts, int Lfull, const float* pos, float* x, int R, int L, int D,
                           hipStream_t s) {
     if (R <= 0) return hipSuccess;
+    if (D % 4) return hipErrorInvalidValue;
     const size_t total = (size_t)R * L * (D / 4);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(add_pos_kernel, dim3(grid), dim3(256), 0, s, prompts, Lfull, pos, x, R, L, D);
@@ -247,6 +250,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const int32_t* __restr
 hipError_t launch_gather_rows(const int32_t* ids, const float* table, float* out, int n, int D, int vocab,
                               hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (D % 4) return hipErrorInvalidValue;
     const size_t total = (size_t)n * (D / 4);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, s, ids, table, out, n, D, vocab);
@@ -529,7 +533,7 @@ __global__ __launch_bounds__(256) void split_global_local_kernel(const float* __
 hipError_t launch_split_global_local(const float* tok, float* glob, float* local, int B, int L, int E,
                                      hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (E % 32) return hipErrorInvalidValue;
+    if (E % 32 || !local) return hipErrorInvalidValue;      // (glob may be null, local is always written)
     hipLaunchKernelGGL(split_global_local_kernel, dim3(E / 32, B), dim3(256), 0, s, tok, glob, local, B, L, E);
     return hipGetLastError();
 }
@@ -546,6 +550,7 @@ __global__ void copy_rows_kernel(const float* __restrict__ x, float* __restrict_
 hipError_t launch_copy_rows(const float* x, float* out, int B, int row_stride, int D, hipStream_t s,
                             const int32_t* gather) {
     if (B <= 0) return hipSuccess;
+    if (D <= 0 || (size_t)B * D > (size_t)INT_MAX - 255) return hipErrorInvalidValue;      // (the kernel's element index is an int)
     hipLaunchKernelGGL(copy_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, x, out, B, row_stride, D, gather);
     return hipGetLastError();
 }
@@ -571,7 +576,7 @@ __global__ void copy_rows_hilo_kernel(const half_t* __restrict__ hi, const half_
 hipError_t launch_copy_rows_hilo(const half_t* hi, const half_t* lo, const float* muc, float* out, int B, int row_stride, int D,
                                  hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (D % 256) return hipErrorInvalidValue;
+    if (D <= 0 || D % 256 || (size_t)B * D > (size_t)INT_MAX - 255) return hipErrorInvalidValue;      // (int element index, as copy_rows)
     hipLaunchKernelGGL(copy_rows_hilo_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, hi, lo, muc, out, B, row_stride, D);
     return hipGetLastError();
 }
@@ -599,7 +604,12 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(const half_t* __restrict__
     float c = 0.f, b = 0.f, cg = 0.f;
     for (int k = lane; k < K; k += 64) {
         const float w = (float)w16[(size_t)n * K + k];
-        const half_t wf = (half_t)(w * gamma[k]);
+        // fp16(fl(w gamma)): the product is rounded to fp32 FIRST.  Left to -ffp-contract the multiply and the conversion became one
+        // mixed-precision instruction that rounds the exact product once, and about 1 weight in 30 000 was another fp16 number than
+        // the one this line and hg_kernels.h state (tests/test_gpu_elem.py::test_fold_ln); the empty asm keeps the two apart
+        float wg = w * gamma[k];
+        asm volatile("" : "+v"(wg));
+        const half_t wf = (half_t)wg;
         wf16[(size_t)n * K + k] = wf;
         c += (float)wf;
         b += w * beta[k];
@@ -617,6 +627,8 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(const half_t* __restrict__
 }
 hipError_t launch_fold_ln(const half_t* w16, const float* gamma, const float* beta, const float* bias, half_t* wf16,
                           float* cs, float* bf, int N, int K, hipStream_t s, float* csg) {
+    if (N <= 0) return hipSuccess;
+    if (K <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fold_ln_kernel, dim3((N + 3) / 4), dim3(256), 0, s, w16, gamma, beta, bias, wf16, cs, bf, N, K, csg);
     return hipGetLastError();
 }

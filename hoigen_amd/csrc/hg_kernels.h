@@ -210,7 +210,8 @@ hipError_t launch_layernorm_f32(const float* x, const float* w, const float* b, 
 // EVERY call (the matrix lives in a shared workspace; the weight's pad columns are zero, but 0 x NaN is NaN).
 inline int im2col_kp(int p) { return (3 * p * p + 63) / 64 * 64; }
 hipError_t launch_im2col(const float* x, half_t* out, int B, int R, int p, hipStream_t s);
-// x[r][:] = table[ids[r/L*ld_ids + r%L]][:] + pos[r%L][:]   (text: token_embedding + positional)
+// x[r][:] = table[ids[r/L*ld_ids + r%L]][:] + pos[r%L][:]   (text: token_embedding + positional).  This and the next two move rows in
+// 16-byte chunks: D % 4 != 0 is refused (hipErrorInvalidValue), ids are clamped to the table
 hipError_t launch_embed_tokens(const int32_t* ids, int ld_ids, const float* table, const float* pos, float* x,
                                int T, int L, int D, int vocab, hipStream_t s);
 // x[r][:] = prompts[(r/L)*Lfull + r%L][:] + pos[r%L][:]
@@ -240,18 +241,19 @@ hipError_t launch_reparam(const float* mean, const float* logvar, const float* e
                           int ld16, hipStream_t s);
 hipError_t launch_vae_loss(const float* recon, const float* x, const float* mean, const float* logvar, int R,
                            int D, float* loss, hipStream_t s);
-// tokens [B*L, E] fp32 -> global [B,E] (token 0) and local [B,E,g,g] (tokens 1..), NCHW
+// tokens [B*L, E] fp32 -> global [B,E] (token 0; may be null) and local [B,E,g,g] (tokens 1..; required), NCHW; E % 32 == 0
 hipError_t launch_split_global_local(const float* tok, float* glob, float* local, int B, int L, int E,
                                      hipStream_t s);
 hipError_t launch_copy_rows(const float* x, float* out, int B, int row_stride, int D, hipStream_t s,
-                            const int32_t* gather = nullptr);   // row b*row_stride (+ gather[b])
+                            const int32_t* gather = nullptr);   // row b*row_stride (+ gather[b], clamped); B * D within int (refused beyond, as below)
 // the same from a stream held as centre + hi + lo (GemmArgs::hl): hi [*, D] row-major, lo in gemm_ring2's tile-fragment order
 hipError_t launch_copy_rows_hilo(const half_t* hi, const half_t* lo, const float* muc, float* out, int B, int row_stride, int D,
                                  hipStream_t s);
 // first N columns of a [R, ld] fp32 matrix -> dense [R, N]
 hipError_t launch_copy_cols(const float* x, int ld, float* out, int R, int N, hipStream_t s);
 // ---- LayerNorm folding support (DESIGN.md §4 "LayerNorm folded into the GEMMs")
-// W16 [N,K], gamma/beta [K], bias [N]  ->  Wf16 = fp16(W * gamma), cs[n] = sum_k float(Wf16[n][k]), bf[n] = bias[n] + sum_k W[n][k] * beta[k]
+// (N <= 0: nothing to do, success; K <= 0 refused)
+// W16 [N,K], gamma/beta [K], bias [N]  ->  Wf16 = fp16(fl(W * gamma)) (two roundings: fp32, then fp16), cs[n] = sum_k float(Wf16[n][k]), bf[n] = bias[n] + sum_k W[n][k] * beta[k]
 hipError_t launch_fold_ln(const half_t* w16, const float* gamma, const float* beta, const float* bias, half_t* wf16,
                           float* cs, float* bf, int N, int K, hipStream_t s, float* csg = nullptr);
 // x fp32 [M,D] -> centred fp16 copy x16 = fp16(x - mean), mu[m] = mean, mr[m] = (0, rstd) (eps 1e-5, biased variance)

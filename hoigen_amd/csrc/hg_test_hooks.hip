@@ -1,4 +1,5 @@
-// Test hooks: single kernels behind the C ABI, operands rounded to fp16 on the device (tests/test_gpu_gemm.py, test_gpu_attention*.py).
+// Test hooks: single kernels behind the C ABI, operands rounded to fp16 on the device (tests/test_gpu_gemm.py, test_gpu_attention*.py);
+// hg_test_elem: one launcher of hg_elem.hip on the caller's own buffers, nothing converted (tests/test_gpu_elem.py).
 #include "hg_host.h"
 
 extern "C" {
@@ -354,6 +355,50 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
         HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, causal, s));
     }
     HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)M * D, s));
+    return HG_OK;
+}
+
+// One launcher of hg_elem.hip with the caller's own device buffers (include/hoigen_amd.h has the table of operands; tests/test_gpu_elem.py).
+int hg_test_elem(hg_ctx* c, int op, const hg_test_elem_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x) return fail(c, HG_ERR_INVALID, "hg_test_elem: args are required");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    void* const* p = x->p;
+    const int32_t* i = x->i;
+    auto F = [&](int k) { return (float*)p[k]; };
+    auto H = [&](int k) { return (half_t*)p[k]; };
+    auto I = [&](int k) { return (int32_t*)p[k]; };
+    hipError_t e;
+    switch (op) {
+        case 0: e = launch_layernorm_f16(F(0), F(1), F(2), H(3), i[0], i[1], I(4), i[2], i[3], s); break;
+        case 1: e = launch_layernorm_f32(F(0), F(1), F(2), F(3), i[0], i[1], s, F(4), F(5), i[2]); break;
+        case 2: e = launch_layernorm_rowstats(F(0), F(1), F(2), H(3), F(4), F(5), F(6), i[0], i[1], s, F(7), F(8), i[2], i[3]); break;
+        case 3: e = launch_rowstats_cast(F(0), H(1), F(2), F(3), i[0], i[1], s, F(4), F(5)); break;
+        case 4: e = launch_finalize_stats(F(0), F(1), F(2), i[0], i[1], i[2], s, F(3), i[3] != 0, (int*)p[4]); break;
+        case 5: e = launch_fold_ln(H(0), F(1), F(2), F(3), H(4), F(5), F(6), i[0], i[1], s, F(7)); break;
+        case 6: e = launch_copy_rows(F(0), F(1), i[0], i[1], i[2], s, I(2)); break;
+        case 7: e = launch_copy_rows_hilo(H(0), H(1), F(2), F(3), i[0], i[1], i[2], s); break;
+        case 8: e = launch_copy_cols(F(0), i[0], F(1), i[1], i[2], s); break;
+        case 9: e = launch_im2col(F(0), H(1), i[0], i[1], i[2], s); break;
+        case 10: e = launch_embed_tokens(I(0), i[0], F(1), F(2), F(3), i[1], i[2], i[3], i[4], s); break;
+        case 11: e = launch_add_pos(F(0), i[0], F(1), F(2), i[1], i[2], i[3], s); break;
+        case 12: e = launch_gather_rows(I(0), F(1), F(2), i[0], i[1], i[2], s); break;
+        case 13: e = launch_eot_argmax(I(0), i[0], i[1], I(1), I(2), s); break;
+        case 14: e = launch_clamp_eot(I(0), i[0], i[1], I(1), I(2), s, I(3)); break;
+        case 15: e = launch_poison_if_flag(F(0), (size_t)x->n, I(1), s); break;
+        case 16: e = launch_f32_to_f16(F(0), H(1), (size_t)x->n, s); break;
+        case 17: e = launch_f16_to_f32(H(0), F(1), (size_t)x->n, s); break;
+        case 18: e = launch_f16_remainder(F(0), H(1), (size_t)x->n, s); break;
+        case 19: e = launch_transpose_to_f16(p[0], i[0], H(1), i[1], i[2], s); break;
+        case 20: e = launch_l2_normalize(F(0), F(1), i[0], i[1], s); break;
+        case 21: e = launch_assemble_prompts(F(0), F(1), F(2), F(3), I(4), i[0], i[1], i[2], i[3], i[4], F(5), s); break;
+        case 22: e = launch_vae_loss(F(0), F(1), F(2), F(3), i[0], i[1], F(4), s); break;
+        case 23: e = launch_split_global_local(F(0), F(1), F(2), i[0], i[1], i[2], s); break;
+        default: return fail(c, HG_ERR_INVALID, "hg_test_elem: op must be 0 .. 23");
+    }
+    if (e == hipErrorInvalidValue) return fail(c, HG_ERR_INVALID, "hg_test_elem: op %d refused by its launcher: %s", op, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_elem: op %d failed: %s", op, hipGetErrorString(e));
     return HG_OK;
 }
 

@@ -455,6 +455,43 @@ int hg_test_adapter(hg_ctx*, int block, int mode, const float* x, const float* c
                     const uint8_t* mask, int N, float* out, float* copy_out, float* mr_out, float* muc_out, float* q_out,
                     int32_t* path, void* stream);
 
+/* Test hook for the row / elementwise kernels (hoigen_amd/csrc/hg_elem.hip): ONE launch_* call with the caller's device pointers, in
+ * the kernels' own types (fp32, fp16, int32, bytes - nothing is converted on the way), on the caller's stream.  No workspace of the
+ * context is used, no option read, no tower touched.  HG_ERR_INVALID, with the HIP error in hg_last_error, where the launcher refuses
+ * the call (nothing was launched then); HG_ERR_HIP for any other HIP error.  Unused pointers are NULL, unused ints 0.
+ *   op                     p[0 ..]                                                          i[0 ..]                        n
+ *   0  layernorm_f16       x, w, b, out (fp16), gather (int32)                              M, D, rows_per_seq, in_row_mul
+ *   1  layernorm_f32       x, w, b, out, pos, cls                                           M, D, L
+ *   2  layernorm_rowstats  x (in place), w, b, x16 (fp16), mr, mu, muc, pos, cls            M, D, L, ld16
+ *   3  rowstats_cast       x, x16 (fp16), mr, mu, muc, gamma                                M, D
+ *   4  finalize_stats      stats, mr, mu, muc, range_flag (int32)                           M, nt, gw, centred
+ *   5  fold_ln             w16 (fp16), gamma, beta, bias, wf16 (fp16), cs, bf, csg          N, K
+ *   6  copy_rows           x, out, gather (int32)                                           B, row_stride, D
+ *   7  copy_rows_hilo      hi (fp16), lo (bytes), muc, out                                  B, row_stride, D
+ *   8  copy_cols           x, out                                                           ld, R, N
+ *   9  im2col              x, out (fp16)                                                    B, R, p
+ *   10 embed_tokens        ids (int32), table, pos, x                                       ld_ids, T, L, D, vocab
+ *   11 add_pos             prompts, pos, x                                                  Lfull, R, L, D
+ *   12 gather_rows         ids (int32), table, out                                          n, D, vocab
+ *   13 eot_argmax          ids (int32), eot (int32), max_eot (int32)                        T, L
+ *   14 clamp_eot           in (int32), out (int32), flag (int32), flag_dev (int32)          n, Leff
+ *   15 poison_if_flag      out, flag (int32)                                                                               elements
+ *   16 f32_to_f16          in, out (fp16)                                                                                  elements
+ *   17 f16_to_f32          in (fp16), out                                                                                  elements
+ *   18 f16_remainder       in, out (fp16)                                                                                  elements
+ *   19 transpose_to_f16    in (fp32 or fp16), out (fp16)                                    in_dtype (0 fp32, 1 fp16), rows, cols
+ *   20 l2_normalize        x, out                                                           R, D
+ *   21 assemble_prompts    prefix, suffix, ctx, bias, target (int32), prompts               R, C, L, n_ctx, D
+ *   22 vae_loss            recon, x, mean, logvar, loss                                     R, D
+ *   23 split_global_local  tok, glob, local                                                 B, L, E
+ * (pointers fp32 where no type is given; the launchers' own argument names, hoigen_amd/csrc/hg_kernels.h) */
+typedef struct {
+    void* p[9];
+    uint64_t n;
+    int32_t i[6];
+} hg_test_elem_args;
+int hg_test_elem(hg_ctx*, int op, const hg_test_elem_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
