@@ -93,6 +93,11 @@ class hg_test_gemm_ex_args(C.Structure):
                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldc", "epi", "kernel", "G", "L", "n_split", "ld2", "ld3", "chain", "stop")]
 
 
+class hg_test_qkv_attn_ex_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("a", "w", "bias", "cs", "mr", "out", "qkv_out")] + \
+               [(n, C.c_int32) for n in ("n_seq", "L", "heads", "fused", "lda", "ldo", "pad_fill")]
+
+
 class hg_test_elem_args(C.Structure):
     _fields_ = [("p", C.c_void_p * 9), ("n", C.c_uint64), ("i", C.c_int32 * 6)]
 
@@ -136,6 +141,7 @@ SIGNATURES = {
     "hg_test_gemm_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hg_test_qkv_attn": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "hg_test_qkv_attn_ex": (_I, [_P, C.POINTER(hg_test_qkv_attn_ex_args), _P]),
     "hg_test_gemm_hilo": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "hg_test_image_stream": (_I, [_P, _P, _I, _P, _P, _P]),
     "hg_test_text_stream": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),

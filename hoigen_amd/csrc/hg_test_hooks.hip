@@ -1,4 +1,5 @@
-// Test hooks: single kernels behind the C ABI, operands rounded to fp16 on the device (tests/test_gpu_gemm.py, test_gpu_attention*.py);
+// Test hooks: single kernels behind the C ABI, operands rounded to fp16 on the device (tests/test_gpu_gemm.py, test_gpu_attention*.py,
+// test_gpu_qkv_attn_bound.py);
 // hg_test_elem: one launcher of hg_elem.hip on the caller's own buffers, nothing converted (tests/test_gpu_elem.py).
 #include "hg_host.h"
 
@@ -278,45 +279,61 @@ int hg_test_attention(hg_ctx* c, const float* qkv, const float* q0, const int32_
     return HG_OK;
 }
 
-int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
-                     int L, int heads, int fused, float* out, void* stream) {
-    if (!c || !a || !w || !cs || !mr || !out || n_seq <= 0 || heads < 1) return HG_ERR_INVALID;
+// One call of the fused in_proj + attention kernels, or of the two launches they replace, with the arguments production sets
+// (include/hoigen_amd.h has the contract; tests/test_gpu_qkv_attn_bound.py).  Every refusal is decided before anything is written.
+int hg_test_qkv_attn_ex(hg_ctx* c, const hg_test_qkv_attn_ex_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x || !x->a || !x->w || !x->cs || !x->mr || !x->out || x->n_seq <= 0 || x->L <= 0 || x->heads < 1) return HG_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     HG_ON_DEVICE(c);
+    const int n_seq = x->n_seq, L = x->L, heads = x->heads;
+    int fused = x->fused;
     const int D = heads * 64, M = n_seq * L;
     const int K = D + ((fused & 2) ? 64 : 0);      // (bit 1: a is [M, D + 64], w [3D, D + 64] - the shape of a block with a folded adapter)
     // bit 2: the causal mask - the text tower's kernel (hg_qkv_attn_text.hip, L <= 80) against the folded GEMM + the causal attention launch
     const bool causal = (fused & 4) != 0;
     if ((fused & ~7) || (causal && (fused & 2))) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: fused must be 0 .. 5");
     fused &= 1;
-    // (the folded ring GEMM wants 512 rows: a shorter causal call runs it over zero rows up to there - a row's result does not
+    const int lda = x->lda ? x->lda : K, ldo = x->ldo ? x->ldo : D;
+    if (lda < K || ldo < D || lda % 8 || ldo % 8) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: lda >= K, ldo >= D, both multiples of 8");
+    if (x->pad_fill != 0 && x->pad_fill != 1) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: pad_fill is 0 or 1");
+    if (x->qkv_out && fused) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: qkv_out goes with the two launches (fused bit 0 clear)");
+    // (the folded ring GEMM wants 512 rows: a shorter causal call runs it over the pad rows up to there - a row's result does not
     // depend on the rows beside it)
     const int Mg = causal && M < 512 ? 512 : M;
     const size_t Mp = rup(Mg, 256);
-    if (fused && causal && !qkv_attn_text_ok(n_seq, L, D, heads, K))
+    if (fused && causal && !qkv_attn_text_ok(n_seq, L, D, heads, lda))
         return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused causal kernel");
-    if (fused && !causal && !qkv_attn_ok(n_seq, L, D, heads, K, K)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused kernel");
-    int rc = ensure(c, c->h, Mp * K * 2);
+    if (fused && !causal && !qkv_attn_ok(n_seq, L, D, heads, lda, K)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the fused kernel");
+    if (!fused) {
+        GemmArgs g = gemm_args(nullptr, lda, nullptr, x->bias, nullptr, 3 * D, Mg, 3 * D, K);
+        g.cs = x->cs; g.mr = x->mr;
+        if (!gemm_ln_ok(EPI_LN_BIAS_F16, g)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the folded GEMM");
+    }
+    int rc = ensure(c, c->h, Mp * lda * 2);
+    if (!rc) rc = ensure(c, c->hg, (size_t)M * K * 2);
     if (!rc) rc = ensure(c, c->fc, (size_t)3 * D * K * 2 * 2 + (size_t)(heads / 2 + 1) * 768 * 4);
     if (!rc) rc = ensure(c, c->qkv, Mp * 3 * D * 2);
-    if (!rc) rc = ensure(c, c->att, Mp * D * 2);
+    if (!rc) rc = ensure(c, c->att, Mp * ldo * 2);
     if (!rc) rc = ensure(c, c->mr, Mp * 2 * 4);
     if (rc) return rc;
     half_t* w16 = (half_t*)c->fc.p;
     half_t* wp = w16 + (size_t)3 * D * K;
     float* bcs = (float*)(wp + (size_t)3 * D * K);
-    HG_HIP(hipMemsetAsync(c->h.p, 0, Mp * K * 2, s));
-    HG_HIP(launch_f32_to_f16(a, (half_t*)c->h.p, (size_t)M * K, s));
-    HG_HIP(launch_f32_to_f16(w, w16, (size_t)3 * D * K, s));
+    // rows M .. Mp - 1 and columns K .. lda - 1 of the operand: zeros, or fp16 NaN (the byte 0x7E twice)
+    HG_HIP(hipMemsetAsync(c->h.p, x->pad_fill ? 0x7E : 0, Mp * lda * 2, s));
+    HG_HIP(launch_f32_to_f16(x->a, (half_t*)c->hg.p, (size_t)M * K, s));
+    HG_HIP(hipMemcpy2DAsync(c->h.p, (size_t)lda * 2, c->hg.p, (size_t)K * 2, (size_t)K * 2, M, hipMemcpyDeviceToDevice, s));
+    HG_HIP(launch_f32_to_f16(x->w, w16, (size_t)3 * D * K, s));
     HG_HIP(hipMemsetAsync(c->mr.p, 0, Mp * 2 * 4, s));
-    HG_HIP(hipMemcpyAsync(c->mr.p, mr, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
-    HG_HIP(hipMemsetAsync(c->att.p, 0, Mp * D * 2, s));
+    HG_HIP(hipMemcpyAsync(c->mr.p, x->mr, (size_t)M * 2 * 4, hipMemcpyDeviceToDevice, s));
+    HG_HIP(hipMemsetAsync(c->att.p, 0x5A, Mp * ldo * 2, s));      // what a kernel does not write comes back as 203.25
     if (fused) {
-        HG_HIP(launch_pack_qkv(w16, bias, cs, wp, bcs, D, heads, s, K));
+        HG_HIP(launch_pack_qkv(w16, x->bias, x->cs, wp, bcs, D, heads, s, K));
         QkvAttnArgs qa{};
-        qa.x16 = (const half_t*)c->h.p; qa.lda = K; qa.K = K; qa.wp = wp; qa.bcs = bcs; qa.mr = (const float*)c->mr.p;
-        qa.out = (half_t*)c->att.p; qa.ldo = D; qa.n_seq = n_seq; qa.L = L; qa.D = D; qa.heads = heads;
-        qa.gsz = c->opt_qkv_attn_gsz; qa.a_bytes = (unsigned)(Mp * (size_t)K * 2);
+        qa.x16 = (const half_t*)c->h.p; qa.lda = lda; qa.K = K; qa.wp = wp; qa.bcs = bcs; qa.mr = (const float*)c->mr.p;
+        qa.out = (half_t*)c->att.p; qa.ldo = ldo; qa.n_seq = n_seq; qa.L = L; qa.D = D; qa.heads = heads;
+        qa.gsz = c->opt_qkv_attn_gsz; qa.a_bytes = (unsigned)(Mp * (size_t)lda * 2);
 #ifdef HG_STAMPS
         if (!(rc = ensure(c, c->cq, 256 * 8 * 16 * 8))) qa.dbg = (unsigned long long*)c->cq.p;      // read back by tools/qkv_attn_stamps.py
         else return rc;
@@ -325,6 +342,7 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
         ProfScope ps(c, s, HG_PROF_QKV_ATTN, n_seq, L, heads);
         hipError_t e = causal ? launch_qkv_attn_text(qa, s) : launch_qkv_attn(qa, s);
         ps.finish();
+        if (e == hipErrorInvalidValue) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: refused by the launcher");
         if (e != hipSuccess) return fail(c, HG_ERR_HIP, "test qkv_attn launch failed: %s", hipGetErrorString(e));
 #ifdef HG_STAMPS
         {      // diagnostic build: median over workgroups of the per-wave s_memtime totals of every phase (hg_qkv_attn.hip QA_ST)
@@ -348,14 +366,23 @@ int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bia
         }
 #endif
     } else {
-        GemmArgs g = gemm_args((const half_t*)c->h.p, K, w16, bias, c->qkv.p, 3 * D, Mg, 3 * D, K);
-        g.cs = cs; g.mr = (const float*)c->mr.p;
-        if (!gemm_ln_ok(EPI_LN_BIAS_F16, g)) return fail(c, HG_ERR_INVALID, "hg_test_qkv_attn: shape not eligible for the folded GEMM");
+        GemmArgs g = gemm_args((const half_t*)c->h.p, lda, w16, x->bias, c->qkv.p, 3 * D, Mg, 3 * D, K);
+        g.cs = x->cs; g.mr = (const float*)c->mr.p;
         HG_HIP(gemm(c, EPI_LN_BIAS_F16, g, s));
-        HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, causal, s));
+        HG_HIP(attention(c, (const half_t*)c->qkv.p, (half_t*)c->att.p, n_seq, L, heads, causal, s, ldo));
+        if (x->qkv_out) HG_HIP(launch_f16_to_f32((const half_t*)c->qkv.p, x->qkv_out, (size_t)M * 3 * D, s));
     }
-    HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (size_t)M * D, s));
+    HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, x->out, (size_t)M * ldo, s));
     return HG_OK;
+}
+
+// (hg_test_qkv_attn_ex with dense rows and zeroed pad rows)
+int hg_test_qkv_attn(hg_ctx* c, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
+                     int L, int heads, int fused, float* out, void* stream) {
+    hg_test_qkv_attn_ex_args x{};
+    x.a = a; x.w = w; x.bias = bias; x.cs = cs; x.mr = mr; x.out = out;
+    x.n_seq = n_seq; x.L = L; x.heads = heads; x.fused = fused;
+    return hg_test_qkv_attn_ex(c, &x, stream);
 }
 
 // One launcher of hg_elem.hip with the caller's own device buffers (include/hoigen_amd.h has the table of operands; tests/test_gpu_elem.py).

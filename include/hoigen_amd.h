@@ -419,6 +419,30 @@ int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t*
  * attention launch run_blocks picks at that L.  Values above 5 are HG_ERR_INVALID. */
 int hg_test_qkv_attn(hg_ctx*, const float* a, const float* w, const float* bias, const float* cs, const float* mr, int n_seq,
                      int L, int heads, int fused, float* out, void* stream);
+/* Test hook: hg_test_qkv_attn with the arguments a tower call sets and that hook cannot (it is this one with lda = ldo = 0, pad_fill = 0,
+ * qkv_out = NULL).  All pointers are device fp32.
+ *   a [M, K]       dense, M = n_seq * L, K = D (+ 64 with fused bit 1); laid out inside as fp16 rows of stride lda
+ *   w [3D, K], bias [3D] or NULL, cs [3D], mr [M, 2], n_seq, L, heads, fused: as hg_test_qkv_attn
+ *   lda            0 = K; >= K, a multiple of 8.  A tower call has lda = D + 64 with K = D in a block whose adapter is not folded
+ *   ldo            0 = D; >= D, a multiple of 8.  out [M, ldo]: WHOLE rows come back; the fp16 output buffer is filled with the pattern
+ *                  0x5A5A first, so every column >= D of a row (and whatever else a kernel leaves unwritten) comes back as 203.25
+ *   pad_fill       what rows M .. Mp - 1 (Mp = M rounded up to 256; 512 at least under the causal mask) and columns K .. lda - 1 of the
+ *                  operand buffer hold: 0 zeros, 1 fp16 NaN.  The pad rows of mr are zero either way.  The kernels are told
+ *                  a_bytes = Mp * lda * 2 readable bytes, as a tower call computes it
+ *   qkv_out        NULL, or [M, 3D]: the fp16 q | k | v the folded GEMM wrote.  With fused bit 0 clear only
+ * HG_ERR_INVALID, with nothing written, for lda / ldo / pad_fill out of range, qkv_out with fused bit 0 set, and whatever the
+ * launchers' own eligibility tests (qkv_attn_ok, qkv_attn_text_ok, gemm_ln_ok) refuse. */
+typedef struct {
+    const float* a;
+    const float* w;
+    const float* bias;
+    const float* cs;
+    const float* mr;
+    float* out;
+    float* qkv_out;
+    int32_t n_seq, L, heads, fused, lda, ldo, pad_fill;
+} hg_test_qkv_attn_ex_args;
+int hg_test_qkv_attn_ex(hg_ctx*, const hg_test_qkv_attn_ex_args* args, void* stream);
 
 /* Test hooks for the whole residual stream of a tower (every row, not only the rows that reach an output): as
  * hg_encode_image / hg_encode_text_ids (same options, `out` bit for bit the same), additionally copying the stream into

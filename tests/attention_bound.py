@@ -1,5 +1,5 @@
-"""What the attention kernels (hg_attn.hip, hg_attn_long.hip, and through bit-identity the attention half of hg_qkv_attn.hip and
-hg_qkv_attn_text.hip) are held to: an exact float64 softmax(q k^T / 8) v of the fp16-rounded inputs, computed on the CPU, and a bound PER
+"""What the attention kernels (hg_attn.hip, hg_attn_long.hip; the attention half of hg_qkv_attn.hip and hg_qkv_attn_text.hip is held to
+it on hard operands of its own, and one term more for subnormal outputs, by tests/qkv_attn_bound.py) are held to: an exact float64 softmax(q k^T / 8) v of the fp16-rounded inputs, computed on the CPU, and a bound PER
 OUTPUT ELEMENT that is the sum of the worst case of each fp16 rounding tile_softmax_pv (hg_attn_dev.h) performs.  A plain module beside the
 tests (tests/test_attention_rounding_model.py, tests/test_gpu_attention.py, tests/test_gpu_attention_long.py import it): no fixtures, no
 GPU, no library.
