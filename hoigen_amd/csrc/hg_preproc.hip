@@ -18,6 +18,9 @@
 //   h_bounds[n_px][2] (first tap, count)  h_kk[n_px][ks_h]  v_bounds[n_px][2]  v_kk[n_px][ks_v]
 // "src" is the virtual image the resize sees: the crop, pasted at (pad_x, pad_y) into src_w x src_h of
 // background when square padding is on.  n_rows source rows [row_lo, row_lo + n_rows) feed the vertical pass.
+//
+// This file is compiled with -ffp-contract=off (build.sh): under the library's -ffp-contract=fast the backend fuses multiply-add pairs
+// whatever the `fp contract(off)` pragmas below say, and both the weight tables and roi_align_kernel promise one rounding per operation.
 #include "hg_kernels.h"
 
 namespace hg {

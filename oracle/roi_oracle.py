@@ -18,7 +18,9 @@ PARITY UNPINNED against the real library: no torchvision here to generate vector
 tests/test_roi_align.py anchors this restatement on (a) analytic properties (constant and affine feature maps, for
 which bilinear sampling is exact) and (b) hand-derived known-answer vectors (tests/golden/roi_known_answers.py) that
 separate the aligned=True half-pixel offset, the adaptive ceil(roi/P) sampling grid and the boundary rules from their
-alternatives.
+alternatives.  tests/roi_bound.py adds a float64 cross-check from another hand: the operation written from its definition (tent
+functions, matrix products), to which this restatement is held per element within a derived rounding bound
+(tests/test_roi_model.py) - a mistake shared by this file and the kernel, which restate the same published order, would show there.
 """
 import math
 

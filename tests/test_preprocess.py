@@ -52,7 +52,7 @@ def test_hip_preprocess_bit_exact_vs_pillow_goldens(g6):
         out, u8 = preprocess.CropPreprocessor(224)(img, g6[f"boxes{ci}"], return_u8=True)
         assert np.array_equal(u8.cpu().numpy(), g6[f"u8_{ci}"]), "uint8 crops must be bit-exact"
         if ci == 0:
-            assert np.abs(out.cpu().numpy() - g6["norm_0"]).max() <= 1e-6
+            assert np.array_equal(out.cpu().numpy().view(np.int32), g6["norm_0"].view(np.int32))      # bits (tests/preproc_cases.py)
         _, u8s = preprocess.CropPreprocessor(224, pad_square=True)(img, g6[f"boxes{ci}"][:2], return_u8=True)
         assert np.array_equal(u8s.cpu().numpy(), g6[f"u8_sq_{ci}"])
         # IResize([224, 224]) + ImageNet normalisation (the detector's CLIP view, utils_tip...:86-89,105-114)
@@ -60,7 +60,7 @@ def test_hip_preprocess_bit_exact_vs_pillow_goldens(g6):
         outr, u8r = pre(img, g6[f"stretch_boxes{ci}"], return_u8=True)
         assert np.array_equal(u8r.cpu().numpy(), g6[f"stretch_u8_{ci}"])
         _, want = po.preprocess_boxes(g6[f"img{ci}"], g6[f"stretch_boxes{ci}"], stretch=True, imagenet_norm=True)
-        assert np.abs(outr.cpu().numpy() - want).max() <= 1e-6
+        assert np.array_equal(outr.cpu().numpy().view(np.int32), want.view(np.int32))
     img0 = torch.from_numpy(g6["img0"]).to(dev)
     assert preprocess.CropPreprocessor()(img0, np.zeros((0, 4), np.int32)).shape == (0, 3, 224, 224)
     with pytest.raises(ValueError):
@@ -84,7 +84,7 @@ def test_hip_preprocess_vs_oracle_random_boxes_and_pipeline():
         want_u8, want = po.preprocess_boxes(img, boxes, 224, pad, bg)
         out, u8 = preprocess.CropPreprocessor(224, pad, bg)(torch.from_numpy(img).to(dev), boxes, return_u8=True)
         assert np.array_equal(u8.cpu().numpy(), want_u8)
-        assert np.abs(out.cpu().numpy() - want).max() <= 1e-6
+        assert np.array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
     from hoigen_amd import synth
     from hoigen_amd.model import build_model
     m = build_model(synth.to_torch(synth.clip_state_dict(synth.VIT_B16, 0))).to(dev)

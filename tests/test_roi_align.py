@@ -17,6 +17,8 @@ from oracle import roi_oracle as ro  # noqa: E402
 SCALE = 14.0 / 224.0
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from roi_known_answers import cases as roi_cases  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import roi_bound as rb  # noqa: E402
 
 
 def test_oracle_known_answers():
@@ -116,10 +118,10 @@ def test_hip_roi_align_vs_oracle():
     f, b = torch.from_numpy(feat).to(dev), torch.from_numpy(boxes).to(dev)
     got = roi_align(f.unsqueeze(0), b, (7, 7), SCALE, aligned=True)
     assert got.shape == (44, 512, 7, 7) and got.dtype == torch.float32
-    assert np.abs(got.cpu().numpy() - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
+    assert np.array_equal(got.cpu().numpy().view(np.int32), want.view(np.int32))      # bits (tests/roi_bound.py, rule 1)
     mean = roi_align(f, b, 7, SCALE, reduce_mean=True)
-    want_mean = want.reshape(44, 512, -1).mean(-1, dtype=np.float32)
-    assert np.abs(mean.cpu().numpy() - want_mean).max() <= 1e-5
+    want_mean = rb.restate(feat, boxes, 7, SCALE)[1]      # the kernel's own order: a sequential fp32 sum over the bins, / 49
+    assert np.array_equal(mean.cpu().numpy().view(np.int32), want_mean.view(np.int32))
     assert roi_align(f, torch.zeros(0, 4, device=dev), 7, SCALE).shape == (0, 512, 7, 7)
     # hand-derived known answers on the device (half-pixel offset, adaptive grid, boundary rules)
     for feat_k, box, scale, P, want_k, what in roi_cases():
@@ -145,5 +147,5 @@ def test_hip_roi_align_on_variant_c_local_map():
     _, local = m.visual(img, None)
     boxes = torch.tensor([[10., 20., 120., 200.], [0., 0., 224., 224.]], device=dev)
     out = roi_align(local[0], boxes, 7, SCALE, reduce_mean=True)
-    want = ro.roi_align_mean(local[0].cpu().numpy(), boxes.cpu().numpy(), 7, SCALE)
-    assert out.shape == (2, 512) and np.abs(out.cpu().numpy() - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
+    want = rb.restate(local[0].float().cpu().numpy(), boxes.cpu().numpy(), 7, SCALE)[1]
+    assert out.shape == (2, 512) and np.array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))

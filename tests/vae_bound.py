@@ -155,13 +155,29 @@ def hidden(a16, w0, b0):
     return pre, h, e_pre + f16_term(h + e_pre), S
 
 
+def chain(a16, layers):
+    """(want, E) [R, N] of a chain of GEMMs from the fp16 operand a16: layers = [(w [N, K], b [N] or None, relu)], every operand float64,
+    weights fp16 numbers.  Every layer but the last is rounded once to fp16 (after its relu, where it has one) and carries its error
+    E_h into the next: E_h @ |w| for what the operand is off, K 2^-23 (|h| + E_h) @ |w| for the accumulation (K + 1 terms and + |b| with
+    a bias, which starts the MFMA chain or is added by the epilogue: the bound covers both).  The last layer is returned in fp32: its
+    bias add rounds once, u |want|.  chain(a16, [(w0, b0, True), (w2, b2, False)]) is `two_layer` term for term."""
+    h, e_h = a16, torch.zeros_like(a16)
+    for i, (w, b, relu) in enumerate(layers):
+        K, aw = w.shape[1], w.abs().t()
+        last = i == len(layers) - 1
+        pre = h @ w.t() + (b[None] if b is not None else 0.0)
+        S = (h.abs() + e_h) @ aw
+        if last:
+            e = e_h @ aw + K * 2.0 ** -23 * S
+            return pre, (e + U * pre.abs() if b is not None else e)
+        e_pre = e_h @ aw + ((K + 1) * 2.0 ** -23 * (S + b.abs()[None]) if b is not None else K * 2.0 ** -23 * S)
+        h = pre.clamp_min(0.0) if relu else pre
+        e_h = e_pre + f16_term(h.abs() + e_pre)
+
+
 def two_layer(a16, w0, b0, w2, b2):
     """(want, E) [R, N] of relu(a16 w0^T + b0) w2^T + b2; every operand float64, a16 / w0 / w2 fp16 numbers"""
-    H = w0.shape[0]
-    _, h, e_h, _ = hidden(a16, w0, b0)
-    want = h @ w2.t() + b2[None]
-    aw = w2.abs().t()
-    return want, e_h @ aw + H * 2.0 ** -23 * ((h + e_h) @ aw) + U * want.abs()
+    return chain(a16, [(w0, b0, True), (w2, b2, False)])
 
 
 def _d(t, rows=None):
