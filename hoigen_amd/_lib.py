@@ -84,6 +84,24 @@ class hg_cache_weights(C.Structure):
                 ("S", C.c_int32), ("K", C.c_int32), ("C", C.c_int32), ("post_div", C.c_float)]
 
 
+HG_HOI_MAX_BRANCH = 6
+HG_HOI_SRC = {"human": 0, "object": 1, "union": 2, "human_object": 3, "global": 4}
+
+
+class hg_hoi_branch(C.Structure):
+    _fields_ = [("source", C.c_int32), ("slot", C.c_int32), ("scale", C.c_float)]
+
+
+class hg_hoi_head_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("feat_local", "feat_global", "boxes", "scores", "labels")] + \
+               [("box_off", C.POINTER(C.c_int32)), ("n_human", C.POINTER(C.c_int32))] + \
+               [(n, C.c_int32) for n in ("B", "C", "H", "W", "P")] + [("spatial_scale", C.c_float), ("n_branch", C.c_int32),
+                ("branch", hg_hoi_branch * HG_HOI_MAX_BRANCH), ("obj2target", C.c_void_p), ("n_obj_classes", C.c_int32),
+                ("num_classes", C.c_int32), ("score_pow", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("pair_h", "pair_o", "objects", "union_boxes", "pooled_single", "pooled_union", "feats",
+                                          "branch_logits", "logits", "prior", "scores_out")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -132,6 +150,7 @@ SIGNATURES = {
     "hg_roi_align": (_I, [_P, _P, _I, _I, _I, _P, _I, C.c_float, _I, _P, _P, _P]),
     "hg_load_cache": (_I, [_P, _I, _P]),
     "hg_cache_logits": (_I, [_P, _I, _P, _I, _P, _P]),
+    "hg_hoi_head": (_I, [_P, C.POINTER(hg_hoi_head_args), _P]),
     "hg_preprocess_crops": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),

@@ -25,6 +25,30 @@ inline int fused_item_rows(const hg_ctx* c, int opt, int R) {
     return (int)(rows < R ? rows : R);
 }
 
+// One chunk of Rc rows of a cache slot from its fp16 operand f16 [rup(Rc, 256), lda] -> out [Rc, Nout]: what hg_cache_logits issues per
+// chunk behind its conversion, and what hg_hoi_head issues per branch on the rows hoi_feats_kernel wrote (lda = 2 K for the human and
+// the object half of the human | object buffer).
+int cache_logits_rows(hg_ctx* c, Cache& m, const half_t* f16, int lda, int Rc, float* out, hipStream_t s) {
+    const size_t Rp = rup(Rc, 256);
+    const int Np = m.has_labels ? m.Cp : m.Sp, Nout = m.has_labels ? m.C : m.S;
+    int rc = ensure(c, c->att, Rp * m.Sp * 2);
+    if (!rc) rc = ensure(c, c->x, Rp * Np * 4);
+    if (rc) return rc;
+    half_t* phi = (half_t*)c->att.p;
+    float* tmp = (float*)c->x.p;
+    if (!m.has_labels) {
+        HG_HIP(gemm(c, EPI_BIAS_F32, gemm_args(f16, lda, m.w16, m.b, tmp, m.Sp, Rc, m.Sp, m.K), s));
+    } else {
+        HG_HIP(gemm(c, EPI_BIAS_F16, gemm_args(f16, lda, m.w16, nullptr, phi, m.Sp, Rc, m.Sp, m.K), s));
+        HG_HIP(hipMemsetAsync(tmp, 0, (size_t)Rc * m.Cp * 4, s));
+        GemmArgs g = gemm_args(phi, m.Sp, m.lt16, m.bias_c, tmp, m.Cp, Rc, m.Cp, m.Sp);
+        g.pos = m.scale;
+        HG_HIP(gemm(c, EPI_SCALE_RESID_F32, g, s));          // 0 + (phi L + b L) * scale
+    }
+    HG_HIP(launch_copy_cols(tmp, Np, out, Rc, Nout, s));
+    return HG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -40,27 +64,110 @@ int hg_cache_logits(hg_ctx* c, int slot, const float* feats, int R, float* out, 
     HG_ON_DEVICE(c);
     for (int r0 = 0, Rc = 0; r0 < R; r0 += Rc) {
         Rc = chunk_rows(c, R - r0);
-        const size_t Rp = rup(Rc, 256);
-        const int Np = m.has_labels ? m.Cp : m.Sp, Nout = m.has_labels ? m.C : m.S;
-        int rc = ensure(c, c->h, Rp * m.K * 2);
-        if (!rc) rc = ensure(c, c->att, Rp * m.Sp * 2);
-        if (!rc) rc = ensure(c, c->x, Rp * Np * 4);
+        int rc = ensure(c, c->h, rup(Rc, 256) * m.K * 2);
         if (rc) return rc;
         half_t* f16 = (half_t*)c->h.p;
-        half_t* phi = (half_t*)c->att.p;
-        float* tmp = (float*)c->x.p;
         HG_HIP(launch_f32_to_f16(feats + (size_t)r0 * m.K, f16, (size_t)Rc * m.K, s));
-        if (!m.has_labels) {
-            HG_HIP(gemm(c, EPI_BIAS_F32, gemm_args(f16, m.K, m.w16, m.b, tmp, m.Sp, Rc, m.Sp, m.K), s));
-        } else {
-            HG_HIP(gemm(c, EPI_BIAS_F16, gemm_args(f16, m.K, m.w16, nullptr, phi, m.Sp, Rc, m.Sp, m.K), s));
-            HG_HIP(hipMemsetAsync(tmp, 0, (size_t)Rc * m.Cp * 4, s));
-            GemmArgs g = gemm_args(phi, m.Sp, m.lt16, m.bias_c, tmp, m.Cp, Rc, m.Cp, m.Sp);
-            g.pos = m.scale;
-            HG_HIP(gemm(c, EPI_SCALE_RESID_F32, g, s));          // 0 + (phi L + b L) * scale
-        }
-        HG_HIP(launch_copy_cols(tmp, Np, out + (size_t)r0 * Nout, Rc, Nout, s));
+        rc = cache_logits_rows(c, m, f16, m.K, Rc, out + (size_t)r0 * (m.has_labels ? m.C : m.S), s);
+        if (rc) return rc;
     }
+    return HG_OK;
+}
+
+// ---- interaction head (hg_hoi_head.hip) --------------------------------------------------------------------------------------------
+int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!a) return fail(c, HG_ERR_INVALID, "hg_hoi_head: no arguments");
+    if (a->B < 0 || a->B > HOI_MAX_IMAGES) return fail(c, HG_ERR_INVALID, "hg_hoi_head: %d images (at most %d a call)", a->B, HOI_MAX_IMAGES);
+    if (a->B == 0) return HG_OK;
+    if (!a->box_off || !a->n_human) return fail(c, HG_ERR_INVALID, "hg_hoi_head: box_off / n_human missing");
+    if (a->H <= 0 || a->W <= 0 || a->H > HOI_MAX_SIDE || a->W > HOI_MAX_SIDE || a->C <= 0 || a->C > HOI_MAX_C || a->P <= 0 ||
+        a->P > HOI_MAX_P)
+        return fail(c, HG_ERR_INVALID, "hg_hoi_head: map %d x %d x %d, P = %d (H, W <= %d, C <= %d, P <= %d)", a->C, a->H, a->W, a->P, HOI_MAX_SIDE,
+                    HOI_MAX_C, HOI_MAX_P);
+    if (a->n_branch < 0 || a->n_branch > HG_HOI_MAX_BRANCH)
+        return fail(c, HG_ERR_INVALID, "hg_hoi_head: %d branches (at most %d)", a->n_branch, HG_HOI_MAX_BRANCH);
+    HoiBatch hb{};
+    hb.B = a->B;
+    long pairs = 0;
+    for (int b = 0; b < a->B; ++b) {
+        const long n = (long)a->box_off[b + 1] - a->box_off[b], nh = a->n_human[b];
+        if (a->box_off[0] != 0 || n < 0) return fail(c, HG_ERR_INVALID, "hg_hoi_head: box_off must start at 0 and not decrease (image %d)", b);
+        if (nh < 0 || nh > n) return fail(c, HG_ERR_INVALID, "hg_hoi_head: image %d has %ld humans among %ld boxes", b, nh, n);
+        hb.box_off[b] = a->box_off[b];
+        hb.pair_off[b] = (int)pairs;
+        pairs += n > 1 ? nh * (n - 1) : 0;
+        if (pairs > (1 << 24)) return fail(c, HG_ERR_INVALID, "hg_hoi_head: more than 2^24 pairs");
+    }
+    hb.box_off[a->B] = hb.N = a->box_off[a->B];
+    hb.pair_off[a->B] = hb.Pt = (int)pairs;
+    if (hb.N == 0) return HG_OK;
+    const int C = a->C, NC = a->num_classes, nb = a->n_branch, Pt = hb.Pt;
+    if (!a->feat_local || !a->boxes) return fail(c, HG_ERR_INVALID, "hg_hoi_head: feat_local / boxes missing");
+    bool global = false;
+    if (nb > 0) {
+        if (C % 64) return fail(c, HG_ERR_INVALID, "hg_hoi_head: C = %d is not a multiple of 64 (the branch GEMMs' K)", C);
+        if (NC <= 0 || !a->logits) return fail(c, HG_ERR_INVALID, "hg_hoi_head: num_classes / logits missing");
+        for (int i = 0; i < nb; ++i) {
+            const hg_hoi_branch& br = a->branch[i];
+            if (br.source < HG_HOI_SRC_HUMAN || br.source > HG_HOI_SRC_GLOBAL)
+                return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d has source %d", i, br.source);
+            if (br.slot < 0 || br.slot >= HG_MAX_CACHE_SLOTS || !c->cache[br.slot].loaded)
+                return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d: cache slot %d not loaded", i, br.slot);
+            const Cache& m = c->cache[br.slot];
+            const int K = br.source == HG_HOI_SRC_HUMAN_OBJECT ? 2 * C : C, Nout = m.has_labels ? m.C : m.S;
+            if (m.K != K || Nout != NC)
+                return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d: slot %d maps %d -> %d, the branch needs %d -> %d", i, br.slot, m.K, Nout, K, NC);
+            if (br.source == HG_HOI_SRC_GLOBAL) global = true;
+        }
+        if (global && !a->feat_global) return fail(c, HG_ERR_INVALID, "hg_hoi_head: a global branch without feat_global");
+    }
+    const bool want_prior = a->prior || a->scores_out;
+    if (nb == 0 && a->scores_out) return fail(c, HG_ERR_INVALID, "hg_hoi_head: scores need logits, and there is no branch");
+    if (want_prior && (!a->scores || !a->labels || !a->obj2target || a->n_obj_classes <= 0 || NC <= 0))
+        return fail(c, HG_ERR_INVALID, "hg_hoi_head: prior / scores need scores, labels, obj2target and num_classes");
+    if (a->objects && !a->labels) return fail(c, HG_ERR_INVALID, "hg_hoi_head: objects need labels");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Rp = rup(std::max(Pt, 1), 256);
+    int rc = ensure(c, c->hoi_tab, (size_t)(hb.N + Pt) * HOI_TAB * 4);
+    if (!rc && !(a->pooled_single && (a->pooled_union || !Pt))) rc = ensure(c, c->hoi_pool, (size_t)(hb.N + Pt) * C * 4);
+    if (!rc && nb > 0 && Pt > 0) rc = ensure(c, c->hoi_a16, Rp * C * 2 * (global ? 4 : 3));
+    if (!rc && nb > 0 && Pt > 0 && !a->branch_logits) rc = ensure(c, c->hoi_br, (size_t)nb * Pt * NC * 4);
+    if (rc) return rc;
+    float* tab = (float*)c->hoi_tab.p;
+    float* ps = a->pooled_single ? a->pooled_single : (float*)c->hoi_pool.p;
+    float* pu = a->pooled_union ? a->pooled_union : (float*)c->hoi_pool.p + (size_t)hb.N * C;
+    HG_HIP(launch_hoi_setup(hb, a->boxes, a->labels, a->spatial_scale, a->P, a->H, a->W, a->pair_h, a->pair_o, a->objects, a->union_boxes, tab, s));
+    HG_HIP(launch_hoi_pool(hb, a->feat_local, C, a->H, a->W, a->P, tab, ps, pu, c->n_cu, s));
+    if (Pt == 0) return HG_OK;
+    half_t* ho16 = nb > 0 ? (half_t*)c->hoi_a16.p : nullptr;
+    half_t* u16 = nb > 0 ? ho16 + Rp * 2 * C : nullptr;
+    half_t* g16 = global ? u16 + Rp * C : nullptr;
+    if (nb > 0 || a->feats) HG_HIP(launch_hoi_feats(hb, ps, pu, a->feat_global, C, a->feats, ho16, u16, g16, s));
+    HoiEpilogue e{};
+    e.n = nb;
+    float* br_out = a->branch_logits ? a->branch_logits : (float*)c->hoi_br.p;
+    for (int i = 0; i < nb; ++i) {
+        const hg_hoi_branch& br = a->branch[i];
+        Cache& m = c->cache[br.slot];
+        const half_t* A = br.source == HG_HOI_SRC_UNION ? u16 : br.source == HG_HOI_SRC_GLOBAL ? g16 : ho16 + (br.source == HG_HOI_SRC_OBJECT ? C : 0);
+        const int lda = br.source == HG_HOI_SRC_UNION || br.source == HG_HOI_SRC_GLOBAL ? C : 2 * C;
+        float* out = br_out + (size_t)i * Pt * NC;
+        // Chunks are cut at multiples of 256 rows (option chunk_rows takes any value from 256 on): the GEMMs read whole 256-row tiles of
+        // A, and with every r0 a multiple of 256 the last chunk's tiles end at row rup(Pt, 256) = Rp, the rows each operand of hoi_a16 has.
+        for (int r0 = 0, Rc = 0; r0 < Pt; r0 += Rc) {
+            Rc = chunk_rows(c, Pt - r0);
+            if (r0 + Rc < Pt) Rc -= Rc % 256;
+            rc = cache_logits_rows(c, m, A + (size_t)r0 * lda, lda, Rc, out + (size_t)r0 * NC, s);
+            if (rc) return rc;
+        }
+        e.branch[i] = out;
+        e.scale[i] = br.scale;
+    }
+    if (nb > 0 || want_prior)
+        HG_HIP(launch_hoi_epilogue(hb, e, a->scores, a->labels, a->obj2target, a->n_obj_classes, NC, a->score_pow, nb > 0 ? a->logits : nullptr,
+                                   a->prior, a->scores_out, s));
     return HG_OK;
 }
 

@@ -287,6 +287,37 @@ hipError_t launch_preprocess(const uint8_t* img, int H, int W, const int32_t* he
 hipError_t launch_roi_align(const float* feat, int C, int H, int W, const float* boxes, int n, float spatial_scale,
                             int P, float* out_pooled, float* out_mean, hipStream_t s);
 
+// ---- interaction head (hg_hoi_head.hip): batched pair RoI pooling, operand rows, logits / priors / scores ----------------------
+static constexpr int HOI_MAX_IMAGES = 64;       // images per call (HoiBatch travels as a kernel argument)
+static constexpr int HOI_MAX_SIDE = 32;         // H, W of the local map at most
+static constexpr int HOI_MAX_C = 1024;
+static constexpr int HOI_MAX_P = 32;          // bins per side: P * P stays an int far below 2^24, a set-up thread walks at most P * HOI_MAX_GRID samples
+static constexpr int HOI_MAX_BRANCH = 6;
+static constexpr int HOI_MAX_GRID = 65536;      // samples per bin and axis beyond which a RoI is refused (its pooled row is NaN)
+static constexpr int HOI_TAB = 72;              // words per RoI of the table hoi_setup_kernel writes (layout: hg_hoi_head.hip)
+static constexpr size_t HOI_LDS_MAX = 160 * 1024;
+struct HoiBatch {      // host-built, by value: boxes of image b are rows box_off[b] .. box_off[b + 1] - 1, its pairs pair_off[b] ..
+    int B, N, Pt;      // images, boxes and pairs of the batch
+    int box_off[HOI_MAX_IMAGES + 1], pair_off[HOI_MAX_IMAGES + 1];
+};
+struct HoiEpilogue {
+    int n;
+    const float* branch[HOI_MAX_BRANCH];      // [Pt, NC] each
+    float scale[HOI_MAX_BRANCH];
+};
+int hoi_pool_chunk(int H, int W);             // channels per LDS chunk: 64 while 64 x (H W | 1) floats fit HOI_LDS_MAX (24 x 24 does), else 32
+hipError_t launch_hoi_setup(const HoiBatch& hb, const float* boxes, const int32_t* labels, float scale, int P, int H, int W,
+                            int32_t* pair_h, int32_t* pair_o, int32_t* objects, float* union_boxes, float* tab, hipStream_t s);
+hipError_t launch_hoi_pool(const HoiBatch& hb, const float* feat, int C, int H, int W, int P, const float* tab, float* pooled_single,
+                           float* pooled_union, int n_cu, hipStream_t s);
+// feats (nullable) fp32 [Pt, 3C] = human | object | union; ho16 [Pt, 2C], u16 [Pt, C], g16 (nullable; needs feat_global) [Pt, C]
+hipError_t launch_hoi_feats(const HoiBatch& hb, const float* pooled_single, const float* pooled_union, const float* feat_global, int C,
+                            float* feats, half_t* ho16, half_t* u16, half_t* g16, hipStream_t s);
+// logits [Pt, NC], prior [2, Pt, NC], out_scores [Pt, NC]: each nullable
+hipError_t launch_hoi_epilogue(const HoiBatch& hb, const HoiEpilogue& e, const float* scores, const int32_t* labels,
+                               const uint8_t* obj2target, int n_obj, int NC, float score_pow, float* logits, float* prior,
+                               float* out_scores, hipStream_t s);
+
 // ---- adapter (variant C) --------------------------------------------------------------------
 // tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
 static constexpr int ADAPTER_MAX_L = 224;

@@ -220,6 +220,57 @@ typedef struct {
 int hg_load_cache(hg_ctx*, int slot, const hg_cache_weights* w);
 int hg_cache_logits(hg_ctx*, int slot, const float* feats, int R, float* out, void* stream);
 
+/* The interaction head for a batch of images in one call: UPT.compute_roi_embeddings in eval mode with individual_norm = True,
+ * logits_type = 'HO+U+T', no DINO branch, no use_weight_pred, generated features not appended
+ * (upt_tip_cache_model_free_finetune_distill3.py:959-1268), compute_prior_scores (:806-833) and the score of postprocessing
+ * (:1408-1427).  Image b has the boxes box_off[b] .. box_off[b + 1] - 1, HUMANS FIRST (the caller applies the permutation of
+ * :988-996), n_human[b] of them humans.  Its pairs are all (x, y) with x < n_human[b], y != x, row-major (:1007-1012):
+ * n_human (n - 1) of them, none when n_human == 0 or n <= 1 (:998).  Pt = all pairs of the batch, N = box_off[B].
+ *   pair_h / pair_o / objects  int32 [Pt]: x, y (local to the image) and labels[y]                                      (:1245-1247)
+ *   union_boxes                [Pt, 4]: min / max of the two boxes' corners                                             (:1019-1023)
+ *   pooled_single [N, C], pooled_union [Pt, C]: torchvision.ops.roi_align(.., (P, P), spatial_scale, aligned=True)
+ *       .flatten(2).mean(-1) of every box and union box (:1027-1037), as ONE contraction per RoI and channel against the separable
+ *       weights of its samples - not hg_roi_align's operation order: equal within both rounding bounds, not bit for bit
+ *   feats                      [Pt, 3C] = human | object | union rows, each x / x.norm() (:1044-1050) as hg_l2_normalize computes it
+ *   branch_logits              [n_branch, Pt, num_classes]: branch i = hg_cache_logits(branch[i].slot) on the rows of its source:
+ *       human, object, union [Pt, C], human|object [Pt, 2C] (:1166) or feat_global[b] / its norm repeated over the image's pairs
+ *       (:960, :1132-1138)                                                                                              (:1156-1170)
+ *   logits                     [Pt, num_classes] = branch_0 * scale_0 + branch_1 * scale_1 + .., left to right          (:1195-1196)
+ *   prior                      [2, Pt, num_classes]: scores[x] ^ score_pow and scores[y] ^ score_pow on the columns where
+ *       obj2target[labels[y]] is set (uint8 [n_obj_classes, num_classes], device), 0 elsewhere                          (:806-833)
+ *   scores                     [Pt, num_classes] = sigmoid(logits) * prior[0] * prior[1]                                (:1417-1423)
+ * A zero-area box pools to 0 and its normalised row is NaN, as in the reference; so are the rows of every pair that contains it.
+ * feat_local fp32 [B, C, H, W] (hg_encode_image_prior's out_local), feat_global fp32 [B, C] (nullable without a global branch),
+ * boxes [N, 4] (x1, y1, x2, y2, image pixels), scores [N], labels int32 [N]: device.  box_off [B + 1], n_human [B]: HOST.
+ * Limits: B <= 64, H, W <= 32, C <= 1024, P <= 32, n_branch <= 6; with branches C % 64 == 0, every slot loaded (hg_load_cache) with K = C
+ * (2C for human|object) and output width num_classes.  n_branch == 0 pools only (any C; logits may be NULL, prior may be asked for, scores_out may not: HG_ERR_INVALID).  Every output but
+ * logits may be NULL.  Asynchronous on `stream`. */
+#define HG_HOI_MAX_BRANCH 6
+#define HG_HOI_SRC_HUMAN 0
+#define HG_HOI_SRC_OBJECT 1
+#define HG_HOI_SRC_UNION 2
+#define HG_HOI_SRC_HUMAN_OBJECT 3
+#define HG_HOI_SRC_GLOBAL 4
+typedef struct {
+    int32_t source, slot;
+    float scale;
+} hg_hoi_branch;
+typedef struct {
+    const float *feat_local, *feat_global, *boxes, *scores;
+    const int32_t* labels;
+    const int32_t *box_off, *n_human;
+    int32_t B, C, H, W, P;
+    float spatial_scale;
+    int32_t n_branch;
+    hg_hoi_branch branch[HG_HOI_MAX_BRANCH];
+    const uint8_t* obj2target;
+    int32_t n_obj_classes, num_classes;
+    float score_pow;
+    int32_t *pair_h, *pair_o, *objects;
+    float *union_boxes, *pooled_single, *pooled_union, *feats, *branch_logits, *logits, *prior, *scores_out;
+} hg_hoi_head_args;
+int hg_hoi_head(hg_ctx*, const hg_hoi_head_args* args, void* stream);
+
 /* Crop pre-processing in front of encode_image: for every box of one image
  *   image.crop(box)                       pre_images/crop_images.py:204-219 (PIL: zeros outside the image)
  *   [expand2square(crop, background)]     utils_tip_cache_and_union_finetune.py:201-212  (pad_square != 0)
