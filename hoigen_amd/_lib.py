@@ -102,6 +102,23 @@ class hg_hoi_head_args(C.Structure):
                                           "branch_logits", "logits", "prior", "scores_out")]
 
 
+HG_MAX_PRIOR_SLOTS = 4
+
+
+class hg_prior_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "hidden", "out", "n_obj_classes")] + \
+               [(n, hg_tensor) for n in ("w0", "b0", "w1", "b1", "w2", "b2", "object_embedding")]
+
+
+class hg_region_priors_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("scores", "labels", "boxes")] + \
+               [("q_off", C.POINTER(C.c_int32)), ("image_sizes", C.POINTER(C.c_float)), ("B", C.c_int32),
+                ("box_score_thresh", C.c_float), ("nms_thresh", C.c_float)] + \
+               [(n, C.c_int32) for n in ("human_idx", "min_instances", "max_instances", "prior_slot")] + \
+               [(n, C.c_void_p) for n in ("counts", "keep", "out_boxes", "out_scores", "out_labels", "survivors", "priors", "mask",
+                                          "table_out")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -151,6 +168,8 @@ SIGNATURES = {
     "hg_load_cache": (_I, [_P, _I, _P]),
     "hg_cache_logits": (_I, [_P, _I, _P, _I, _P, _P]),
     "hg_hoi_head": (_I, [_P, C.POINTER(hg_hoi_head_args), _P]),
+    "hg_load_priors": (_I, [_P, _I, C.POINTER(hg_prior_weights)]),
+    "hg_region_priors": (_I, [_P, C.POINTER(hg_region_priors_args), _P]),
     "hg_preprocess_crops": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),

@@ -102,6 +102,7 @@ void hg_destroy(hg_ctx* c) {
     for (auto& v : c->vae) free_all(v.owned);
     for (auto& m : c->mlp) free_all(m.owned);
     for (auto& m : c->cache) free_all(m.owned);
+    for (auto& m : c->prior) free_all(m.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

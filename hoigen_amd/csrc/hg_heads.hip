@@ -171,6 +171,64 @@ int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
     return HG_OK;
 }
 
+// ---- region proposals and instance priors (hg_region_props.hip) ----------------------------------------------------------------------
+int hg_region_priors(hg_ctx* c, const hg_region_priors_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!a) return fail(c, HG_ERR_INVALID, "hg_region_priors: no arguments");
+    if (a->B < 0 || a->B > PROPS_MAX_IMAGES) return fail(c, HG_ERR_INVALID, "hg_region_priors: %d images (at most %d a call)", a->B, PROPS_MAX_IMAGES);
+    if (a->max_instances < 1 || 2 * a->max_instances > PROPS_MAX_CAP || a->min_instances < 0 || a->min_instances > a->max_instances)
+        return fail(c, HG_ERR_INVALID, "hg_region_priors: min_instances = %d, max_instances = %d (0 <= min <= max, 1 <= max, 2 max <= %d rows an image)",
+                    a->min_instances, a->max_instances, PROPS_MAX_CAP);
+    if (a->prior_slot < -1 || a->prior_slot >= HG_MAX_PRIOR_SLOTS)
+        return fail(c, HG_ERR_INVALID, "hg_region_priors: prior slot %d (-1 .. %d)", a->prior_slot, HG_MAX_PRIOR_SLOTS - 1);
+    const bool want_priors = a->prior_slot >= 0;
+    if (want_priors && !c->prior[a->prior_slot].loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_region_priors: prior slot %d not loaded", a->prior_slot);
+    if (a->B == 0) return HG_OK;
+    if (!a->q_off || !a->counts) return fail(c, HG_ERR_INVALID, "hg_region_priors: q_off / counts missing");
+    if (want_priors && (!a->image_sizes || !a->priors || !a->mask)) return fail(c, HG_ERR_INVALID, "hg_region_priors: priors need image_sizes, priors and mask");
+    if (a->table_out && !want_priors) return fail(c, HG_ERR_INVALID, "hg_region_priors: table_out without a prior slot");
+    PropsBatch pb{};
+    pb.B = a->B;
+    if (a->q_off[0] != 0) return fail(c, HG_ERR_INVALID, "hg_region_priors: q_off must start at 0");
+    for (int b = 0; b < a->B; ++b) {
+        const long q = (long)a->q_off[b + 1] - a->q_off[b];
+        if (q < 0 || q > PROPS_MAX_Q) return fail(c, HG_ERR_INVALID, "hg_region_priors: image %d has %ld detections (0 .. %d)", b, q, PROPS_MAX_Q);
+        pb.q_off[b] = a->q_off[b];
+        pb.img_h[b] = a->image_sizes ? a->image_sizes[2 * b] : 1.f;
+        pb.img_w[b] = a->image_sizes ? a->image_sizes[2 * b + 1] : 1.f;
+    }
+    pb.q_off[a->B] = a->q_off[a->B];
+    if (pb.q_off[a->B] > 0 && (!a->scores || !a->labels || !a->boxes)) return fail(c, HG_ERR_INVALID, "hg_region_priors: scores / labels / boxes missing");
+    const int n_out = (a->keep != nullptr) + (a->out_boxes != nullptr) + (a->out_scores != nullptr) + (a->out_labels != nullptr);
+    if (n_out != 0 && n_out != 4) return fail(c, HG_ERR_INVALID, "hg_region_priors: keep, out_boxes, out_scores and out_labels come together or not at all");
+    if (((uintptr_t)a->boxes | (uintptr_t)a->out_boxes) & 15) return fail(c, HG_ERR_INVALID, "hg_region_priors: boxes / out_boxes must be 16-byte aligned");
+    const int cap = 2 * a->max_instances;
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    int32_t *keep = a->keep, *out_labels = a->out_labels;
+    float *out_boxes = a->out_boxes, *out_scores = a->out_scores;
+    if (!n_out) {
+        const size_t slots = (size_t)a->B * cap;
+        int rc = ensure(c, c->props, slots * 7 * 4);
+        if (rc) return rc;
+        out_boxes = (float*)c->props.p;
+        out_scores = out_boxes + 4 * slots;
+        keep = (int32_t*)(out_scores + slots);
+        out_labels = keep + slots;
+    }
+    PropsSelect ps{};
+    ps.score_thr = a->box_score_thresh; ps.nms_thr = a->nms_thresh;
+    ps.human_idx = a->human_idx; ps.min_inst = a->min_instances; ps.max_inst = a->max_instances; ps.cap = cap;
+    ps.n_classes = want_priors ? c->prior[a->prior_slot].n_classes : 0;
+    HG_HIP(launch_props_select(pb, ps, a->scores, a->labels, a->boxes, a->counts, keep, out_boxes, out_scores, out_labels, a->survivors, s));
+    if (!want_priors) return HG_OK;
+    const Priors& m = c->prior[a->prior_slot];
+    PriorDev pw{m.hid, m.w0t, m.b0, m.w1t, m.b1, m.w2t, m.b2, m.T};
+    HG_HIP(launch_prior_mlp(pb, pw, cap, a->counts, out_boxes, out_scores, out_labels, a->priors, a->mask, s));
+    if (a->table_out) HG_HIP(hipMemcpyAsync(a->table_out, m.T, (size_t)m.n_classes * m.hid * 4, hipMemcpyDeviceToDevice, s));
+    return HG_OK;
+}
+
 // ---- CoOp-VAE ---------------------------------------------------------------------------------------------
 static int vae_fused_rows(const hg_ctx* c, int R) { return fused_item_rows(c, c->opt_vae_fused, R); }
 static int generator_rows(hg_ctx* c, Vae& v, const half_t* z16, int R, float* bias, hipStream_t s) {

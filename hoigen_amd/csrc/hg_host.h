@@ -128,6 +128,13 @@ struct Mlp {
     float *b0 = nullptr, *b2 = nullptr, *b4 = nullptr;
     std::vector<void*> owned;
 };
+
+struct Priors {      // priors_downproj + object_embedding (hg_load_priors): fp32, linears as [in][out], and the folded table T
+    bool loaded = false;
+    int E = 0, hid = 0, n_classes = 0;
+    float *w0t = nullptr, *b0 = nullptr, *w1t = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr, *T = nullptr;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -139,6 +146,7 @@ struct hg_ctx {
     Vae vae[HG_MAX_SLOTS];
     Mlp mlp[HG_MAX_SLOTS];
     Cache cache[HG_MAX_CACHE_SLOTS];
+    Priors prior[HG_MAX_PRIOR_SLOTS];
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
@@ -147,6 +155,7 @@ struct hg_ctx {
     Buf xlo;             // low half of the residual stream while it is held as centre + hi + lo (GemmArgs::hl)
     Buf pair_ready;      // hg_mlp_pair.hip: ready counters [blocks][256-row panels], zeroed at the start of every tower pass
     Buf hoi_tab, hoi_pool, hoi_a16, hoi_br;      // hg_hoi_head: RoI table; pooled means; fp16 operand rows HO | U | G; branch logits
+    Buf props;           // hg_region_priors: keep, boxes, scores, labels of the selected instances where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
     int max_chunk_rows = 32768;
@@ -210,7 +219,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br}
+     &(c)->hoi_br, &(c)->props}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

@@ -318,6 +318,41 @@ hipError_t launch_hoi_epilogue(const HoiBatch& hb, const HoiEpilogue& e, const f
                                const uint8_t* obj2target, int n_obj, int NC, float score_pow, float* logits, float* prior,
                                float* out_scores, hipStream_t s);
 
+// ---- region proposals and instance priors (hg_region_props.hip): NMS, selection, prior rows, priors_downproj ------------------------
+static constexpr int PROPS_MAX_IMAGES = 64;     // images per call (PropsBatch travels as a kernel argument)
+static constexpr int PROPS_MAX_Q = 512;         // detections per image at most: scores, labels, boxes and Q bit rows of Q bits stay in LDS
+static constexpr int PROPS_WORDS = PROPS_MAX_Q / 32;
+static constexpr int PROPS_MAX_CAP = 64;        // rows per image = 2 max_instances at most: one lane per output slot
+static constexpr int PROPS_MAX_E = 1024;
+static constexpr int PROPS_MAX_HID = 256;       // one thread per hidden column
+static constexpr int PROPS_OUT = 64;            // the adapters' bottleneck
+static constexpr int PROPS_MAX_CLASSES = 256;
+static constexpr int PRIOR_ROWS = 16;           // rows per workgroup of prior_mlp_kernel
+struct PropsBatch {      // host-built, by value: detections of image b are rows q_off[b] .. q_off[b + 1] - 1
+    int B;
+    int q_off[PROPS_MAX_IMAGES + 1];
+    float img_h[PROPS_MAX_IMAGES], img_w[PROPS_MAX_IMAGES];
+};
+struct PropsSelect {
+    float score_thr, nms_thr;
+    int human_idx, min_inst, max_inst, cap;
+    int n_classes;       // rows of the prior table the labels index (0: proposals only, labels unchecked)
+};
+struct PriorDev {        // fp32, linears as [in][out]: w0t [5 + E][hid], w1t [hid][hid], w2t [hid][64]; T [n_classes][hid]
+    int hid;
+    const float *w0t, *b0, *w1t, *b1, *w2t, *b2, *T;
+};
+// counts [B][4] = n, n_human, status, survivors; keep / out_scores / out_labels [B][cap], out_boxes [B][cap][4] (16-byte aligned, as
+// boxes); survivors (nullable) [q_off[B]]: image b's NMS survivors in order from q_off[b] on
+hipError_t launch_props_select(const PropsBatch& pb, const PropsSelect& ps, const float* scores, const int32_t* labels, const float* boxes,
+                               int32_t* counts, int32_t* keep, float* out_boxes, float* out_scores, int32_t* out_labels,
+                               int32_t* survivors, hipStream_t s);
+hipError_t launch_prior_pack(const float* in, int N, int K, float* out, hipStream_t s);      // [N][K] -> [K][N]
+hipError_t launch_prior_table(const float* emb, const float* w0t, int n_classes, int E, int hid, float* T, hipStream_t s);
+// priors [B][cap][64], mask [B][cap] (1 = pad) from what launch_props_select wrote
+hipError_t launch_prior_mlp(const PropsBatch& pb, const PriorDev& pw, int cap, const int32_t* counts, const float* sel_boxes,
+                            const float* sel_scores, const int32_t* sel_labels, float* priors, uint8_t* mask, hipStream_t s);
+
 // ---- adapter (variant C) --------------------------------------------------------------------
 // tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
 static constexpr int ADAPTER_MAX_L = 224;

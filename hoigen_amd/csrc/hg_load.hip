@@ -651,4 +651,47 @@ int hg_load_cache(hg_ctx* c, int slot, const hg_cache_weights* w) {
     return HG_OK;
 }
 
+// priors_downproj + object_embedding (hg_region_props.hip).  A second call on a loaded slot is the update path: everything is rebuilt,
+// the table T included.
+int hg_load_priors(hg_ctx* c, int slot, const hg_prior_weights* w) {
+    if (!c) return HG_ERR_INVALID;
+    if (!w || slot < 0 || slot >= HG_MAX_PRIOR_SLOTS) return fail(c, HG_ERR_INVALID, "hg_load_priors: slot %d (0 .. %d) / no weights", slot, HG_MAX_PRIOR_SLOTS - 1);
+    if (w->E <= 0 || w->E > PROPS_MAX_E || w->hidden <= 0 || w->hidden > PROPS_MAX_HID || w->out != PROPS_OUT || w->n_obj_classes <= 0 ||
+        w->n_obj_classes > PROPS_MAX_CLASSES)
+        return fail(c, HG_ERR_INVALID, "hg_load_priors: E = %d, hidden = %d, out = %d, %d classes (E <= %d, hidden <= %d, out == %d, classes <= %d)",
+                    w->E, w->hidden, w->out, w->n_obj_classes, PROPS_MAX_E, PROPS_MAX_HID, PROPS_OUT, PROPS_MAX_CLASSES);
+    HG_ON_DEVICE(c);
+    HG_HIP(hipDeviceSynchronize());      // (an update: no call in flight still reads the slot)
+    Priors& m = c->prior[slot];
+    free_all(m.owned);
+    m = Priors{};
+    m.E = w->E; m.hid = w->hidden; m.n_classes = w->n_obj_classes;
+    const int K0 = m.E + 5, hid = m.hid;
+    std::vector<void*> scratch;
+    float *w0 = nullptr, *w1 = nullptr, *w2 = nullptr, *emb = nullptr;
+    int rc = 0;
+    keep_first(rc, as_f32(c, scratch, w->w0, (size_t)hid * K0, &w0, "priors_downproj.layers.0.weight"));
+    keep_first(rc, as_f32(c, scratch, w->w1, (size_t)hid * hid, &w1, "priors_downproj.layers.1.weight"));
+    keep_first(rc, as_f32(c, scratch, w->w2, (size_t)PROPS_OUT * hid, &w2, "priors_downproj.layers.2.weight"));
+    keep_first(rc, as_f32(c, scratch, w->object_embedding, (size_t)m.n_classes * m.E, &emb, "object_embedding"));
+    keep_first(rc, as_f32(c, m.owned, w->b0, hid, &m.b0, "priors_downproj.layers.0.bias"));
+    keep_first(rc, as_f32(c, m.owned, w->b1, hid, &m.b1, "priors_downproj.layers.1.bias"));
+    keep_first(rc, as_f32(c, m.owned, w->b2, PROPS_OUT, &m.b2, "priors_downproj.layers.2.bias"));
+    keep_first(rc, dev_alloc(c, m.owned, (size_t)K0 * hid * 4, (void**)&m.w0t));
+    keep_first(rc, dev_alloc(c, m.owned, (size_t)hid * hid * 4, (void**)&m.w1t));
+    keep_first(rc, dev_alloc(c, m.owned, (size_t)hid * PROPS_OUT * 4, (void**)&m.w2t));
+    keep_first(rc, dev_alloc(c, m.owned, (size_t)m.n_classes * hid * 4, (void**)&m.T));
+    hipError_t e = hipSuccess;
+    if (!rc) e = launch_prior_pack(w0, hid, K0, m.w0t, 0);
+    if (!rc && e == hipSuccess) e = launch_prior_pack(w1, hid, hid, m.w1t, 0);
+    if (!rc && e == hipSuccess) e = launch_prior_pack(w2, PROPS_OUT, hid, m.w2t, 0);
+    if (!rc && e == hipSuccess) e = launch_prior_table(emb, m.w0t, m.n_classes, m.E, hid, m.T, 0);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    free_all(scratch);
+    if (rc) return rc < 0 ? rc : HG_ERR_INVALID;
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_load_priors: %s", hipGetErrorString(e));
+    m.loaded = true;
+    return HG_OK;
+}
+
 }  // extern "C"

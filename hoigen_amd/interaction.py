@@ -9,8 +9,9 @@ Counterpart of ``UPT.compute_roi_embeddings`` + ``compute_prior_scores`` + ``pos
     logits, prior, bh, bo, objects = head(feat_global, feat_local, image_sizes, region_props)
     detections = head.postprocess(boxes, bh, bo, logits, prior, objects, image_sizes)
 
-Out of scope, plain torch in the caller as before: ``get_prior`` / ``priors_downproj``, NMS / ``prepare_region_proposals``, the
-training-time appended features and losses.  Inference only; CPU tensors and gradient callers raise ``RuntimeError`` (there is no
+``region_props`` may be the list ``hoigen_amd.proposals.DetectorFrontEnd`` returned (NMS / ``prepare_region_proposals``, ``get_prior`` /
+``priors_downproj`` in one call of their own): its dicts carry the human counts, and no label leaves the device here.  Out of scope,
+plain torch in the caller as before: the training-time appended features and losses.  Inference only; CPU tensors and gradient callers raise ``RuntimeError`` (there is no
 CPU fallback).
 """
 from typing import List, Optional, Sequence, Tuple
@@ -41,6 +42,19 @@ def plan_batch(labels: Sequence[torch.Tensor], human_idx: int):
         perm.append(p)
         box_off.append(box_off[-1] + n)
         n_human.append(n_h)
+        pair_off.append(pair_off[-1] + (n_h * (n - 1) if n > 1 else 0))
+    return perm, box_off, n_human, pair_off
+
+
+def plan_from_counts(sizes: Sequence[int], n_humans: Sequence[int]):
+    """``plan_batch`` for region proposals that arrive humans first with their human counts on the host - what
+    ``hoigen_amd.proposals.DetectorFrontEnd`` returns (``n_human`` in every dict): the permutation is the identity and no label leaves
+    the device."""
+    perm, box_off, n_human, pair_off = [], [0], [], [0]
+    for n, n_h in zip(sizes, n_humans):
+        perm.append(torch.arange(n))
+        box_off.append(box_off[-1] + n)
+        n_human.append(int(n_h))
         pair_off.append(pair_off[-1] + (n_h * (n - 1) if n > 1 else 0))
     return perm, box_off, n_human, pair_off
 
@@ -117,7 +131,10 @@ class HOIHead:
         # spatial_scale = 1 / (image_size[0, 0] / local_features.shape[1]) in the tensor's own arithmetic (:1027)
         scale = float(1 / (image_sizes[0, 0] / H))
         labels = [p["labels"] for p in region_props]
-        perm, box_off, n_human, pair_off = plan_batch(labels, self.human_idx)
+        if all(isinstance(p.get("n_human"), int) for p in region_props):      # DetectorFrontEnd's: humans first, counts on the host
+            perm, box_off, n_human, pair_off = plan_from_counts([int(lb.numel()) for lb in labels], [p["n_human"] for p in region_props])
+        else:
+            perm, box_off, n_human, pair_off = plan_batch(labels, self.human_idx)
         N, Pt = box_off[-1], pair_off[-1]
         label_dtype = labels[0].dtype if labels else torch.int64
         order = torch.cat([p + o for p, o in zip(perm, box_off)]).to(dev) if N else torch.zeros(0, dtype=torch.int64, device=dev)

@@ -271,6 +271,68 @@ typedef struct {
 } hg_hoi_head_args;
 int hg_hoi_head(hg_ctx*, const hg_hoi_head_args* args, void* stream);
 
+/* Region proposals and instance priors for a batch of images in one call: what UPT.forward does between DETR's PostProcess and the
+ * encoders (upt_tip_cache_model_free_finetune_distill3.py:1543-1660).
+ *
+ * hg_load_priors: priors_downproj = MLP(E + 5, hidden, 64, 3) (:40-52, :520; state-dict keys layers.{0,1,2}.{weight,bias}) and
+ * object_embedding [n_obj_classes, E] (:1464) for prior_type 'cbe', prior_method 0 (:468-469).  The label-dependent part of the first
+ * layer is folded into a table here: T[c][n] = sum_k object_embedding[c][k] * w0[n][5 + k] (fp32, k ascending, one accumulator, multiply
+ * and add rounded separately).  Calling it again on a loaded slot is the update path (priors_downproj is trainable during adapter
+ * fine-tuning); the next hg_region_priors sees the new weights.  Synchronous.
+ * Limits: E <= 1024, hidden <= 256, out == 64, n_obj_classes <= 256. */
+#define HG_MAX_PRIOR_SLOTS 4
+typedef struct {
+    int32_t E, hidden, out, n_obj_classes;
+    hg_tensor w0, b0; /* [hidden, E + 5], [hidden] */
+    hg_tensor w1, b1; /* [hidden, hidden], [hidden] */
+    hg_tensor w2, b2; /* [out, hidden], [out] */
+    hg_tensor object_embedding; /* [n_obj_classes, E] */
+} hg_prior_weights;
+int hg_load_priors(hg_ctx*, int slot, const hg_prior_weights* w);
+/* hg_region_priors: prepare_region_proposals (:1361-1406), get_prior (:1445-1495) and priors_downproj (:1492) of B images.
+ * Input: what DETR's PostProcess returns (detr/models/detr.py:258-290), concatenated: scores [Qt], labels int32 [Qt], boxes [Qt, 4]
+ * (x1, y1, x2, y2 in pixels; 16-byte aligned), image b = rows q_off[b] .. q_off[b + 1] - 1.
+ *   class-aware NMS   torchvision.ops.boxes._batched_nms_coordinate_trick (the path batched_nms takes below 4 000 boxes), restated in
+ *       fp32, one rounding per operation: off = (float)label * (max coordinate of the image + 1.0f), every coordinate + off, a STABLE
+ *       order by descending score (ties to the lower input index - the reference's argsort leaves them open), greedy suppression where
+ *       inter / ((area_i + area_j) - inter) > nms_thresh, inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0),
+ *       area = (x2 - x1) * (y2 - y1) on the offset boxes.  0 / 0 is not > nms_thresh: the box stays.                         (:1367)
+ *   selection         over the survivors in order: h = humans (label == human_idx) with score >= box_score_thresh; h < min_instances
+ *       takes the first min_instances humans of ALL survivors (or as many as there are), h > max_instances the first max_instances,
+ *       otherwise those h; the other labels likewise; output = humans, then the others, each by descending score         (:1371-1398)
+ *   priors            row = (score, x1 / w, y1 / h, x2 / w, y2 / h, object_embedding[label]) with (h, w) = image_sizes[b], a division;
+ *       three linears, ReLU behind the first two; rows n_b .. cap - 1 hold the MLP of a zero row, as the reference's padded tensor
+ *       does; mask = 1 there                                                                                              (:1445-1495)
+ * Output, cap = 2 * max_instances slots per image:
+ *   counts      int32 [B, 4] = n, n_human, status, number of NMS survivors
+ *   keep        int32 [B, cap]   indices into the image's input list (-1 behind n)
+ *   out_boxes [B, cap, 4] (16-byte aligned), out_scores [B, cap], out_labels int32 [B, cap]   (0, 0, -1 behind n)
+ *   survivors   int32 [Qt], nullable: image b's NMS survivors in order, from q_off[b] on (counts[b][3] of them; the rest is not written)
+ *   priors      [B, cap, 64], mask uint8 [B, cap]        (prior_slot >= 0)
+ *   table_out   [n_obj_classes, hidden], nullable: the slot's table T
+ * keep, out_boxes, out_scores and out_labels may be NULL together (the library's workspace holds them).  prior_slot = -1: proposals only.
+ * status: bit 0 = the image has a non-finite score or coordinate, bit 1 = a label outside [0, n_obj_classes) (prior_slot >= 0 only);
+ * such an image gets n = 0 and pad rows; the other images of the batch are not affected.
+ * q_off [B + 1] and image_sizes [B, 2] = (h, w) as floats: HOST.  Limits: B <= 64, q_off[b + 1] - q_off[b] <= 512,
+ * 0 <= min_instances <= max_instances, 1 <= max_instances <= 32.  No host synchronisation, no allocation in steady state. */
+typedef struct {
+    const float* scores;
+    const int32_t* labels;
+    const float* boxes;
+    const int32_t* q_off;
+    const float* image_sizes;
+    int32_t B;
+    float box_score_thresh, nms_thresh;
+    int32_t human_idx, min_instances, max_instances, prior_slot;
+    int32_t *counts, *keep;
+    float *out_boxes, *out_scores;
+    int32_t *out_labels, *survivors;
+    float* priors;
+    uint8_t* mask;
+    float* table_out;
+} hg_region_priors_args;
+int hg_region_priors(hg_ctx*, const hg_region_priors_args* args, void* stream);
+
 /* Crop pre-processing in front of encode_image: for every box of one image
  *   image.crop(box)                       pre_images/crop_images.py:204-219 (PIL: zeros outside the image)
  *   [expand2square(crop, background)]     utils_tip_cache_and_union_finetune.py:201-212  (pad_square != 0)
