@@ -119,6 +119,17 @@ class hg_region_priors_args(C.Structure):
                                           "table_out")]
 
 
+class hg_hoi_detections_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("prior", "scores", "pair_h", "pair_o", "objects", "boxes")] + \
+               [("pair_off", C.POINTER(C.c_int32)), ("box_off", C.POINTER(C.c_int32)), ("B", C.c_int32), ("num_classes", C.c_int32),
+                ("conversion", C.c_void_p), ("n_obj_classes", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("gt_boxes_h", "gt_boxes_o", "gt_hoi")] + \
+               [("gt_off", C.POINTER(C.c_int32)), ("gt_sizes", C.POINTER(C.c_int32)), ("gt_format", C.c_int32), ("min_iou", C.c_float),
+                ("cap", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("det_off", "det_pair", "det_verb", "det_h", "det_o", "det_object", "det_score", "det_interaction",
+                                          "det_label", "det_gt", "det_max_iou", "gt_boxes_out", "status")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -170,6 +181,7 @@ SIGNATURES = {
     "hg_hoi_head": (_I, [_P, C.POINTER(hg_hoi_head_args), _P]),
     "hg_load_priors": (_I, [_P, _I, C.POINTER(hg_prior_weights)]),
     "hg_region_priors": (_I, [_P, C.POINTER(hg_region_priors_args), _P]),
+    "hg_hoi_detections": (_I, [_P, C.POINTER(hg_hoi_detections_args), _P]),
     "hg_preprocess_crops": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),

@@ -229,6 +229,73 @@ int hg_region_priors(hg_ctx* c, const hg_region_priors_args* a, void* stream) {
     return HG_OK;
 }
 
+// ---- detections and ground-truth matching (hg_detections.hip) -------------------------------------------------------------------------
+int hg_hoi_detections(hg_ctx* c, const hg_hoi_detections_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!a) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: no arguments");
+    if (a->B < 0 || a->B > DET_MAX_IMAGES) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: %d images (at most %d a call)", a->B, DET_MAX_IMAGES);
+    if (a->num_classes <= 0 || a->num_classes > DET_MAX_NC)
+        return fail(c, HG_ERR_INVALID, "hg_hoi_detections: num_classes = %d (1 .. %d)", a->num_classes, DET_MAX_NC);
+    if (a->cap < 0) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: cap = %d", a->cap);
+    if (!a->det_off) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: det_off missing");
+    if (!a->pair_off || !a->box_off) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: pair_off / box_off missing");
+    const bool assoc = a->gt_off != nullptr;
+    if (assoc && !a->gt_sizes && a->gt_format == 1) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: gt_format 1 needs gt_sizes");
+    if (assoc && a->gt_format != 0 && a->gt_format != 1) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: gt_format = %d (0 or 1)", a->gt_format);
+    if (a->conversion && a->n_obj_classes <= 0) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: conversion without n_obj_classes");
+    DetBatch db{};
+    db.B = a->B;
+    if (a->pair_off[0] != 0 || a->box_off[0] != 0 || (assoc && a->gt_off[0] != 0))
+        return fail(c, HG_ERR_INVALID, "hg_hoi_detections: pair_off, box_off and gt_off must start at 0");
+    for (int b = 0; b < a->B; ++b) {
+        const long np = (long)a->pair_off[b + 1] - a->pair_off[b], nb = (long)a->box_off[b + 1] - a->box_off[b];
+        const long ng = assoc ? (long)a->gt_off[b + 1] - a->gt_off[b] : 0;
+        if (np < 0 || nb < 0) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: pair_off / box_off decrease at image %d", b);
+        if (ng < 0 || ng > DET_MAX_GT) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: image %d has %ld ground-truth pairs (0 .. %d)", b, ng, DET_MAX_GT);
+        if (a->pair_off[b + 1] > (1 << 24)) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: more than 2^24 pairs");
+        db.pair_off[b + 1] = a->pair_off[b + 1];
+        db.box_off[b + 1] = a->box_off[b + 1];
+        db.gt_off[b + 1] = assoc ? a->gt_off[b + 1] : 0;
+        db.img_h[b] = a->gt_sizes ? a->gt_sizes[2 * b] : 1;
+        db.img_w[b] = a->gt_sizes ? a->gt_sizes[2 * b + 1] : 1;
+    }
+    const int B = a->B, Pt = db.Pt = db.pair_off[B], NC = a->num_classes, Gt = db.gt_off[B], cap = a->cap;
+    if ((long)Pt * NC > 0x7FFFFFFFl) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: %d pairs x %d classes do not fit a 32-bit count", Pt, NC);
+    if (Pt > 0 && (!a->prior || !a->pair_h || !a->pair_o || !a->objects))
+        return fail(c, HG_ERR_INVALID, "hg_hoi_detections: prior / pair_h / pair_o / objects missing");
+    if (Pt > 0 && cap > 0 && a->det_score && !a->scores) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: det_score needs scores");
+    if (assoc && Pt > 0 && cap > 0 && (!a->scores || !a->boxes)) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: the association needs scores and boxes");
+    if (assoc && Gt > 0 && (!a->gt_boxes_h || !a->gt_boxes_o || !a->gt_hoi)) return fail(c, HG_ERR_INVALID, "hg_hoi_detections: gt_boxes_h / gt_boxes_o / gt_hoi missing");
+    if (!assoc && (a->det_label || a->det_gt || a->det_max_iou || a->gt_boxes_out))
+        return fail(c, HG_ERR_INVALID, "hg_hoi_detections: det_label / det_gt / det_max_iou / gt_boxes_out need ground truth (gt_off)");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    if (B == 0) return HG_OK;
+    // workspace: cnt [Pt], bsum [nblk], and one [cap] array for each entry array the association reads that the caller left out
+    const size_t nblk = ((size_t)Pt + DET_ROWS - 1) / DET_ROWS;
+    DetEntries e{a->det_pair, a->det_verb, a->det_h, a->det_o, a->det_object, a->det_score, a->det_interaction};
+    int32_t* det_gt = a->det_gt;
+    const int n_sub = assoc ? (!e.h) + (!e.o) + (!e.score) + (!e.interaction) + (!det_gt) : 0;
+    int rc = ensure(c, c->det, ((size_t)Pt + nblk + (size_t)n_sub * cap + 1) * 4);
+    if (rc) return rc;
+    int32_t* cnt = (int32_t*)c->det.p;
+    int32_t* bsum = cnt + Pt;
+    int32_t* sub = bsum + nblk;
+    if (assoc) {
+        if (!e.h) { e.h = sub; sub += cap; }
+        if (!e.o) { e.o = sub; sub += cap; }
+        if (!e.score) { e.score = (float*)sub; sub += cap; }
+        if (!e.interaction) { e.interaction = sub; sub += cap; }
+        if (!det_gt) { det_gt = sub; sub += cap; }
+    }
+    HG_HIP(launch_det_compact(db, a->prior, a->scores, a->pair_h, a->pair_o, a->objects, a->conversion, a->n_obj_classes, NC, cap, cnt, bsum,
+                              a->det_off, e, a->status, s));
+    if (assoc)
+        HG_HIP(launch_det_assoc(db, a->boxes, a->gt_boxes_h, a->gt_boxes_o, a->gt_hoi, a->gt_format, a->min_iou, cap, Gt, a->det_off, e, a->det_label,
+                                det_gt, a->det_max_iou, a->gt_boxes_out, a->status, s));
+    return HG_OK;
+}
+
 // ---- CoOp-VAE ---------------------------------------------------------------------------------------------
 static int vae_fused_rows(const hg_ctx* c, int R) { return fused_item_rows(c, c->opt_vae_fused, R); }
 static int generator_rows(hg_ctx* c, Vae& v, const half_t* z16, int R, float* bias, hipStream_t s) {

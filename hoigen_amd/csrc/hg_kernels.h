@@ -353,6 +353,30 @@ hipError_t launch_prior_table(const float* emb, const float* w0t, int n_classes,
 hipError_t launch_prior_mlp(const PropsBatch& pb, const PriorDev& pw, int cap, const int32_t* counts, const float* sel_boxes,
                             const float* sel_scores, const int32_t* sel_labels, float* priors, uint8_t* mask, hipStream_t s);
 
+// ---- detections and their association with the ground truth (hg_detections.hip) ---------------------------------------------------------
+static constexpr int DET_MAX_IMAGES = 64;       // images per call (DetBatch travels as a kernel argument)
+static constexpr int DET_MAX_NC = 1024;
+static constexpr int DET_MAX_GT = 256;          // ground-truth pairs per image: one thread each, boxes, classes and keys in LDS
+static constexpr int DET_ROWS = 64;             // pair rows per workgroup of det_count_kernel / det_write_kernel: one wave scans their counts
+struct DetBatch {      // host-built, by value: pairs, boxes and ground-truth pairs of image b are rows x_off[b] .. x_off[b + 1] - 1
+    int B, Pt;
+    int pair_off[DET_MAX_IMAGES + 1], box_off[DET_MAX_IMAGES + 1], gt_off[DET_MAX_IMAGES + 1];
+    int img_h[DET_MAX_IMAGES], img_w[DET_MAX_IMAGES];
+};
+struct DetEntries {    // one word per detection each, [cap]; each nullable for det_write_kernel
+    int32_t *pair, *verb, *h, *o, *object;
+    float* score;
+    int32_t* interaction;
+};
+// cnt [Pt] and bsum [ceil(Pt / DET_ROWS)]: workspace.  det_off [B + 1]; status [B] nullable.  Nothing is written at or beyond slot cap.
+hipError_t launch_det_compact(const DetBatch& db, const float* prior, const float* scores, const int32_t* pair_h, const int32_t* pair_o,
+                              const int32_t* objects, const int32_t* conversion, int n_obj, int NC, int cap, int32_t* cnt, int32_t* bsum,
+                              int32_t* det_off, const DetEntries& e, int32_t* status, hipStream_t s);
+// needs e.h, e.o, e.score, e.interaction and det_gt; det_label, det_max_iou, gt_out [2][Gt][4] and status nullable
+hipError_t launch_det_assoc(const DetBatch& db, const float* boxes, const float* gt_h, const float* gt_o, const int32_t* gt_hoi, int gt_format,
+                            float min_iou, int cap, int Gt, const int32_t* det_off, const DetEntries& e, float* det_label, int32_t* det_gt,
+                            float* det_max_iou, float* gt_out, int32_t* status, hipStream_t s);
+
 // ---- adapter (variant C) --------------------------------------------------------------------
 // tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
 static constexpr int ADAPTER_MAX_L = 224;

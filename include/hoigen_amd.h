@@ -333,6 +333,63 @@ typedef struct {
 } hg_region_priors_args;
 int hg_region_priors(hg_ctx*, const hg_region_priors_args* args, void* stream);
 
+/* hg_hoi_detections: what follows hg_hoi_head, for the B images of that call - the detections of UPT.postprocessing
+ * (upt_tip_cache_model_free_finetune_distill3.py:1408-1427) compacted on the device, and, with ground truth, test_hico's per-image body
+ * (utils_tip_cache_and_union_finetune.py:376-409): conversion[objects, verbs] (:385-388), recover_boxes (upt...:1269-1274,
+ * detr/util/box_ops.py:9-13), the `for hoi_idx in unique_hoi` loop (:394-407) with BoxPairAssociation(min_iou)
+ * (pocket/pocket/utils/association.py:17-116) for all classes of an image at once.
+ * Input: hg_hoi_head's prior [2, Pt, NC], scores_out [Pt, NC], pair_h / pair_o / objects [Pt] and the batch's boxes [N, 4]: device.
+ * pair_off [B + 1], box_off [B + 1]: HOST.  conversion int32 [n_obj_classes, NC], device, nullable: object_n_verb_to_interaction with -1
+ * where the reference has None; NULL = the interaction is the verb (num_classes 600).
+ *   detections   every (p, c) with prior[0][p][c] * prior[1][p][c] != 0 - ONE fp32 multiply, a NaN counts, as torch.nonzero has it - in
+ *       row-major order (:1418).  Image b's entries are the slots det_off[b] .. det_off[b + 1] - 1:
+ *       det_pair = p - pair_off[b], det_verb = c, det_h / det_o = pair_h[p] / pair_o[p], det_object = objects[p],
+ *       det_score = the word scores[p][c], det_interaction = conversion[objects[p]][c] or c.  Nothing is written at or beyond slot cap;
+ *       det_off always holds the true counts.
+ *   ground truth (gt_off != NULL): gt_boxes_h, gt_boxes_o [Gt, 4], gt_hoi int32 [Gt]: device; gt_off [B + 1], gt_sizes int32 [B, 2] =
+ *       (h, w): HOST.  gt_format 0 = x1, y1, x2, y2 in pixels, taken as they are; 1 = normalised cx, cy, w, h recovered as
+ *       ((cx - 0.5f w) (float)w_img, (cy - 0.5f h) (float)h_img, (cx + 0.5f w) (float)w_img, (cy + 0.5f h) (float)h_img), one rounding per
+ *       operation.  gt_boxes_out [2, Gt, 4] = the recovered boxes, human then object.
+ *   association  for detection d and every ground-truth pair g of its image with gt_hoi[g] == det_interaction[d] (>= 0):
+ *       iou = min(iou_h, iou_o), each torchvision's box_iou in fp32, one rounding per operation: area = (x2 - x1) * (y2 - y1),
+ *       inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0), iou = inter / ((area_g + area_d) - inter); minimum, maximum and the
+ *       clamp hand a NaN on as torch's do.  det_max_iou / det_gt = iou.max(0): the first index of the maximum, relative to the image; a NaN
+ *       makes the maximum NaN (written as 0x7FC00000) from its first index on.  No ground truth of the class (or interaction -1, or a
+ *       pair index outside the image's boxes): det_gt = -1, det_max_iou = 0.  d is a candidate of det_gt[d] alone, and only if
+ *       det_max_iou > min_iou (strict; NaN is not greater).  Per ground-truth pair the candidate with the highest score gets det_label 1
+ *       (a NaN score ranks above every number, -0 == +0, ties go to the lowest detection index, as argmax has it), every other
+ *       detection 0.
+ *   status       int32 [B]: bit 0 = an entry whose conversion is negative or whose object lies outside the table (its interaction is -1 and
+ *       its label 0), bit 1 = a non-finite recovered ground-truth box, bit 2 = the image's entries end behind slot cap.
+ * The results do not depend on the batch around an image or on the order in which workgroups run: slots come from a prefix sum, the winner
+ * of a ground-truth pair from the maximum of distinct keys.  Every output but det_off [B + 1] may be NULL; det_label, det_gt, det_max_iou and
+ * gt_boxes_out need gt_off and stay untouched without it.  Limits (HG_ERR_INVALID otherwise): B <= 64, 1 <= num_classes <= 1024, at most
+ * 256 ground-truth pairs an image, at most 2^24 pairs, pairs x num_classes < 2^31, cap >= 0.  No host synchronisation, no allocation in
+ * steady state, asynchronous on `stream`. */
+typedef struct {
+    const float *prior, *scores;
+    const int32_t *pair_h, *pair_o, *objects;
+    const float* boxes;
+    const int32_t *pair_off, *box_off; /* HOST */
+    int32_t B, num_classes;
+    const int32_t* conversion;
+    int32_t n_obj_classes;
+    const float *gt_boxes_h, *gt_boxes_o;
+    const int32_t* gt_hoi;
+    const int32_t *gt_off, *gt_sizes; /* HOST */
+    int32_t gt_format;
+    float min_iou;
+    int32_t cap;
+    int32_t *det_off, *det_pair, *det_verb, *det_h, *det_o, *det_object;
+    float* det_score;
+    int32_t* det_interaction;
+    float* det_label;
+    int32_t* det_gt;
+    float *det_max_iou, *gt_boxes_out;
+    int32_t* status;
+} hg_hoi_detections_args;
+int hg_hoi_detections(hg_ctx*, const hg_hoi_detections_args* args, void* stream);
+
 /* Crop pre-processing in front of encode_image: for every box of one image
  *   image.crop(box)                       pre_images/crop_images.py:204-219 (PIL: zeros outside the image)
  *   [expand2square(crop, background)]     utils_tip_cache_and_union_finetune.py:201-212  (pad_square != 0)
