@@ -130,6 +130,15 @@ class hg_hoi_detections_args(C.Structure):
                                           "det_label", "det_gt", "det_max_iou", "gt_boxes_out", "status")]
 
 
+HG_PRE_MAX_IMAGES, HG_PRE_MAX_N, HG_PRE_MAX_NPX, HG_PRE_MAX_TAPS = 64, 4096, 518, 65      # limits of one hg_preprocess_batch call
+
+
+class hg_preprocess_batch_args(C.Structure):
+    _fields_ = [("images", C.POINTER(C.c_void_p)), ("heights", C.POINTER(C.c_int32)), ("widths", C.POINTER(C.c_int32)), ("B", C.c_int32),
+                ("boxes", C.c_void_p), ("crop_image", C.c_void_p), ("n", C.c_int32), ("n_px", C.c_int32), ("flags", C.c_int32),
+                ("background", C.c_uint32), ("out", C.c_void_p), ("out_u8", C.c_void_p), ("status", C.c_void_p)]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -183,6 +192,7 @@ SIGNATURES = {
     "hg_region_priors": (_I, [_P, C.POINTER(hg_region_priors_args), _P]),
     "hg_hoi_detections": (_I, [_P, C.POINTER(hg_hoi_detections_args), _P]),
     "hg_preprocess_crops": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P]),
+    "hg_preprocess_batch": (_I, [_P, C.POINTER(hg_preprocess_batch_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),

@@ -4,6 +4,7 @@
 #include <limits.h>
 
 #include "hg_host.h"
+#include "hg_preproc_geom.h"
 
 namespace {
 
@@ -184,6 +185,33 @@ int hg_preprocess_crops(hg_ctx* c, const uint8_t* img, int H, int W, const int32
     HG_HIP(hipStreamSynchronize(s));      // `head` is a stack-lifetime host buffer
     HG_HIP(launch_preprocess(img, H, W, head_d, tab, tab_off, n, n_px, max_rows, (uint8_t*)c->pre.p, out, out_u8, s,
                              (pad_square & HG_PRE_IMAGENET_NORM) != 0));
+    return HG_OK;
+}
+
+int hg_preprocess_batch(hg_ctx* c, const hg_preprocess_batch_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!a) return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: null arguments");
+    if (a->n == 0) return HG_OK;
+    if (a->B < 1 || a->B > PREB_MAX_IMAGES) return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: B must be 1 .. %d (got %d)", PREB_MAX_IMAGES, a->B);
+    if (a->n < 0 || a->n > PREB_MAX_N) return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: n must be 0 .. %d (got %d)", PREB_MAX_N, a->n);
+    if (a->n_px < 1 || a->n_px > PREB_MAX_NPX) return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: n_px must be 1 .. %d (got %d)", PREB_MAX_NPX, a->n_px);
+    if (!a->images || !a->heights || !a->widths || !a->boxes || !a->crop_image || !a->out || !a->status)
+        return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: null pointer among images, heights, widths, boxes, crop_image, out, status");
+    PreBatch pb = {};
+    pb.B = a->B;
+    for (int b = 0; b < a->B; ++b) {
+        if (!a->images[b] || a->heights[b] <= 0 || a->widths[b] <= 0)
+            return fail(c, HG_ERR_INVALID, "hg_preprocess_batch: image %d is null or has a side <= 0", b);
+        pb.img[b] = a->images[b]; pb.H[b] = a->heights[b]; pb.W[b] = a->widths[b];
+    }
+    HG_ON_DEVICE(c);
+    // headers [n][24] | tables [n][2][n_px * 67]: from n, n_px and the tap limit alone (the boxes never reach the host)
+    const size_t head_words = (size_t)a->n * PREB_HDR;
+    int rc = ensure(c, c->prebatch, (head_words + (size_t)a->n * 2 * preb_axis_words(a->n_px)) * 4);
+    if (rc) return rc;
+    int32_t* head = (int32_t*)c->prebatch.p;
+    HG_HIP(launch_preprocess_batch(pb, a->boxes, a->crop_image, a->n, a->n_px, a->flags, a->background, head, head + head_words, a->out,
+                                   a->out_u8, a->status, (hipStream_t)stream));
     return HG_OK;
 }
 

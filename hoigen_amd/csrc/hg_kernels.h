@@ -282,6 +282,17 @@ hipError_t launch_preprocess(const uint8_t* img, int H, int W, const int32_t* he
                              const int32_t* tab_off, int n, int n_px, int max_rows, uint8_t* tmp, float* out,
                              uint8_t* out_u8, hipStream_t s, bool imagenet_norm = false);
 
+// ---- crop pre-processing of a batch of images (hg_preproc_batch.hip; limits and layouts: hg_preproc_geom.h): boxes [n][4] and
+// crop_image [n] are DEVICE arrays; head [n][24] and tab [n][2][n_px * 67] are workspace sized from n and n_px alone; status [n]
+struct PreBatch {      // host-built, by value: the image table
+    const uint8_t* img[64];
+    int H[64], W[64];
+    int B;
+};
+hipError_t launch_preprocess_batch(const PreBatch& pb, const int32_t* boxes, const int32_t* crop_image, int n, int n_px, int flags,
+                                   uint32_t background, int32_t* head, int32_t* tab, float* out, uint8_t* out_u8, int32_t* status,
+                                   hipStream_t s);
+
 // RoI-align (torchvision semantics, aligned=True, sampling_ratio=-1) of feat [C,H,W] for boxes [n,4] (device):
 // out_pooled [n,C,P,P] and/or out_mean [n,C] (= .flatten(2).mean(-1)); either may be null
 hipError_t launch_roi_align(const float* feat, int C, int H, int W, const float* boxes, int n, float spatial_scale,

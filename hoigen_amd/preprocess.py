@@ -10,6 +10,11 @@ for all boxes of one image in three kernel launches (``hg_preprocess_crops``), p
 fixed-point weight tables (IEEE double, the formulas of Pillow's ``precompute_coeffs`` /
 ``normalize_coeffs_8bpc``) and two kernels do the integer accumulation.  There is no CPU fallback: CPU tensors
 raise ``RuntimeError``.
+
+``CropPreprocessor.batch`` does the same for the crops of a batch of images in one call (``hg_preprocess_batch``, two launches): the
+boxes stay in device memory, the geometry is worked out per crop on the device and the intermediate of the separable resize stays in
+LDS, so the host neither waits nor copies anything back.  With ``stretch=True, imagenet_norm=True`` and no boxes it is the detector's
+CLIP view of every image of a batch (utils_tip_cache_and_union_finetune.py:105-114).
 """
 from typing import Sequence
 
@@ -62,3 +67,103 @@ class CropPreprocessor:
                                                     torch.cuda.current_stream().cuda_stream)
             _lib.check(idx, rc, "hg_preprocess_crops")
         return (out, u8) if return_u8 else out
+
+    STATUS_REASONS = ((1, "empty crop box"), (2, "more than 65 resampling taps on an axis (a downscale above 16), or a box coordinate "
+                                                 "outside +-2**20"), (4, "image index outside the call"))
+
+    def batch(self, images, boxes=None, return_u8: bool = False, check: bool = True, out=None):
+        """The crops of a batch of images in one call (``hg_preprocess_batch``): ``images`` a list of uint8 [H, W, 3] device tensors of
+        any sizes, ``boxes`` a list with one [n_b, 4] integer array or tensor (host or device) per image, or ``None`` for the whole
+        image, one crop each (with ``stretch=True, imagenet_norm=True`` the detector's CLIP view of the batch).  Returns
+        float32 [sum n_b, 3, n_px, n_px] in image order (``return_u8``: and the uint8 crops).  Nothing is copied back from the device
+        unless ``check``: then the per-crop status is read in one copy and a refused crop raises ``ValueError``; with ``check=False`` the
+        int32 status tensor is returned as the last element (0: done; bit 0 empty box, bit 1 tap limit, bit 2 image index) and a refused
+        crop is NaN / 0.  Every crop has the bits of the per-image call.  ``out``: the tensors to write into instead of new ones, a tuple
+        ``(planes float32 [n, 3, n_px, n_px], crops uint8 [n, n_px, n_px, 3] or None, status int32 [n])``, contiguous, on the images' device
+        (views of larger buffers are fine); they are what is returned."""
+        images = list(images)
+        for im in images:
+            if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                raise TypeError("every image must be a uint8 tensor [H, W, 3]")
+            if im.device.type != "cuda":
+                raise RuntimeError("hoigen_amd: crop pre-processing runs only on a HIP device (there is no CPU fallback)")
+        if boxes is None:
+            boxes = [np.array([[0, 0, im.shape[1], im.shape[0]]], np.int32) for im in images]
+        boxes = list(boxes)
+        if len(boxes) != len(images):
+            raise ValueError("one box array per image")
+        if not images:
+            raise ValueError("no images")
+        dev = images[0].device
+        if any(im.device != dev for im in images):
+            raise RuntimeError("hoigen_amd: the images of one batch must live on one device")
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        npx = self.n_px
+        counts, parts = [], []
+        for b in boxes:
+            if isinstance(b, torch.Tensor):
+                b = b.reshape(-1, 4)
+                if b.is_floating_point():
+                    raise TypeError("boxes must be integers (records.pil_box rounds as PIL does)")
+                b = b.to(device=dev, dtype=torch.int32)      # a host tensor is uploaded; a device tensor stays where it is
+            else:
+                b = np.ascontiguousarray(np.asarray(b).reshape(-1, 4))
+                if b.size and b.dtype.kind not in "iu":
+                    raise TypeError("boxes must be integers (records.pil_box rounds as PIL does)")
+                b = b.astype(np.int32)
+            counts.append(int(b.shape[0]))
+            parts.append(b)
+        n = sum(counts)
+        if out is None:
+            out = torch.empty(n, 3, npx, npx, dtype=torch.float32, device=dev)
+            u8 = torch.empty(n, npx, npx, 3, dtype=torch.uint8, device=dev) if return_u8 else None
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+        else:
+            out, u8, status = out
+            want = [(out, torch.float32, (n, 3, npx, npx)), (status, torch.int32, (n,))] + ([(u8, torch.uint8, (n, npx, npx, 3))] if return_u8 else [])
+            for t, dtype, shape in want:
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} is needed")
+        crop_of = np.repeat(np.arange(len(images)), counts)            # image of every crop
+        if n:
+            host = [p for p in parts if not isinstance(p, torch.Tensor)]
+            if len(host) == len(parts):      # one upload for the whole batch
+                bx = torch.from_numpy(np.concatenate(parts, axis=0)).to(dev)
+            else:
+                bx = torch.cat([p if isinstance(p, torch.Tensor) else torch.from_numpy(p).to(dev) for p in parts], dim=0).contiguous()
+            bg = (int(self.background[0]) & 255) | ((int(self.background[1]) & 255) << 8) | ((int(self.background[2]) & 255) << 16)
+            keep = [im.contiguous() for im in images]
+            start = np.concatenate([[0], np.cumsum(counts)])
+            lib, handle = _lib.lib(), _lib.ctx(idx)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream().cuda_stream
+                # calls of at most 64 images and 4096 crops, each writing its slice of the one output
+                i0 = 0
+                while i0 < len(keep):
+                    i1 = i0 + 1
+                    while i1 < len(keep) and i1 - i0 < _lib.HG_PRE_MAX_IMAGES and start[i1 + 1] - start[i0] <= _lib.HG_PRE_MAX_N:
+                        i1 += 1
+                    B = i1 - i0
+                    ptrs = (_lib.C.c_void_p * B)(*[im.data_ptr() for im in keep[i0:i1]])
+                    hs = (_lib.C.c_int32 * B)(*[im.shape[0] for im in keep[i0:i1]])
+                    ws = (_lib.C.c_int32 * B)(*[im.shape[1] for im in keep[i0:i1]])
+                    local = torch.from_numpy((crop_of[start[i0]:start[i1]] - i0).astype(np.int32)).to(dev)
+                    for c0 in range(int(start[i0]), int(start[i1]), _lib.HG_PRE_MAX_N):      # (one image with more than 4096 boxes)
+                        c1 = min(c0 + _lib.HG_PRE_MAX_N, int(start[i1]))
+                        a = _lib.hg_preprocess_batch_args(
+                            ptrs, hs, ws, B, bx[c0:c1].data_ptr(), local[c0 - int(start[i0]):].data_ptr(), c1 - c0, npx, self.flags, bg,
+                            out[c0:c1].data_ptr(), u8[c0:c1].data_ptr() if return_u8 else None, status[c0:c1].data_ptr())
+                        _lib.check(idx, lib.hg_preprocess_batch(handle, _lib.C.byref(a), stream), "hg_preprocess_batch")
+                    i0 = i1
+            if check:
+                st = status.cpu().numpy()
+                bad = np.nonzero(st)[0]
+                if bad.size:
+                    i = int(bad[0])
+                    why = "; ".join(r for bit, r in self.STATUS_REASONS if st[i] & bit)
+                    raise ValueError(f"{why}: crop {i} (box {i - int(start[crop_of[i]])} of image {int(crop_of[i])}); "
+                                     f"{bad.size} of {n} crops refused")
+        res = (out, u8) if return_u8 else (out,)
+        if not check:
+            res = res + (status,)
+        return res[0] if len(res) == 1 else res

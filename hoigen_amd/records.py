@@ -12,7 +12,7 @@ ONE batch of 3n crops; features are returned un-normalised (the consumer divides
 BASELINE.json config 5 ("pre-extracted-feature regeneration") is this loop over a dataset with the batch sharded
 over the GPUs (hoigen_amd.distributed).
 """
-from typing import Dict
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -30,6 +30,69 @@ def pil_box(boxes: np.ndarray) -> np.ndarray:
     """Float boxes -> the integer box PIL's ``image.crop`` uses: each coordinate rounded to the nearest integer
     (ImageCrop: ``int(round(x))``)."""
     return np.rint(np.asarray(boxes, np.float64)).astype(np.int32)
+
+
+def plan_record_batches(pair_counts: Sequence[int], max_crops: int = 256, max_images: int = 64) -> List[Tuple[int, int]]:
+    """Cut images 0 .. len(pair_counts) - 1, in order, into groups [first, last) of at most ``max_images`` images and at most
+    ``max_crops`` crops (an image of n pairs has 3 n crops).  An image's crops are never split: an image that alone exceeds
+    ``max_crops`` forms a group of its own.  Pure host."""
+    if max_crops < 1 or max_images < 1:
+        raise ValueError("max_crops and max_images must be >= 1")
+    groups, first, crops = [], 0, 0
+    for i, n in enumerate(pair_counts):
+        if n < 0:
+            raise ValueError("negative pair count")
+        if i > first and (i - first >= max_images or crops + 3 * n > max_crops):
+            groups.append((first, i))
+            first, crops = i, 0
+        crops += 3 * n
+    if len(pair_counts) > first:
+        groups.append((first, len(pair_counts)))
+    return groups
+
+
+@torch.no_grad()
+def emit_records(clip_model, images, annotations, n_px: int = 224, max_crops: int = 256,
+                 preprocessor: CropPreprocessor = None) -> List[Dict[str, np.ndarray]]:
+    """The records of a sequence of images, the list ``[emit_record(clip_model, image, **annotation) ...]`` would give, with one
+    ``CropPreprocessor.batch`` call, one ``encode_image`` and one device-to-host copy per group of ``plan_record_batches`` instead of per
+    image.  ``annotations``: one dict with ``boxes_h``, ``boxes_o``, ``verbs``, ``objects`` per image.  The crops of an image keep the
+    order union, object, human; they have the bits of the per-image crops.  (The features of a 6-crop and a 256-crop ``encode_image``
+    call differ within the tower's contract: the tower chooses its kernels by the rows of a call.)"""
+    images, annotations = list(images), list(annotations)
+    if len(images) != len(annotations):
+        raise ValueError("one annotation per image")
+    pre = preprocessor or CropPreprocessor(n_px)
+    recs, crops = [], []
+    for a in annotations:
+        bh = np.asarray(a["boxes_h"], np.float32).reshape(-1, 4)
+        bo = np.asarray(a["boxes_o"], np.float32).reshape(-1, 4)
+        n = bh.shape[0]
+        if bo.shape[0] != n or len(a["verbs"]) != n or len(a["objects"]) != n:
+            raise ValueError("boxes_h, boxes_o, verbs and objects must describe the same pairs")
+        recs.append({"boxes_h": bh, "boxes_o": bo, "verbs": np.asarray(a["verbs"], np.int64), "objects": np.asarray(a["objects"], np.int64)})
+        crops.append(np.concatenate([pil_box(union_boxes(bh, bo)), pil_box(bo), pil_box(bh)], axis=0).reshape(-1, 4))
+    for first, last in plan_record_batches([r["boxes_h"].shape[0] for r in recs], max_crops):
+        total = sum(c.shape[0] for c in crops[first:last])
+        feats = np.zeros((0, clip_model.visual.output_dim), np.float32)
+        if total:
+            # One device-to-host copy per group: the per-crop status (0 .. 7, exact in fp32) rides as a last column of the features.
+            # A refused crop is NaN and the tower runs on it before the error below is raised: checking first would cost a second copy
+            # and a host wait in front of the tower for every group, to be quicker only where the call fails anyway.
+            x, status = pre.batch(images[first:last], crops[first:last], check=False)
+            both = torch.cat([clip_model.encode_image(x).float(), status.float()[:, None]], dim=1).cpu().numpy()      # the one copy
+            feats, st = both[:, :-1], both[:, -1].astype(np.int64)
+            if st.any():
+                i = int(np.nonzero(st)[0][0])
+                why = "; ".join(r for bit, r in CropPreprocessor.STATUS_REASONS if st[i] & bit)
+                raise ValueError(f"{why}: crop {i} of the group of images {first} .. {last - 1}")
+        at = 0
+        for i in range(first, last):
+            n = recs[i]["boxes_h"].shape[0]
+            f = feats[at:at + 3 * n]
+            at += 3 * n
+            recs[i].update(union_features=f[:n].copy(), object_features=f[n:2 * n].copy(), huamn_features=f[2 * n:].copy())
+    return recs
 
 
 @torch.no_grad()

@@ -407,6 +407,32 @@ int hg_hoi_detections(hg_ctx*, const hg_hoi_detections_args* args, void* stream)
 #define HG_PRE_IMAGENET_NORM 4
 int hg_preprocess_crops(hg_ctx*, const uint8_t* img, int H, int W, const int32_t* boxes_host, int n, int n_px,
                         int pad_square, uint32_t background, float* out, uint8_t* out_u8, void* stream);
+/* Crop pre-processing for the crops of a batch of images in one call: crop i of image crop_image[i] receives exactly the bytes and
+ * fp32 bits hg_preprocess_crops gives for that box on that image with the same flags - image.crop / expand2square / _transform(n_px)
+ * (pre_images/crop_images.py:204-219, utils_tip_cache_and_union_finetune.py:201-212, clipnet/clip.py:75-82) or, with HG_PRE_STRETCH |
+ * HG_PRE_IMAGENET_NORM and the whole-image box, the detector's CLIP view of every image of a batch
+ * (utils_tip_cache_and_union_finetune.py:105-114).  The boxes are in DEVICE memory and the host never reads them: no host
+ * synchronisation, no device-to-host copy, no allocation in steady state; the workspace is n * (24 + 2 * n_px * 67) words, sized
+ * from n and n_px alone.  Asynchronous on `stream`.
+ * Limits (HG_ERR_INVALID with a message): 1 <= B <= 64, 0 <= n <= 4096, 1 <= n_px <= 518.  Checked per crop on the device, reported in
+ * status[i] (0: done) while every other crop of the call is unaffected:
+ *   bit 0  empty box (x1 <= x0 or y1 <= y0)
+ *   bit 1  more than 65 taps on either axis (a downscale above 16), or a box coordinate outside +-2^20
+ *   bit 2  crop_image[i] outside [0, B)
+ * A crop with a non-zero status has NaN in all its fp32 planes and 0 in its uint8 output. */
+typedef struct {
+    const uint8_t* const* images;      /* HOST [B]: device pointers, uint8 [H_b, W_b, 3] RGB */
+    const int32_t *heights, *widths;   /* HOST [B] */
+    int32_t B;
+    const int32_t* boxes;              /* DEVICE int32 [n][4] = (x0, y0, x1, y1), PIL convention, may leave the image */
+    const int32_t* crop_image;         /* DEVICE int32 [n]: the image of crop i */
+    int32_t n, n_px, flags;            /* flags: HG_PRE_PAD_SQUARE | HG_PRE_STRETCH | HG_PRE_IMAGENET_NORM, per call */
+    uint32_t background;               /* 0x00BBGGRR */
+    float* out;                        /* DEVICE fp32 [n, 3, n_px, n_px] */
+    uint8_t* out_u8;                   /* DEVICE, nullable: uint8 [n, n_px, n_px, 3] */
+    int32_t* status;                   /* DEVICE int32 [n] */
+} hg_preprocess_batch_args;
+int hg_preprocess_batch(hg_ctx*, const hg_preprocess_batch_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
