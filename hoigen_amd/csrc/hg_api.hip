@@ -31,9 +31,10 @@ const Option OPTIONS[] = {
     {"mlp_pair_chunk", "HG_MLP_PAIR_CHUNK", &hg_ctx::opt_mlp_pair_chunk, false, 1, 64, "1 .. 64"},
     {"mlp_pair_fc_slots", "HG_MLP_PAIR_FC_SLOTS", &hg_ctx::opt_mlp_pair_fc_slots, false, 1, 64, "1 .. 64"},
     {"mlp_pair256", "HG_MLP_PAIR256", &hg_ctx::opt_mlp_pair256, false, 0, 1, "0 or 1"},
-    {"mlp_pair256_min_m", "HG_MLP_PAIR256_MIN_M", &hg_ctx::opt_mlp_pair256_min_m, false, 2048, INT_MAX, ">= 2048"},
+    {"mlp_pair256_min_m", "HG_MLP_PAIR256_MIN_M", &hg_ctx::opt_mlp_pair256_min_m, false, 256, INT_MAX, ">= 256"},
     {"mlp_pair256_chunk", "HG_MLP_PAIR256_CHUNK", &hg_ctx::opt_mlp_pair256_chunk, false, 1, 64, "1 .. 64"},
     {"mlp_pair256_ratio", "HG_MLP_PAIR256_RATIO", &hg_ctx::opt_mlp_pair256_ratio, false, 1, 8, "1 .. 8"},
+    {"mlp_pair256_ph2", "HG_MLP_PAIR256_PH2", &hg_ctx::opt_mlp_pair256_ph2, false, 0, 1, "0 or 1"},
     {"mlp_pair256_launches", "HG_MLP_PAIR256_LAUNCHES", &hg_ctx::n_pair256_launches, false, 0, INT_MAX, ">= 0"},      // (a counter: see the header)
     {"mlp_pair_fault", "HG_MLP_PAIR_FAULT", &hg_ctx::opt_mlp_pair_fault, false, 0, 1, "0 or 1"},
 };

@@ -22,10 +22,33 @@ namespace hg {
 #define SEG_E(k) do {} while (0)
 #endif
 
-// HL (EPI_RESID_LN_F32 at MF = 4, four phases; GemmArgs::hl): the residual stream as centre + hi + lo, in the very bytes the 128 x 256
+// Fragment I of 16 (8 of A, 8 of W) of the one-tile two-phase loop, read from LDS into a FIXED register tuple, v[192 + 4 I : 195 + 4 I].
+// Left to the register allocator, values that live across the loop in ones and twos (a zero for the panel poll's address, the lane
+// number, hoisted epilogue addresses) end up between the fragment tuples and push them to 2 (mod 4), where MFMAs issue slower.  The
+// ds_read itself is the asm statement: an empty asm that only names the tuple reads the register the ds_read is filling, and the
+// compiler then waits for every ds_read on its own (measured: profiles/mlp_pair256_ph2.txt).  The compiler does not know of these
+// reads: the fetch segment ends in an explicit lgkmcnt(0) (sync_fetch) before anything uses them.
+template <int I, int OFF, class T>
+__device__ __forceinline__ void ds_read_fixed(T& x, int addr) {
+    static_assert(sizeof(T) == 16 && I >= 0 && I < 16 && OFF >= 0 && OFF < 65536, "a 4-register fragment, 16 tuples, a 16-bit offset");
+#define HG_DS_READ_FIXED(n, r) if constexpr (I == n) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={" r "}"(x) : "v"(addr), "n"(OFF) : "memory")
+    HG_DS_READ_FIXED(0, "v[192:195]"); HG_DS_READ_FIXED(1, "v[196:199]"); HG_DS_READ_FIXED(2, "v[200:203]"); HG_DS_READ_FIXED(3, "v[204:207]");
+    HG_DS_READ_FIXED(4, "v[208:211]"); HG_DS_READ_FIXED(5, "v[212:215]"); HG_DS_READ_FIXED(6, "v[216:219]"); HG_DS_READ_FIXED(7, "v[220:223]");
+    HG_DS_READ_FIXED(8, "v[224:227]"); HG_DS_READ_FIXED(9, "v[228:231]"); HG_DS_READ_FIXED(10, "v[232:235]"); HG_DS_READ_FIXED(11, "v[236:239]");
+    HG_DS_READ_FIXED(12, "v[240:243]"); HG_DS_READ_FIXED(13, "v[244:247]"); HG_DS_READ_FIXED(14, "v[248:251]"); HG_DS_READ_FIXED(15, "v[252:255]");
+#undef HG_DS_READ_FIXED
+}
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// HL (EPI_RESID_LN_F32 at MF = 4; GemmArgs::hl): the residual stream as centre + hi + lo, in the very bytes the 128 x 256
 // kernel reads and writes (hg_gemm_ring2_body.h): 2 = hi + lo in, hi + lo out; 3 = hi + lo in, fp32 out.  SCHED::CONSUME: the A operand
 // is written by other workgroups of this launch on the same XCD (hg_mlp_pair256.hip): it is fetched past this CU's vector L1 (sc1); the
 // caller has waited for the row panel and runs the body on ONE tile per call, so the operand ring never reaches into a panel early.
+// The two-phase loop (PH2) under EPI_RESID_LN_F32 exists for such one-tile calls only: no tile follows and no stores are pending at the
+// start, so its K-tile kinds are decided at compile time and only the last one carries the residual prefetch (hg_mlp_pair256p.hip).
 template <int MF, int EPI, bool PH2, int HL = 0, class SCHED>
 __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned a_bytes, const int mode, const SCHED& sc) {
 #if defined(__HIP_DEVICE_COMPILE__)   // device-only builtins (buffer resources, LDS DMA): host sees just the stub
@@ -44,7 +67,11 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     constexpr bool F16_STORES = (EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_QGELU_F16 || EPI == EPI_BIAS_RELU_F16 ||
                                  EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_QGELU_F16);
     constexpr bool IN_HL = (HL == 2 || HL == 3), OUT_HL = (HL == 2);
-    static_assert(HL == 0 || (IN_HL && RLN && MF == 4 && !PH2), "hi / lo stream: EPI_RESID_LN_F32 on 256 rows, four phases, hl 2 or 3");
+    static_assert(HL == 0 || (IN_HL && RLN && MF == 4), "hi / lo stream: EPI_RESID_LN_F32 on 256 rows, hl 2 or 3");
+    // ONE: PH2 on a one-tile call (SCHED::CONSUME).  The stream ends with the tile, the bias staging above the prologue has drained
+    // every older store: `more` and `post` are constants, and the waits of the last two K-tiles count what is really behind them
+    constexpr bool ONE = PH2 && SCHED::CONSUME;
+    static_assert(!(PH2 && RLN) || (ONE && MF == 4), "two-phase loop under EPI_RESID_LN_F32: one tile per call, 256 rows");
     // (HL: per pair of row tiles 4 copy + 2 statistics stores and 4 lo or 16 fp32 stores, four pairs)
     constexpr int E_RAW = IN_HL ? (OUT_HL ? 40 : 88) : RLN ? 8 * MF + 4 * MF + 2 * MF : (F16_STORES ? 4 * MF : 8 * MF);
     constexpr int E = E_RAW > 52 ? 52 : E_RAW;
@@ -79,7 +106,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
     // (the MLP pair kernel's schedules rebuild the thread id from the wave index and v_mbcnt, behind an opaque move: threadIdx.x itself
     // would have to stay in v0 across the other body, and with v0 / v1 taken every register tuple of this body - accumulators, fragments -
     // starts at 2 (mod 4) instead of 0: the same K loop then runs 6 % slower (profiles/r06_mlp_pair.txt))
-    const int tid = sc.thread_id(), lane = tid & 63;
+    const int tid = sc.thread_id();
+    int lane = tid & 63;      // (ONE: rebuilt behind the steady-state loop, see there)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int nk = p.K / BK;
@@ -209,6 +237,24 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
                 wb[h][g2][ks] = *reinterpret_cast<const half8*>(smem + buf + h * BH + w_row + g2 * 2048 + coff[ks]);
+    };
+
+    // (ONE) the same reads into fixed tuples (ds_read_fixed): LDS addresses, the ring's base included
+    auto read_A_fixed = [&](auto H, int buf) {
+        constexpr int h = decltype(H)::value;
+        const int base = (int)(unsigned)(__SIZE_TYPE__)(HG_LDS char*)smem + buf + a_row;
+        static_for<2 * MF>([&](auto I) {
+            constexpr int f = decltype(I)::value >> 1, ks = decltype(I)::value & 1;
+            if constexpr (MF == 4) ds_read_fixed<f * 2 + ks, h * AH + f * 2048>(xa[f][ks], base + coff[ks]);
+        });
+    };
+    auto read_W_fixed = [&](auto H, int buf) {
+        constexpr int h = decltype(H)::value;
+        const int base = (int)(unsigned)(__SIZE_TYPE__)(HG_LDS char*)smem + buf + w_row;
+        static_for<4>([&](auto I) {
+            constexpr int g2 = decltype(I)::value >> 1, ks = decltype(I)::value & 1;
+            ds_read_fixed<8 + h * 4 + g2 * 2 + ks, h * BH + g2 * 2048>(wb[h][g2][ks], base + coff[ks]);
+        });
     };
 
     f32x4 acc[2][2][MF][2];
@@ -376,8 +422,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             constexpr int KINDX = decltype(KIND_T)::value;
             constexpr int KIND = KINDX >= 4 ? 0 : KINDX;
             const int buf = (g & 1) * STAGE;
-            const bool post = post_ok;
-            const bool more = KIND < 2 || r + 1 < n_items;       // a K-tile two positions ahead exists
+            const bool post = !ONE && post_ok;
+            const bool more = KIND < 2 || (!ONE && r + 1 < n_items);       // a K-tile two positions ahead exists
             const bool pub = PUB && r > 0 && wave == 0;      // this wave publishes the previous tile
             (void)post; (void)more; (void)pub;
             // Two phases per K-tile (32 MFMAs per segment, half the barriers):
@@ -385,16 +431,23 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             //   PB: fetch A1 (t);       refill A0 W0 W1 (t+2);         wait -> A0 W0 W1 (t+1) landed; quadrants (1,1) (1,0)
             // both waits leave NP = 2GA+2GB DMA instructions (64 KiB per CU) in flight
             constexpr int NP = 2 * GA + 2 * GB;
-            read_A(0, buf);
-            read_W(I0{}, buf);
-            read_W(I1{}, buf);
+            if constexpr (ONE) {
+                read_A_fixed(I0{}, buf);
+                read_W_fixed(I0{}, buf);
+                read_W_fixed(I1{}, buf);
+            } else {
+                read_A(0, buf);
+                read_W(I0{}, buf);
+                read_W(I1{}, buf);
+            }
             if constexpr (LNC && KIND == 2) {
                 if (lane < BM / 16)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsM, (HG_LDS void*)(smem + MR_OFF + wave * BM), 16, lane * 16,
                                                              (m0 + wave * (BM / 8)) * 8, 0, 0);
             }
             if (KIND < 3 || more) issue_A(1, 0, GA);      // A1 of position g+1 exists unless the stream ends here
-            if constexpr (ROLL && KIND == 3) {
+            if constexpr (IN_HL && KIND == 3) unit_load(0);      // (xa, both W halves and this unit fit: 256 VGPRs, none spilled)
+            if constexpr (ROLL && !IN_HL && KIND == 3) {
                 {      // first ROLL_W residual chunks (+ the first row group's centre) of this tile
 #pragma unroll
                     for (int c = 0; c < ROLL_W; ++c) xw[c] = chunk_load(c);
@@ -424,8 +477,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             if constexpr (KINDX == 5) { if (pub) wait_vm<NP + 1>(); else wait_vm<NP>(); }
             else if constexpr (KIND == 0) wait_vm<NP>();
             else if constexpr (KIND == 1) { if (post) wait_vm<NP + E>(); else wait_vm<NP>(); }
-            else if constexpr (KIND == 2) { if (more) wait_vm<NP>(); else wait_vm<0>(); }
-            else { if (more) wait_vm<NP + R>(); else wait_vm<0>(); }
+            else if constexpr (KIND == 2) { if (more) wait_vm<NP>(); else wait_vm<ONE ? NP : 0>(); }      // (ONE: A1 of the last K-tile is behind it)
+            else { if (more) wait_vm<NP + R>(); else wait_vm<ONE ? R : 0>(); }      // (ONE: only the prefetch is younger)
             SEG_E(0);
             sync_fetch();
             mma(I0{}, I0{});
@@ -435,14 +488,15 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
                 // every wave has passed this phase's wait: the previous tile's stores have all retired
                 if (pub) sc.publish(tm_prev, lane);
             }
-            read_A(1, buf);
+            if constexpr (ONE) read_A_fixed(I1{}, buf);
+            else read_A(1, buf);
             if (KIND < 2 || more) { ld_advance(std::integral_constant<int, KIND == 2 ? 1 : 0>{}); issue_A(0, 0, GA); issue_W(0, 0, GB); issue_W(1, 0, GB); }
             SEG_B(0);
             if constexpr (KINDX == 4) { if (pub) wait_vm<NP + 1>(); else wait_vm<NP>(); }
             else if constexpr (KIND == 0) wait_vm<NP>();
             else if constexpr (KIND == 1) { if (post) wait_vm<NP + E>(); else wait_vm<NP>(); }
-            else if constexpr (KIND == 2) { if (more) wait_vm<NP>(); else wait_vm<0>(); }
-            else { if (more) wait_vm<NP + R>(); else wait_vm<0>(); }
+            else if constexpr (KIND == 2) { if (more) wait_vm<NP>(); else wait_vm<ONE ? GA : 0>(); }      // (ONE: A1 of the last K-tile may still fly)
+            else { if (more) wait_vm<NP + R>(); else if constexpr (!ONE) wait_vm<0>(); }      // (ONE: every operand has landed, the prefetch flies on)
             SEG_E(0);
             sync_fetch();
             mma(I1{}, I1{});
@@ -463,8 +517,13 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, const unsigned
             for (int kt = PUB ? 3 : 1; kt < klen - 2; ++kt) {
                 ph2_ktile(K0{});
             }
+            // (ONE) the lane number again, from an opaque thread id (Pair256ProjSchedT<true>): what the prefetch and the epilogue derive from
+            // it - row and column offsets, 64-bit addresses - is then worked out HERE and not held in VGPRs across the loop, which has
+            // 64 of them fewer with the fragments in fixed tuples (the hi / lo -> fp32 instance spilled one)
+            if constexpr (ONE) lane = sc.thread_id() & 63;
             ph2_ktile(K2{});
             ph2_ktile(K3{});
+            if constexpr (ONE) asm volatile("" : "+v"(lane));      // (and once more: the epilogue's own addresses are not held across the last K-tiles)
         } else {
         for (int kt = 0; kt < klen; ++kt, ++g) {
             const int buf = (g & 1) * STAGE;

@@ -192,6 +192,8 @@ struct hg_ctx {
                                        // panels; 6 measured best of 1 .. 32 on the headline step: profiles/mlp_pair256.txt)
     int opt_mlp_pair256_ratio = 4;     // ... c_fc tile times a 256 x 256 c_proj tile takes, what its dealing balances with: 166-176 k against 43-44 k ticks per
                                        // tile in the per-slot stamps (profiles/mlp_pair256.txt)
+    int opt_mlp_pair256_ph2 = 1;       // ... c_proj's K loop there in two phases (hg_mlp_pair256p.hip) instead of four (hg_mlp_pair256.hip).  Same bits
+                                       // (profiles/mlp_pair256_ph2.txt)
     int n_pair256_launches = 0;  // ... launches of that kernel so far (option "mlp_pair256_launches": read it; setting it restarts the count; the profiler
                                  // record is the pair launch's, so this is how a caller tells which kernel ran)
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound

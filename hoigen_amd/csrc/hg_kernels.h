@@ -101,6 +101,7 @@ hipError_t launch_gemm_simple(int epi, const GemmArgs& a, hipStream_t s);
 // word set when a hand-off wait times out; ch: 256-row panels of an XCD per chunk of the c_fc tile order; fc_slots: workgroups per XCD
 // that run c_fc tiles (of n_cu / 8)
 bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu);
+bool mlp_pair_shapes_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu);      // ... without its bound of 2 048 rows
 size_t mlp_pair_ready_words(int M);
 hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int fc_slots, int n_cu, hipStream_t s,
                            int grid_short = 0);      // grid_short (fault injection: hg_api.hip option mlp_pair_fault): workgroups NOT launched
@@ -108,6 +109,9 @@ hipError_t launch_mlp_pair(const GemmArgs& fc, const GemmArgs& proj, unsigned* r
 bool mlp_pair256_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu, int min_m);
 hipError_t launch_mlp_pair256(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int ratio, int n_cu,
                               hipStream_t s, int grid_short = 0);      // ch: panels per chunk of the c_fc order; ratio: c_fc tile times per c_proj tile
+// ... and c_proj's K loop in the two-phase form (hg_mlp_pair256p.hip): whatever mlp_pair256_ok takes, the same arguments and bits
+hipError_t launch_mlp_pair256p(const GemmArgs& fc, const GemmArgs& proj, unsigned* ready, int* err, int ch, int ratio, int n_cu,
+                               hipStream_t s, int grid_short = 0);
 // two 4-wave workgroups per CU, 128x256 tiles, free-running (hg_gemm_duo.hip): residual GEMMs and fp16/fp32 outputs
 bool gemm_duo_ok(int epi, const GemmArgs& a);
 hipError_t launch_gemm_duo(int epi, const GemmArgs& a, hipStream_t s);

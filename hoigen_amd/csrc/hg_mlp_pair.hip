@@ -162,13 +162,14 @@ __global__ __launch_bounds__(512, 2) void mlp_pair_kernel(const MlpPairArgs P_in
 }
 
 // c_fc: a LayerNorm-folded QuickGELU GEMM the 256 x 256 ring kernel takes; c_proj: the LayerNorm-emitting residual GEMM on fc
-bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu) {
+bool mlp_pair_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu) { return fc.M >= 8 * 256 && mlp_pair_shapes_ok(fc, proj, n_cu); }
+// (without the row bound: the 256-row launch deals whatever panels there are - XCDs without a panel own no tile - and has a bound of its own)
+bool mlp_pair_shapes_ok(const GemmArgs& fc, const GemmArgs& proj, int n_cu) {
     if (n_cu != 32 * MLP_NX) return false;      // one workgroup per CU must put gridDim / 8 workgroups on each of the 8 XCDs (MI355X: 8 x 32 CUs)
     if (!gemm_ln_ok(EPI_LN_BIAS_QGELU_F16, fc) || !gemm_ln_ok(EPI_RESID_LN_F32, proj)) return false;
     if (fc.M != proj.M || proj.K != fc.N || proj.lda != fc.ldc || (const void*)proj.A != fc.out) return false;
     if (fc.K < 5 * 64 || proj.K < 8 * 64) return false;                    // K-tile kinds of the two hand-off protocols
     if ((size_t)((fc.M + 255) / 256) * 256 * fc.ldc * 2 >= (1ull << 32)) return false;      // fc through one buffer descriptor
-    if (fc.M < 8 * 256) return false;
     // (the text tower: the next LayerNorm's weight in the activation copy - beside the stream's hi half where the stream leaves as hi / lo)
     if (proj.gamma && proj.hl == 2 && (!proj.out3 || proj.ld3 < proj.N || (proj.ld3 % 8))) return false;
     return proj.hl == 0 || proj.hl == 2 || proj.hl == 3;

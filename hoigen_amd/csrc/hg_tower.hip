@@ -358,10 +358,11 @@ int plan_tower(hg_ctx* c, const std::vector<BlockW>& blocks, const TowerCall& t,
     for (size_t i = 0; p.pair_on && i + 1 < nb; ++i) {    // (the arguments name the next block's copy: behind the loop above)
         const GemmArgs fc = fc_args(p, blocks[i], p.blocks[i], D);
         const GemmArgs proj = proj_args(p, blocks[i], p.blocks[i], D, &p.blocks[i + 1], blocks[i + 1].ln1_w);
-        p.blocks[i].pair = mlp_pair_ok(fc, proj, c->n_cu);
         // (the text tower keeps the 128-row kernel in either text_ln_fold form: the 256-row one has no gamma instance and has not been
         // measured at width 512)
-        p.blocks[i].pair256 = p.blocks[i].pair && c->opt_mlp_pair256 && !t.causal && mlp_pair256_ok(fc, proj, c->n_cu, c->opt_mlp_pair256_min_m);
+        // (... and alone takes calls of fewer than 2 048 rows, where mlp_pair256_min_m lets it)
+        p.blocks[i].pair256 = c->opt_mlp_pair256 && !t.causal && mlp_pair256_ok(fc, proj, c->n_cu, c->opt_mlp_pair256_min_m);
+        p.blocks[i].pair = p.blocks[i].pair256 || mlp_pair_ok(fc, proj, c->n_cu);
     }
     p.pre16 = !t.pre_w ? (p.gs ? p.hg : p.h) : nb ? p.blocks[0].x16 : p.h;      // (rowstats_cast writes dense rows)
     p.pre_ld = t.pre_w && nb ? p.blocks[0].ldx : D;
@@ -460,7 +461,9 @@ int launch_mlp(hg_ctx* c, const TowerCall& t, const TowerPlan& p, const std::vec
         ProfScope ps(c, s, HG_PROF_MLP_PAIR, p.M, 4 * D, D);
         unsigned* ready = (unsigned*)c->pair_ready.p + i * (size_t)p.pair_panels;
         if (b.pair256) ++c->n_pair256_launches;
-        if (b.pair256)
+        if (b.pair256 && c->opt_mlp_pair256_ph2)
+            HG_HIP(launch_mlp_pair256p(fc, proj, ready, c->pair_err, c->opt_mlp_pair256_chunk, c->opt_mlp_pair256_ratio, c->n_cu, s, c->opt_mlp_pair_fault));
+        else if (b.pair256)
             HG_HIP(launch_mlp_pair256(fc, proj, ready, c->pair_err, c->opt_mlp_pair256_chunk, c->opt_mlp_pair256_ratio, c->n_cu, s, c->opt_mlp_pair_fault));
         else
             HG_HIP(launch_mlp_pair(fc, proj, ready, c->pair_err, c->opt_mlp_pair_chunk, c->opt_mlp_pair_fc_slots, c->n_cu, s, c->opt_mlp_pair_fault));

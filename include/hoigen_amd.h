@@ -498,10 +498,13 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      activation copy (the vision tower), its c_proj tiles are 256 x 256 instead of 128 x 256 (hoigen_amd/csrc/hg_mlp_pair256.hip:
  *                      a third less global -> LDS traffic per flop, the work slots of an XCD share its tiles by work); the text tower's form and
  *                      0: 128 x 256.  Bit-identical results in both; the same ready words, error word and profiler record.
- *   "mlp_pair256_min_m" [HG_MLP_PAIR256_MIN_M] >= 2048: rows from which on "mlp_pair256" applies (default 25000: measured faster from 128 crops =
+ *   "mlp_pair256_min_m" [HG_MLP_PAIR256_MIN_M] >= 256: rows from which on "mlp_pair256" applies (default 25000: measured faster from 128 crops =
  *                      25 216 rows on, slower at 96 crops and below, where a slot owns too few of the big tiles)
  *   "mlp_pair256_chunk" [HG_MLP_PAIR256_CHUNK] 1 .. 64: 256-row panels of an XCD per chunk of that kernel's c_fc tile order (default 6; speed only)
  *   "mlp_pair256_ratio" [HG_MLP_PAIR256_RATIO] 1 .. 8: c_fc tile times its dealing counts for a c_proj tile (default 4: measured 3.8 - 4.1; speed only)
+ *   "mlp_pair256_ph2" [HG_MLP_PAIR256_PH2] 1 (default): wherever "mlp_pair256" applies, c_proj runs the two-phase K loop c_fc already runs (half the
+ *                      barriers, no decisions inside the loop: hoigen_amd/csrc/hg_mlp_pair256p.hip); 0: the four-phase loop
+ *                      (hg_mlp_pair256.hip).  Bit-identical results in both; the same launch count and profiler record.
  *   "mlp_pair256_launches" [HG_MLP_PAIR256_LAUNCHES] a counter, not a switch: hg_get_option reads how many launches of that kernel the context has
  *                      made (its profiler record is the pair launch's); setting it (>= 0) restarts the count from that value
  *   "mlp_pair_fault"  [HG_MLP_PAIR_FAULT]  test hook, default 0.  1: that launch goes out one workgroup short - a work slot nobody takes -, so that the
