@@ -139,6 +139,18 @@ class hg_preprocess_batch_args(C.Structure):
                 ("background", C.c_uint32), ("out", C.c_void_p), ("out_u8", C.c_void_p), ("status", C.c_void_p)]
 
 
+# limits of one hg_detector_views call, and the tiling of its kernel (hoigen_amd/csrc/hg_detector_views_geom.h): output rows of a band at
+# most, output columns of a strip, strips of a workgroup, rows of the window in LDS
+HG_DV_MAX_IMAGES, HG_DV_MAX_SIDE, HG_DV_MAX_TAPS, HG_DV_MAX_CLIP_PX = 64, 2048, 65, 518
+HG_DV_BAND, HG_DV_STRIP, HG_DV_STRIPS, HG_DV_WIN_ROWS = 32, 64, 4, 72
+
+
+class hg_detector_views_args(C.Structure):
+    _fields_ = [("images", C.POINTER(C.c_void_p)), ("heights", C.POINTER(C.c_int32)), ("widths", C.POINTER(C.c_int32))] + \
+               [(n, C.c_int32) for n in ("B", "size", "max_size", "clip_px", "hmax", "wmax")] + \
+               [(n, C.c_void_p) for n in ("resized_u8", "detr", "mask", "clip")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -193,6 +205,9 @@ SIGNATURES = {
     "hg_hoi_detections": (_I, [_P, C.POINTER(hg_hoi_detections_args), _P]),
     "hg_preprocess_crops": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P]),
     "hg_preprocess_batch": (_I, [_P, C.POINTER(hg_preprocess_batch_args), _P]),
+    "hg_detector_view_shapes": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "hg_detector_views": (_I, [_P, C.POINTER(hg_detector_views_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),

@@ -158,6 +158,7 @@ struct hg_ctx {
     Buf props;           // hg_region_priors: keep, boxes, scores, labels of the selected instances where the caller does not ask for them
     Buf det;             // hg_hoi_detections: row counts, workgroup sums, and the entry arrays the association reads where the caller does not ask for them
     Buf prebatch;        // hg_preprocess_batch: per-crop headers and weight tables, sized from n and n_px alone
+    Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
     int max_chunk_rows = 32768;
@@ -223,7 +224,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch}
+     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

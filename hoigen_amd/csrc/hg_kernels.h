@@ -297,6 +297,19 @@ hipError_t launch_preprocess_batch(const PreBatch& pb, const int32_t* boxes, con
                                    uint32_t background, int32_t* head, int32_t* tab, float* out, uint8_t* out_u8, int32_t* status,
                                    hipStream_t s);
 
+// ---- the detector's two views of a batch (hg_detector_views.hip; limits, sizes and tiling: hg_detector_views_geom.h): tab receives the
+// images' weight tables, boxes [B][4] and crop_image [B] the arguments of the CLIP leg; u8 holds the resized image b at byte
+// 256 * u8_256[b]; detr fp32 [B, 3, hmax, wmax]; mask uint8 [B, hmax, wmax]; max_bands: the most bands any image has (dv_bands)
+struct DvBatch {      // host-built, by value: the image table
+    const uint8_t* img[64];
+    int32_t H[64], W[64], oh[64], ow[64];
+    int32_t tab[64];          // word offset of the image's tables
+    uint32_t u8_256[64];      // byte offset of its resized image / 256
+    int32_t B, hmax, wmax;
+};
+hipError_t launch_detector_views(const DvBatch& dv, int max_bands, int32_t* tab, int32_t* boxes, int32_t* crop_image, uint8_t* u8,
+                                 float* detr, uint8_t* mask, hipStream_t s);
+
 // RoI-align (torchvision semantics, aligned=True, sampling_ratio=-1) of feat [C,H,W] for boxes [n,4] (device):
 // out_pooled [n,C,P,P] and/or out_mean [n,C] (= .flatten(2).mean(-1)); either may be null
 hipError_t launch_roi_align(const float* feat, int C, int H, int W, const float* boxes, int n, float spatial_scale,

@@ -14,7 +14,8 @@ raise ``RuntimeError``.
 ``CropPreprocessor.batch`` does the same for the crops of a batch of images in one call (``hg_preprocess_batch``, two launches): the
 boxes stay in device memory, the geometry is worked out per crop on the device and the intermediate of the separable resize stays in
 LDS, so the host neither waits nor copies anything back.  With ``stretch=True, imagenet_norm=True`` and no boxes it is the detector's
-CLIP view of every image of a batch (utils_tip_cache_and_union_finetune.py:105-114).
+CLIP view of every image of a batch (utils_tip_cache_and_union_finetune.py:105-114) - of the images ``RandomResize([800], 1333)`` has
+already resized: ``detector_views.DetectorViews`` makes those and this view of them from the raw images in one call.
 """
 from typing import Sequence
 

@@ -433,6 +433,53 @@ typedef struct {
     int32_t* status;                   /* DEVICE int32 [n] */
 } hg_preprocess_batch_args;
 int hg_preprocess_batch(hg_ctx*, const hg_preprocess_batch_args* args, void* stream);
+/* The detector's two views of a batch from raw images: what DataFactory.__getitem__, its collate and UPT.forward make of every image on
+ * the host (utils_tip_cache_and_union_finetune.py:109-114, :193-196; upt...:1593, :1613), in one call on the device:
+ *   RandomResize([size], max_size)      detr/datasets/transforms_clip.py:139-170: a Pillow BICUBIC resize of the whole image
+ *   IResize([clip_px, clip_px])         of THAT RESIZED image (transforms_clip.py:279-288)
+ *   ToTensor + Normalize (ImageNet)     utils_tip_cache_and_union_finetune.py:86-89, on both
+ *   nested_tensor_from_tensor_list      detr/util/misc.py:307-329: zero padding to the batch maxima, mask 1 in the padding
+ *
+ * hg_detector_view_shapes is pure host code: no context, no device.  It restates get_size_with_aspect_ratio (transforms_clip.py:142-161)
+ * in doubles for B images of heights[b] x widths[b]; max_size = 0 means None.  With mn = (double)min(w, h), mx = (double)max(w, h): if
+ * mx / mn * size > max_size then size = (int)nearbyint((double)max_size * mn / mx) - Python's round, half to even: a 5 x 132 image at
+ * size 40, max_size 66 gets 2, not 3.  If the short side equals size the output is (h, w); else if w < h, ow = size and
+ * oh = (int)((double)((long long)size * h) / (double)w); otherwise the mirror.  out_sizes [B][2] = (oh, ow) (nullable); *hmax, *wmax the
+ * maxima; u8_off [B + 1] (nullable): the byte offset of every resized image in one buffer, each a multiple of 256, and the total.
+ * Returns HG_OK, or HG_ERR_INVALID at the first image it refuses, with that image's index in *hmax (-1: B < 1, size outside 1 .. 2048
+ * or max_size outside 0 .. 2048) and the reason in *wmax: 1 an output side of 0 (Pillow raises there), 2 an output side above 2048,
+ * 3 more than 65 taps on an axis (a downscale above 16), 4 a height or width below 1.
+ *
+ * hg_detector_views writes, for image b with (oh, ow) and u8_off as above,
+ *   resized_u8 + u8_off[b]  uint8 [oh, ow, 3]: Pillow's 8-bit ImagingResample of the whole image to (ow, oh), bit for bit: horizontal
+ *                           pass first, uint8 rounding after each pass, 22-bit weights (precompute_coeffs) evaluated on the device in IEEE
+ *                           double with one rounding per operation
+ *   detr[b, c, y, x]        ((float)u / 255.0f - mean_c) / std_c of that byte inside (oh, ow), 0 outside
+ *   mask[b, y, x]           0 inside (oh, ow), 1 outside
+ *   clip[b]                 what hg_preprocess_batch gives for the whole-image box of the resized image with HG_PRE_STRETCH |
+ *                           HG_PRE_IMAGENET_NORM at n_px = clip_px (its kernels run inside this call)
+ * Every byte of detr and mask is written: nothing outside detr, mask, clip and resized_u8 [0, u8_off[B]) is touched.  hmax, wmax: the
+ * padded extent; 0, 0 means the maxima of this call's images, anything else must be at least those and at most 2048 (a call that writes
+ * a slice of a larger batch).  No host synchronisation, no device-to-host copy, no allocation in steady state (grow-only
+ * workspace: tables of (ow * (2 + taps_h) + oh * (2 + taps_v)) words an image, and the resized images where resized_u8 is NULL).
+ * Asynchronous on `stream`.  Everything is validated on the host before anything is launched: HG_ERR_INVALID, with the image named in
+ * hg_last_error, for what hg_detector_view_shapes refuses, B outside 1 .. 64, clip_px outside 0 .. 518, a null image, or a resized
+ * image that clip_px is a downscale above 16 of. */
+int hg_detector_view_shapes(const int32_t* heights, const int32_t* widths, int B, int size, int max_size, int32_t* out_sizes,
+                            int32_t* hmax, int32_t* wmax, int64_t* u8_off);
+typedef struct {
+    const uint8_t* const* images;      /* HOST [B]: device pointers, uint8 [H_b, W_b, 3] RGB */
+    const int32_t *heights, *widths;   /* HOST [B] */
+    int32_t B;                         /* <= 64 */
+    int32_t size, max_size;            /* RandomResize([size], max_size); max_size 0: None */
+    int32_t clip_px;                   /* 0: no CLIP view, else <= 518 */
+    int32_t hmax, wmax;                /* 0, 0: this call's maxima */
+    uint8_t* resized_u8;               /* DEVICE, nullable (then in the workspace): image b at u8_off[b] as uint8 [oh_b, ow_b, 3] */
+    float* detr;                       /* DEVICE fp32 [B, 3, hmax, wmax] */
+    uint8_t* mask;                     /* DEVICE uint8 [B, hmax, wmax], 1 = padding */
+    float* clip;                       /* DEVICE fp32 [B, 3, clip_px, clip_px]; unused with clip_px 0 */
+} hg_detector_views_args;
+int hg_detector_views(hg_ctx*, const hg_detector_views_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
