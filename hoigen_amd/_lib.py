@@ -151,6 +151,25 @@ class hg_detector_views_args(C.Structure):
                [(n, C.c_void_p) for n in ("resized_u8", "detr", "mask", "clip")]
 
 
+_DETR_LAYER_FIELDS = ["in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "linear1_weight", "linear1_bias",
+                      "linear2_weight", "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias"]
+HG_DETR_ATTN_MAX_L = 1792      # tokens per image of one hg_detr_encoder call at most (hoigen_amd/csrc/hg_kernels.h)
+
+
+class hg_detr_layer_weights(C.Structure):
+    _fields_ = [(n, hg_tensor) for n in _DETR_LAYER_FIELDS]
+
+
+class hg_detr_encoder_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "heads", "d_ff", "n_layers", "normalize_before", "activation")] + \
+               [("layers", C.POINTER(hg_detr_layer_weights))]
+
+
+class hg_detr_encoder_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("src", "pos", "mask", "out", "trace")] + [("B", C.c_int32), ("S", C.c_int32),
+                ("src_stride", C.c_int64 * 3), ("pos_stride", C.c_int64 * 3), ("out_stride", C.c_int64 * 3)]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -208,6 +227,8 @@ SIGNATURES = {
     "hg_detector_view_shapes": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "hg_detector_views": (_I, [_P, C.POINTER(hg_detector_views_args), _P]),
+    "hg_load_detr_encoder": (_I, [_P, C.POINTER(hg_detr_encoder_weights)]),
+    "hg_detr_encoder": (_I, [_P, C.POINTER(hg_detr_encoder_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -215,6 +236,7 @@ SIGNATURES = {
     "hg_test_gemm_ex": (_I, [_P, C.POINTER(hg_test_gemm_ex_args), _P]),
     "hg_test_gemm_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "hg_test_detr_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "hg_test_qkv_attn": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hg_test_qkv_attn_ex": (_I, [_P, C.POINTER(hg_test_qkv_attn_ex_args), _P]),
     "hg_test_gemm_hilo": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

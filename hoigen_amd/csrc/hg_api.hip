@@ -36,6 +36,8 @@ const Option OPTIONS[] = {
     {"mlp_pair256_ratio", "HG_MLP_PAIR256_RATIO", &hg_ctx::opt_mlp_pair256_ratio, false, 1, 8, "1 .. 8"},
     {"mlp_pair256_ph2", "HG_MLP_PAIR256_PH2", &hg_ctx::opt_mlp_pair256_ph2, false, 0, 1, "0 or 1"},
     {"mlp_pair256_launches", "HG_MLP_PAIR256_LAUNCHES", &hg_ctx::n_pair256_launches, false, 0, INT_MAX, ">= 0"},      // (a counter: see the header)
+    {"detr_attn_chunk", "HG_DETR_ATTN_CHUNK", &hg_ctx::opt_detr_attn_chunk, false, 0, 1280, "0 .. 1280 (a multiple of 32)"},
+    {"detr_attn_waves", "HG_DETR_ATTN_WAVES", &hg_ctx::opt_detr_attn_waves, false, 0, 4, "0, 1, 2 or 4"},
     {"mlp_pair_fault", "HG_MLP_PAIR_FAULT", &hg_ctx::opt_mlp_pair_fault, false, 0, 1, "0 or 1"},
 };
 const Option* find_option(const char* key) {
@@ -105,6 +107,7 @@ void hg_destroy(hg_ctx* c) {
     for (auto& m : c->mlp) free_all(m.owned);
     for (auto& m : c->cache) free_all(m.owned);
     for (auto& m : c->prior) free_all(m.owned);
+    free_all(c->detr.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

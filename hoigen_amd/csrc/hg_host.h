@@ -135,6 +135,16 @@ struct Priors {      // priors_downproj + object_embedding (hg_load_priors): fp3
     float *w0t = nullptr, *b0 = nullptr, *w1t = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr, *T = nullptr;
     std::vector<void*> owned;
 };
+struct DetrLayerW {      // one post-norm encoder layer (detr/models/transformer.py:127-162): linears fp16 [out, in], the rest fp32
+    half_t *w_in, *w_out, *w1, *w2;      // in_proj [3D, D] (q | k | v rows), out_proj [D, D], linear1 [F, D], linear2 [D, F]
+    float *b_in, *b_out, *b1, *b2, *n1_w, *n1_b, *n2_w, *n2_b;
+};
+struct DetrEnc {         // hg_load_detr_encoder
+    bool loaded = false;
+    int D = 0, heads = 0, F = 0;
+    std::vector<DetrLayerW> layers;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -147,6 +157,7 @@ struct hg_ctx {
     Mlp mlp[HG_MAX_SLOTS];
     Cache cache[HG_MAX_CACHE_SLOTS];
     Priors prior[HG_MAX_PRIOR_SLOTS];
+    DetrEnc detr;
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
@@ -158,6 +169,7 @@ struct hg_ctx {
     Buf props;           // hg_region_priors: keep, boxes, scores, labels of the selected instances where the caller does not ask for them
     Buf det;             // hg_hoi_detections: row counts, workgroup sums, and the entry arrays the association reads where the caller does not ask for them
     Buf prebatch;        // hg_preprocess_batch: per-crop headers and weight tables, sized from n and n_px alone
+    Buf detr_ws;         // hg_detr_encoder: the fp32 stream, the batch-major pos, and the fp16 operands x, x + pos, q | k, v, attention output, FFN hidden
     Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
@@ -197,6 +209,8 @@ struct hg_ctx {
                                        // (profiles/mlp_pair256_ph2.txt)
     int n_pair256_launches = 0;  // ... launches of that kernel so far (option "mlp_pair256_launches": read it; setting it restarts the count; the profiler
                                  // record is the pair launch's, so this is how a caller tells which kernel ran)
+    int opt_detr_attn_chunk = 0;     // hg_detr_attn.hip: keys per LDS chunk (0: all keys at once while they fit, 512 beyond; else a multiple of 32 up to 1 280).  Same bits
+    int opt_detr_attn_waves = 0;     // ... query tiles per slab = waves per workgroup: 0 = 4 (measured best or equal in every case: profiles/detr_encoder.txt), else 1, 2 or 4.  Same bits
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
     int n_cu = 256;
     // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became
@@ -224,7 +238,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews}
+     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

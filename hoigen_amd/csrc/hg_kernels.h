@@ -136,6 +136,43 @@ hipError_t launch_attention_long(const half_t* qkv, half_t* out, int n_seq, int 
 hipError_t launch_attention_long_row0(const half_t* qkv, const half_t* q0, const int32_t* sel, half_t* out, int n_seq, int L,
                                       int heads, bool causal, hipStream_t s);
 
+// ---- masked attention with head_dim 32 and separate query / key lengths (hg_detr_attn.hip: the DETR transformer) -------------
+// out = softmax(q k^T / sqrt(32) + key_padding_mask) v per (sequence, head).  q [n_seq * Lq, ldq], k [n_seq * Lk, ldk],
+// v [n_seq * Lk, ldv] fp16, each with its own pointer (16-byte aligned) and row stride in halfs (multiples of 8), head h = columns
+// 32h .. 32h+31; mask uint8 [n_seq, Lk], 1 = padded key, nullable; out fp16 [n_seq * Lq, ldo] (ldo a multiple of 4).
+// 1 <= Lq, Lk <= DETR_ATTN_MAX_L (42 x 42 = 1 764 tokens, the largest grid a stride-32 backbone makes of an 800 / 1333 resize in a
+// batch of mixed orientations, rounded up to 32 keys); above it hipErrorInvalidValue and nothing launched.
+// chunk: keys per LDS chunk - 0 = all keys at once while they fit (Lk <= DETR_ATTN_RESIDENT_L), DETR_ATTN_CHUNK_L beyond; otherwise a
+// multiple of 32 up to DETR_ATTN_RESIDENT_L.  Every chunk size gives the same bits.
+static constexpr int DETR_ATTN_MAX_L = 1792;
+static constexpr int DETR_ATTN_RESIDENT_L = 1280;      // 2 x 64 B x 1 280 keys = a CU's 160 KiB
+static constexpr int DETR_ATTN_CHUNK_L = 512;
+static constexpr int DETR_ATTN_NW = 4;                 // waves per workgroup = 32-query tiles per slab (DetrAttnArgs::waves: 1 or 2 instead)
+struct DetrAttnArgs {
+    const half_t *q, *k, *v;
+    int ldq, ldk, ldv;
+    const uint8_t* mask;
+    half_t* out;
+    int ldo;
+    int n_seq, Lq, Lk, heads;
+    int chunk;
+    int waves = 0;      // query tiles per slab = waves per workgroup: 0 = DETR_ATTN_NW, else 1, 2 or 4.  Same bits
+};
+int detr_attn_chunk_rows(int Lk, int chunk);      // keys per LDS chunk the launch uses
+hipError_t launch_detr_attention(const DetrAttnArgs& a, hipStream_t s);
+
+// ---- row kernels of the DETR encoder (hg_detr_rows.hip) ------------------------------------------------------------------------------
+// entry: src / pos fp32 with element strides (batch, token) and contiguous channels -> x fp32 [B*S, D] (sequence-major per image),
+// x16 = fp16(x), xp16 = fp16(x + pos), posb = pos batch-major [B*S, D]
+hipError_t launch_detr_entry(const float* src, const float* pos, long long sb, long long ss, long long pb, long long ps, int B, int S, int D,
+                             float* x, half_t* x16, half_t* xp16, float* posb, hipStream_t s);
+// post-norm: x = LayerNorm(x; w, b) in place (fp32, eps 1e-5, biased variance), x16 = fp16(x), xp16 = fp16(x + posb) (xp16 nullable),
+// copy = x (nullable: the trace; written element by element, 4-byte alignment is enough).  D a multiple of 4
+hipError_t launch_detr_postnorm(float* x, const float* w, const float* b, const float* posb, half_t* x16, half_t* xp16, float* copy, int M,
+                                int D, hipStream_t s);
+// exit: out[b * ob + t * os + c] = x[(b * S + t) * D + c]
+hipError_t launch_detr_exit(const float* x, float* out, long long ob, long long os, int B, int S, int D, hipStream_t s);
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

@@ -279,6 +279,63 @@ int hg_test_attention(hg_ctx* c, const float* qkv, const float* q0, const int32_
     return HG_OK;
 }
 
+// The DETR attention kernel alone (hg_detr_attn.hip) on fp32 arrays that hold fp16 values (include/hoigen_amd.h has the contract;
+// tests/test_gpu_detr_attention.py).  Every refusal is decided before anything is written.
+int hg_test_detr_attention(hg_ctx* c, const float* q, const float* k, const float* v, const uint8_t* mask, int n_seq, int Lq, int Lk,
+                           int heads, int chunk, int layout, int ldo, float* out, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!q || !k || !v || !out || n_seq < 1 || heads < 1) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: q, k, v, out, n_seq >= 1 and heads >= 1 are required");
+    if (Lq < 1 || Lk < 1 || Lq > DETR_ATTN_MAX_L || Lk > DETR_ATTN_MAX_L)
+        return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: Lq and Lk must be 1 .. %d (got %d, %d)", DETR_ATTN_MAX_L, Lq, Lk);
+    if (chunk < 0) chunk = c->opt_detr_attn_chunk;
+    if (chunk % 32 || chunk > DETR_ATTN_RESIDENT_L) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: chunk must be 0 or a multiple of 32 up to %d", DETR_ATTN_RESIDENT_L);
+    if (layout < 0 || layout > 2 || (layout != 1 && Lq != Lk)) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: layout 0 .. 2; 0 and 2 need Lq == Lk");
+    const int D = heads * 32;
+    if (!ldo) ldo = D;
+    if (ldo < D || ldo % 8) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: ldo >= heads * 32, a multiple of 8");
+    if ((long long)n_seq * (Lq > Lk ? Lq : Lk) > (1LL << 20)) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: at most 2^20 rows");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Mq = (size_t)n_seq * Lq, Mk = (size_t)n_seq * Lk;
+    int rc = ensure(c, c->qkv, (Mq + 2 * Mk) * D * 2);      // the three operands, dense, then interleaved into `h` as the layout asks
+    if (!rc) rc = ensure(c, c->h, (Mq + 2 * Mk) * D * 2);
+    if (!rc) rc = ensure(c, c->att, (Mq + 8) * ldo * 2);
+    if (rc) return rc;
+    HG_HIP(hipMemsetAsync(c->att.p, 0x5A, (Mq + 8) * ldo * 2, s));      // what the kernel does not write comes back as 203.25
+    half_t* d16 = (half_t*)c->qkv.p;
+    HG_HIP(launch_f32_to_f16(q, d16, Mq * D, s));
+    HG_HIP(launch_f32_to_f16(k, d16 + Mq * D, Mk * D, s));
+    HG_HIP(launch_f32_to_f16(v, d16 + (Mq + Mk) * D, Mk * D, s));
+    DetrAttnArgs da{};
+    half_t* b = (half_t*)c->h.p;
+    if (layout == 1) {
+        da.q = d16; da.k = d16 + Mq * D; da.v = d16 + (Mq + Mk) * D; da.ldq = da.ldk = da.ldv = D;
+    } else {      // columns q | k (| v) of one buffer
+        const int ld = layout == 0 ? 2 * D : 3 * D;
+        HG_HIP(hipMemcpy2DAsync(b, (size_t)ld * 2, d16, (size_t)D * 2, (size_t)D * 2, Mq, hipMemcpyDeviceToDevice, s));
+        HG_HIP(hipMemcpy2DAsync(b + D, (size_t)ld * 2, d16 + Mq * D, (size_t)D * 2, (size_t)D * 2, Mk, hipMemcpyDeviceToDevice, s));
+        da.q = b; da.k = b + D; da.ldq = da.ldk = ld;
+        if (layout == 2) {
+            HG_HIP(hipMemcpy2DAsync(b + 2 * D, (size_t)ld * 2, d16 + (Mq + Mk) * D, (size_t)D * 2, (size_t)D * 2, Mk, hipMemcpyDeviceToDevice, s));
+            da.v = b + 2 * D; da.ldv = ld;
+        } else {
+            da.v = d16 + (Mq + Mk) * D; da.ldv = D;
+        }
+    }
+    da.mask = mask; da.out = (half_t*)c->att.p; da.ldo = ldo; da.n_seq = n_seq; da.Lq = Lq; da.Lk = Lk; da.heads = heads; da.chunk = chunk;
+    da.waves = c->opt_detr_attn_waves;
+    if (da.waves == 3) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: option detr_attn_waves must be 0, 1, 2 or 4");
+    hipError_t e;
+    {
+        ProfScope ps(c, s, HG_PROF_ATTENTION, n_seq, Lk, heads);
+        e = launch_detr_attention(da, s);
+    }
+    if (e == hipErrorInvalidValue) return fail(c, HG_ERR_INVALID, "hg_test_detr_attention: refused by the launcher");
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_detr_attention: launch failed: %s", hipGetErrorString(e));
+    HG_HIP(launch_f16_to_f32((const half_t*)c->att.p, out, (Mq + 8) * ldo, s));
+    return HG_OK;
+}
+
 // One call of the fused in_proj + attention kernels, or of the two launches they replace, with the arguments production sets
 // (include/hoigen_amd.h has the contract; tests/test_gpu_qkv_attn_bound.py).  Every refusal is decided before anything is written.
 int hg_test_qkv_attn_ex(hg_ctx* c, const hg_test_qkv_attn_ex_args* x, void* stream) {

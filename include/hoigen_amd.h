@@ -480,6 +480,45 @@ typedef struct {
     float* clip;                       /* DEVICE fp32 [B, 3, clip_px, clip_px]; unused with clip_px 0 */
 } hg_detector_views_args;
 int hg_detector_views(hg_ctx*, const hg_detector_views_args* args, void* stream);
+
+/* ---- DETR transformer encoder (detr/models/transformer.py:62-83 TransformerEncoder over :127-162 TransformerEncoderLayer.forward_post;
+ * called from the detector at upt_tip_cache_model_free_finetune_distill3.py:1594-1605 through detr.py's transformer(...)) ---------------
+ * Six post-norm layers in the detector: q = k = src + pos, v = src, nn.MultiheadAttention with key_padding_mask (head dim 32), residual,
+ * norm1, linear1 -> ReLU -> linear2, residual, norm2.  Dropout is the identity (inference).
+ *
+ * hg_load_detr_encoder: per-layer device pointers with a dtype flag (state-dict keys layers.N.self_attn.in_proj_weight / in_proj_bias,
+ * self_attn.out_proj.weight / bias, linear1, linear2, norm1, norm2); the fp16 copies of the matrices are made here.  Accepted:
+ * 1 .. 12 layers, d_model = 32 * heads and a multiple of 128, d_ff a multiple of 128.  normalize_before != 0 (the pre-norm layer,
+ * transformer.py:164-176) and any activation but ReLU (activation != 0) are refused with a message: HG_ERR_INVALID. */
+typedef struct {
+    hg_tensor in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+        norm1_weight, norm1_bias, norm2_weight, norm2_bias;
+} hg_detr_layer_weights;
+typedef struct {
+    int32_t d_model, heads, d_ff, n_layers;
+    int32_t normalize_before;              /* must be 0 */
+    int32_t activation;                    /* 0 = relu; anything else is refused */
+    const hg_detr_layer_weights* layers;   /* HOST array [n_layers] */
+} hg_detr_encoder_weights;
+int hg_load_detr_encoder(hg_ctx*, const hg_detr_encoder_weights*);
+/* hg_detr_encoder (transformer.py:70-83 with mask = None and norm = None): src, pos (nullable: no positional embedding), out are DEVICE
+ * fp32 with element strides (batch, token, channel) - the reference's [S, B, C] layout is (C, B * C, 1), a batch-first [B, S, C] one
+ * (S * C, C, 1); the channel stride must be 1.  mask DEVICE uint8 [B, S], 1 = padded token (src_key_padding_mask), nullable.  Padded
+ * tokens are still queries and their rows are computed; an image without a visible token gets NaN rows, as nn.MultiheadAttention
+ * gives, and no other image is touched by them.  trace (nullable) DEVICE fp32 [n_layers, B * S, d_model]: the stream after every
+ * layer, batch-major.  src, pos, out and trace need no alignment beyond a float's.  Asynchronous on `stream`, no host wait; the workspace is grow-only: a steady-state call neither allocates nor
+ * synchronises.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message and nothing launched for B < 1, S < 1, S > 1792
+ * (hoigen_amd/csrc/hg_kernels.h: DETR_ATTN_MAX_L), B * S > 2^20, a channel stride other than 1 or a null src / out. */
+typedef struct {
+    const float* src;
+    const float* pos;
+    const uint8_t* mask;
+    float* out;
+    float* trace;
+    int32_t B, S;
+    int64_t src_stride[3], pos_stride[3], out_stride[3];      /* elements: batch, token, channel */
+} hg_detr_encoder_args;
+int hg_detr_encoder(hg_ctx*, const hg_detr_encoder_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -557,6 +596,13 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *   "mlp_pair_fault"  [HG_MLP_PAIR_FAULT]  test hook, default 0.  1: that launch goes out one workgroup short - a work slot nobody takes -, so that the
  *                      hand-off waits that depend on it meet their bound (~0.6 s), the results of the call are wrong and the NEXT call returns
  *                      HG_ERR_HIP (tests/test_gpu_scale.py exercises "an error, never a hang" with it, and the recovery once it is 0 again)
+ *   "detr_attn_chunk" [HG_DETR_ATTN_CHUNK] keys per LDS chunk of the DETR attention kernel (hoigen_amd/csrc/hg_detr_attn.hip): 0 (default) all keys
+ *                      of a (sequence, head) at once while they fit the 160 KiB (Lk <= 1 280), 512 beyond; otherwise a multiple of 32 up to
+ *                      1 280 (a value that is no multiple of 32 makes the calls that use it return HG_ERR_INVALID).  Every value gives the same bits.
+ *   "detr_attn_waves" [HG_DETR_ATTN_WAVES] query tiles per work item (= waves per workgroup) of that kernel: 0 (default) = 4, a 128-query slab; 1 or 2:
+ *                      smaller slabs, a wider grid (one image of 950 tokens: 240 or 120 workgroups instead of 64) that stages K and V more often -
+ *                      measured equal for one image and slower for a batch (profiles/detr_encoder.txt); 3 makes the calls that use it return
+ *                      HG_ERR_INVALID.  Every value gives the same bits.
  *   "chunk_rows"      [HG_CHUNK_ROWS]      rows per VAE / mlp_net / cache-logits chunk (>= 256; default 32768; the last chunk of a
  *                      call absorbs a tail of up to an eighth of it)
  * Unknown keys and out-of-range values return HG_ERR_INVALID. */
@@ -653,6 +699,17 @@ int hg_test_gemm_hilo(hg_ctx*, const float* a, const float* w, const float* bias
  * launch is recorded. */
 int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t* sel, int n_seq, int L, int heads,
                       int causal, float* out, void* stream);
+/* Test hook for the DETR attention kernel alone (hoigen_amd/csrc/hg_detr_attn.hip; the SDPA with key_padding_mask inside
+ * nn.MultiheadAttention at detr/models/transformer.py:155-156, head dim 32): q [n_seq*Lq, heads*32], k and v [n_seq*Lk, heads*32] fp32 on
+ * the device holding fp16 values (rounded to fp16 inside), mask uint8 [n_seq, Lk] (1 = padded key, nullable), out fp32
+ * [n_seq*Lq + 8, ldo] with ldo >= heads*32 a multiple of 8 (0 = heads*32): the kernel's whole output buffer with 8 canary rows behind
+ * it - whatever the kernel does not write (columns >= heads*32, the canary rows) comes back as 203.25.  chunk: keys per LDS chunk (-1: the
+ * context's option detr_attn_chunk).  layout 0: q | k in one [*, 2*heads*32] buffer and v in its own, as the encoder runs it (needs
+ * Lq == Lk); 1: q, k, v in three buffers; 2: one [*, 3*heads*32] buffer (needs Lq == Lk).  HG_ERR_INVALID with nothing written for
+ * Lq or Lk outside 1 .. 1792, a chunk that is no multiple of 32 or above 1 280, or a layout that needs Lq == Lk.  Under
+ * hg_profile_begin(HG_PROF_ATTENTION) the kernel launch is recorded. */
+int hg_test_detr_attention(hg_ctx*, const float* q, const float* k, const float* v, const uint8_t* mask, int n_seq, int Lq, int Lk,
+                           int heads, int chunk, int layout, int ldo, float* out, void* stream);
 
 /* Test hook for the fused in_proj + attention kernel (hoigen_amd/csrc/hg_qkv_attn.hip; the reference ops it replaces:
  * clipnet/model.py:171,181-183).  a [n_seq*L, D] fp32 (rounded to fp16 inside: the centred copy of the stream), w [3D, D] the
