@@ -170,6 +170,25 @@ class hg_detr_encoder_args(C.Structure):
                 ("src_stride", C.c_int64 * 3), ("pos_stride", C.c_int64 * 3), ("out_stride", C.c_int64 * 3)]
 
 
+_DETR_DEC_LAYER_FIELDS = _DETR_LAYER_FIELDS + ["cross_in_proj_weight", "cross_in_proj_bias", "cross_out_proj_weight", "cross_out_proj_bias",
+                                               "norm3_weight", "norm3_bias"]
+
+
+class hg_detr_dec_layer_weights(C.Structure):
+    _fields_ = [(n, hg_tensor) for n in _DETR_DEC_LAYER_FIELDS]
+
+
+class hg_detr_decoder_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "heads", "d_ff", "n_layers", "normalize_before", "activation")] + \
+               [("norm_weight", hg_tensor), ("norm_bias", hg_tensor), ("layers", C.POINTER(hg_detr_dec_layer_weights))]
+
+
+class hg_detr_decoder_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("tgt", "query_pos", "memory", "pos", "memory_mask", "out", "trace")] + \
+               [(n, C.c_int32) for n in ("B", "S", "Q", "return_intermediate")] + \
+               [(n, C.c_int64 * 3) for n in ("tgt_stride", "query_pos_stride", "memory_stride", "pos_stride")] + [("out_stride", C.c_int64 * 4)]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -189,6 +208,7 @@ class hg_test_elem_args(C.Structure):
 
 
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
+HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS = 104, 105
 
 _P = C.c_void_p
 _I = C.c_int
@@ -229,6 +249,8 @@ SIGNATURES = {
     "hg_detector_views": (_I, [_P, C.POINTER(hg_detector_views_args), _P]),
     "hg_load_detr_encoder": (_I, [_P, C.POINTER(hg_detr_encoder_weights)]),
     "hg_detr_encoder": (_I, [_P, C.POINTER(hg_detr_encoder_args), _P]),
+    "hg_load_detr_decoder": (_I, [_P, C.POINTER(hg_detr_decoder_weights)]),
+    "hg_detr_decoder": (_I, [_P, C.POINTER(hg_detr_decoder_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -237,6 +259,7 @@ SIGNATURES = {
     "hg_test_gemm_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hg_test_detr_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "hg_test_detr_ffn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "hg_test_qkv_attn": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hg_test_qkv_attn_ex": (_I, [_P, C.POINTER(hg_test_qkv_attn_ex_args), _P]),
     "hg_test_gemm_hilo": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

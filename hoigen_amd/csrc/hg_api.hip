@@ -38,6 +38,8 @@ const Option OPTIONS[] = {
     {"mlp_pair256_launches", "HG_MLP_PAIR256_LAUNCHES", &hg_ctx::n_pair256_launches, false, 0, INT_MAX, ">= 0"},      // (a counter: see the header)
     {"detr_attn_chunk", "HG_DETR_ATTN_CHUNK", &hg_ctx::opt_detr_attn_chunk, false, 0, 1280, "0 .. 1280 (a multiple of 32)"},
     {"detr_attn_waves", "HG_DETR_ATTN_WAVES", &hg_ctx::opt_detr_attn_waves, false, 0, 4, "0, 1, 2 or 4"},
+    {"detr_ffn", "HG_DETR_FFN", &hg_ctx::opt_detr_ffn, false, 0, 2, "0, 1 or 2"},
+    {"detr_ffn_max_m", "HG_DETR_FFN_MAX_M", &hg_ctx::opt_detr_ffn_max_m, false, 0, 1 << 20, "0 .. 2^20"},
     {"mlp_pair_fault", "HG_MLP_PAIR_FAULT", &hg_ctx::opt_mlp_pair_fault, false, 0, 1, "0 or 1"},
 };
 const Option* find_option(const char* key) {
@@ -108,6 +110,7 @@ void hg_destroy(hg_ctx* c) {
     for (auto& m : c->cache) free_all(m.owned);
     for (auto& m : c->prior) free_all(m.owned);
     free_all(c->detr.owned);
+    free_all(c->detr_dec.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

@@ -145,6 +145,19 @@ struct DetrEnc {         // hg_load_detr_encoder
     std::vector<DetrLayerW> layers;
     std::vector<void*> owned;
 };
+struct DetrDecLayerW {   // one post-norm decoder layer (transformer.py:187-233): the encoder layer's tensors, multihead_attn's q rows and out_proj, norm3
+    DetrLayerW sa;
+    half_t *wq_c, *w_out_c;
+    float *bq_c, *b_out_c, *n3_w, *n3_b;
+};
+struct DetrDec {         // hg_load_detr_decoder
+    bool loaded = false;
+    int D = 0, heads = 0, F = 0;
+    std::vector<DetrDecLayerW> layers;
+    half_t *wk_all = nullptr, *wv_all = nullptr;      // [n_layers * D, D]: the K / V rows of every layer's multihead_attn.in_proj_weight
+    float *bk_all = nullptr, *bv_all = nullptr, *nf_w = nullptr, *nf_b = nullptr;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -158,6 +171,7 @@ struct hg_ctx {
     Cache cache[HG_MAX_CACHE_SLOTS];
     Priors prior[HG_MAX_PRIOR_SLOTS];
     DetrEnc detr;
+    DetrDec detr_dec;
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
@@ -170,6 +184,7 @@ struct hg_ctx {
     Buf det;             // hg_hoi_detections: row counts, workgroup sums, and the entry arrays the association reads where the caller does not ask for them
     Buf prebatch;        // hg_preprocess_batch: per-crop headers and weight tables, sized from n and n_px alone
     Buf detr_ws;         // hg_detr_encoder: the fp32 stream, the batch-major pos, and the fp16 operands x, x + pos, q | k, v, attention output, FFN hidden
+    Buf detr_dec_ws;     // hg_detr_decoder: memory's fp16 copies and every layer's cross-attention K and V, the decoder stream and its fp16 operands, the split FFN's partial sums
     Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
@@ -211,6 +226,10 @@ struct hg_ctx {
                                  // record is the pair launch's, so this is how a caller tells which kernel ran)
     int opt_detr_attn_chunk = 0;     // hg_detr_attn.hip: keys per LDS chunk (0: all keys at once while they fit, 512 beyond; else a multiple of 32 up to 1 280).  Same bits
     int opt_detr_attn_waves = 0;     // ... query tiles per slab = waves per workgroup: 0 = 4 (measured best or equal in every case: profiles/detr_encoder.txt), else 1, 2 or 4.  Same bits
+    int opt_detr_ffn = 0;            // FFN of a DETR decoder layer: 0 the split-over-d_ff kernel (hg_detr_ffn.hip) up to opt_detr_ffn_max_m rows where the shape allows,
+                                     // 1 the two GEMMs, 2 the split kernel or HG_ERR_INVALID
+    int opt_detr_ffn_max_m = 1000;   // ... rows (B * Q) up to which 0 picks the split kernel: it wins by 25 - 31 us a layer from 100 to 950 rows; at 2 888 rows
+                                     // by 7 us, which is the spread of repeated runs (profiles/detr_decoder.txt)
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
     int n_cu = 256;
     // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became
@@ -238,7 +257,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws}
+     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

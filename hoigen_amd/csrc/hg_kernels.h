@@ -173,6 +173,28 @@ hipError_t launch_detr_postnorm(float* x, const float* w, const float* b, const 
 // exit: out[b * ob + t * os + c] = x[(b * S + t) * D + c]
 hipError_t launch_detr_exit(const float* x, float* out, long long ob, long long os, int B, int S, int D, hipStream_t s);
 
+// ---- row kernels of the DETR decoder (hg_detr_rows.hip) ------------------------------------------------------------------------------
+// entry: x fp32 [B*Q, D] (batch-major) = tgt (null: zeros, nothing is read), x16 = fp16(x), xp16 = fp16(x + query_pos), qposb =
+// query_pos batch-major; tgt / query_pos element (b, q, ch) at b * stride_b + q * stride_q + ch (a batch stride of 0 broadcasts)
+hipError_t launch_detr_dec_entry(const float* tgt, long long tb, long long tq, const float* qpos, long long qb, long long qq, int B, int Q,
+                                 int D, float* x, half_t* x16, half_t* xp16, float* qposb, hipStream_t s);
+// tail of a decoder layer: x = LayerNorm(((x + b2) + partial[0]) + ... + partial[n_slices - 1]; w3, b3) in place - b2 nullable (not
+// added: the residual GEMM added it), partial [n_slices][M][D] fp32 in ascending slice order, n_slices >= 0 -, x16 = fp16(x), xp16 =
+// fp16(x + qposb) (nullable), copy = x (nullable, 4-byte alignment), and with out: out[(row / Q) * ob + (row % Q) * oq + ch] =
+// LayerNorm(x; wf, bf), which does not go back into the stream.  D a multiple of 4 up to 512
+hipError_t launch_detr_dec_tail(float* x, const float* b2, const float* partial, int n_slices, const float* w3, const float* b3,
+                                const float* qposb, half_t* x16, half_t* xp16, float* copy, const float* wf, const float* bf, float* out,
+                                long long ob, long long oq, int Q, int M, int D, hipStream_t s);
+
+// ---- the FFN of a short stream split over d_ff (hg_detr_ffn.hip): partial[slice][m][:] = fp16(relu(x16 W1[slice]^T + b1[slice])) W2[:, slice]^T
+// x16 [M, D] fp16, W1 [F, D], W2 [D, F] fp16, b1 [F] fp32 (16-byte aligned); partial fp32 [F / DETR_FFN_SLICE][M][D]: exactly those
+// bytes are written.  D = 128 or 256, F a multiple of DETR_FFN_SLICE up to 8192; otherwise hipErrorInvalidValue and nothing launched
+static constexpr int DETR_FFN_ROWS = 32, DETR_FFN_SLICE = 128;
+bool detr_ffn_ok(int M, int D, int F);
+inline size_t detr_ffn_partial_bytes(int M, int D, int F) { return (size_t)(F / DETR_FFN_SLICE) * M * D * 4; }
+hipError_t launch_detr_ffn(const half_t* x16, const half_t* W1, const float* b1, const half_t* W2, float* partial, int M, int D, int F,
+                           hipStream_t s);
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

@@ -336,6 +336,50 @@ int hg_test_detr_attention(hg_ctx* c, const float* q, const float* k, const floa
     return HG_OK;
 }
 
+// The FFN of a DETR decoder layer with its tail (hg_detr_ffn.hip or the two GEMMs, then detr_dec_tail_kernel), as hg_detr_decoder runs
+// it (include/hoigen_amd.h has the contract; tests/test_gpu_detr_ffn.py).  Every refusal is decided before anything is written.
+int hg_test_detr_ffn(hg_ctx* c, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* norm_w,
+                     const float* norm_b, int M, int D, int F, float* y, float* partials, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x || !w1 || !b1 || !w2 || !b2 || !norm_w || !norm_b || !y) return fail(c, HG_ERR_INVALID, "hg_test_detr_ffn: every input and y are required");
+    if (M < 1 || M > (1 << 20) || D < 128 || D % 128 || D > 512 || F < 128 || F % 128)
+        return fail(c, HG_ERR_INVALID, "hg_test_detr_ffn: 1 <= M <= 2^20, D a multiple of 128 up to 512, F a multiple of 128 (got %d, %d, %d)", M, D, F);
+    const bool fits = detr_ffn_ok(M, D, F);
+    if (c->opt_detr_ffn == 2 && !fits) return fail(c, HG_ERR_INVALID, "hg_test_detr_ffn: option detr_ffn = 2, and the split kernel does not cover this shape");
+    const bool split = c->opt_detr_ffn == 2 || (c->opt_detr_ffn == 0 && fits && M <= c->opt_detr_ffn_max_m);
+    if (partials && !split) return fail(c, HG_ERR_INVALID, "hg_test_detr_ffn: partials exist on the split kernel's path only");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t Mp = rup(M, 256), n_sl = F / DETR_FFN_SLICE;
+    const size_t o_w1 = 0, o_w2 = o_w1 + (size_t)F * D * 2, o_x = o_w2 + (size_t)F * D * 2, o_x16 = o_x + Mp * D * 4, o_x16o = o_x16 + Mp * D * 2,
+                 o_ff = o_x16o + Mp * D * 2, total = o_ff + std::max(Mp * F * 2, rup(detr_ffn_partial_bytes(M, D, F), 256));
+    int rc = ensure(c, c->cx, total);
+    if (rc) return rc;
+    char* ws = (char*)c->cx.p;
+    half_t *w1h = (half_t*)(ws + o_w1), *w2h = (half_t*)(ws + o_w2), *x16 = (half_t*)(ws + o_x16), *x16o = (half_t*)(ws + o_x16o), *ff = (half_t*)(ws + o_ff);
+    float *xs = (float*)(ws + o_x), *part = (float*)(ws + o_ff);
+    HG_HIP(launch_f32_to_f16(w1, w1h, (size_t)F * D, s));
+    HG_HIP(launch_f32_to_f16(w2, w2h, (size_t)F * D, s));
+    HG_HIP(launch_f32_to_f16(x, x16, (size_t)M * D, s));
+    HG_HIP(hipMemcpyAsync(xs, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    if (split) {
+        ProfScope ps(c, s, HG_PROF_DETR_FFN, M, F, D);
+        HG_HIP(launch_detr_ffn(x16, w1h, b1, w2h, part, M, D, F, s));
+        ps.finish();
+        if (partials) HG_HIP(hipMemcpyAsync(partials, part, n_sl * M * D * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+        HG_HIP(gemm(c, EPI_BIAS_RELU_F16, gemm_args(x16, D, w1h, b1, ff, F, M, F, D), s));
+        HG_HIP(gemm(c, EPI_BIAS_RESID_F32, gemm_args(ff, F, w2h, b2, xs, D, M, D, F), s));
+    }
+    {
+        ProfScope ps(c, s, HG_PROF_DETR_ROWS, M, D, split ? (int)n_sl : 0);
+        HG_HIP(launch_detr_dec_tail(xs, split ? b2 : nullptr, split ? part : nullptr, split ? (int)n_sl : 0, norm_w, norm_b, nullptr, x16o, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, 0, 0, 1, M, D, s));
+    }
+    HG_HIP(hipMemcpyAsync(y, xs, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    return HG_OK;
+}
+
 // One call of the fused in_proj + attention kernels, or of the two launches they replace, with the arguments production sets
 // (include/hoigen_amd.h has the contract; tests/test_gpu_qkv_attn_bound.py).  Every refusal is decided before anything is written.
 int hg_test_qkv_attn_ex(hg_ctx* c, const hg_test_qkv_attn_ex_args* x, void* stream) {

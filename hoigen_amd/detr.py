@@ -1,10 +1,12 @@
-"""DETR transformer encoder façade: the reference's ``TransformerEncoder`` (detr/models/transformer.py:62-83 over the post-norm
-``TransformerEncoderLayer`` :127-162) with the same state-dict keys and call signature, running on the HIP kernels
-(hoigen_amd/csrc/hg_detr.hip: hg_load_detr_encoder, hg_detr_encoder).
+"""DETR transformer façade: the reference's ``Transformer``, ``TransformerEncoder`` and ``TransformerDecoder``
+(detr/models/transformer.py:18-124 over the post-norm layers :127-162 and :187-233) with the same state-dict keys and call signatures,
+running on the HIP kernels (hoigen_amd/csrc/hg_detr.hip: hg_load_detr_encoder, hg_detr_encoder; hg_detr_dec.hip: hg_load_detr_decoder,
+hg_detr_decoder).
 
-    self.detector.transformer.encoder = TransformerEncoder.from_module(self.detector.transformer.encoder)
+    self.detector.transformer = Transformer.from_module(self.detector.transformer)
 
-is the whole integration.  Inference only; tensors must live on a HIP device.
+is the whole integration; the two halves can be swapped on their own as well.  Inference only; tensors must live on a
+HIP device.
 """
 from __future__ import annotations
 
@@ -156,3 +158,220 @@ class TransformerEncoder(nn.Module):
         """(output [S, B, C], trace [num_layers, B * S, C]: the stream after every layer, batch-major) - for the tests.  ``out``: an fp32
         [S, B, C] tensor or view to write into (e.g. the permuted view of a batch-first buffer); ``trace``: a contiguous buffer to write the trace into."""
         return self._run(src, mask, src_key_padding_mask, pos, True, out, trace)
+
+
+class TransformerDecoderLayer(nn.Module):
+    """Parameters of detr/models/transformer.py:187-204 (dropout is the identity at inference and holds none)."""
+
+    def __init__(self, d_model: int, nhead: int, dim_feedforward: int = 2048):
+        super().__init__()
+        self.self_attn = MultiheadAttention(d_model, nhead)
+        self.multihead_attn = MultiheadAttention(d_model, nhead)
+        self.linear1 = Linear(d_model, dim_feedforward)
+        self.linear2 = Linear(dim_feedforward, d_model)
+        self.norm1 = LayerNorm(d_model)
+        self.norm2 = LayerNorm(d_model)
+        self.norm3 = LayerNorm(d_model)
+
+
+class TransformerDecoder(nn.Module):
+    """detr/models/transformer.py:86-124.  ``forward(tgt, memory, ..., memory_key_padding_mask, pos, query_pos)`` on ``[Q, B, C]`` /
+    ``[S, B, C]`` tensors returns ``[L, Q, B, C]`` fp32 with ``return_intermediate`` and ``[1, Q, B, C]`` without.  Post-norm ReLU layers
+    with the final norm - what the detector builds (transformer.py:31-35); anything else is refused."""
+
+    def __init__(self, d_model: int = 256, nhead: int = 8, num_layers: int = 6, dim_feedforward: int = 2048,
+                 return_intermediate: bool = False):
+        super().__init__()
+        self.d_model, self.nhead, self.num_layers, self.dim_feedforward = d_model, nhead, num_layers, dim_feedforward
+        self.layers = nn.ModuleList([TransformerDecoderLayer(d_model, nhead, dim_feedforward) for _ in range(num_layers)])
+        self.norm = LayerNorm(d_model)
+        self.return_intermediate = bool(return_intermediate)
+        self._ctx = _Ctx()
+        self._sig = None
+
+    @classmethod
+    def from_module(cls, decoder: nn.Module) -> "TransformerDecoder":
+        """From the reference's TransformerDecoder (or any module with its attributes and state-dict keys ``layers.N.self_attn.*``,
+        ``multihead_attn.*``, ``linear1``, ``linear2``, ``norm1`` .. ``norm3`` and ``norm``)."""
+        if getattr(decoder, "norm", None) is None:
+            raise RuntimeError("hoigen_amd: TransformerDecoder.from_module: the decoder has no final norm (norm is None); the detector's "
+                               "decoder has one (transformer.py:33) and only that form is implemented")
+        layers = list(decoder.layers)
+        if not layers:
+            raise RuntimeError("hoigen_amd: TransformerDecoder.from_module: the decoder has no layers")
+        for i, l in enumerate(layers):
+            if getattr(l, "normalize_before", False):
+                raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: layers.{i} is pre-norm (normalize_before); only the post-norm "
+                                   "layer (transformer.py:212-233) is implemented")
+            act = getattr(l, "activation", torch.nn.functional.relu)
+            if not _is_relu(act):
+                raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: layers.{i} uses activation {act!r}; only ReLU is implemented")
+        w = layers[0].self_attn.in_proj_weight
+        d_model, nhead, d_ff = int(w.shape[1]), int(layers[0].self_attn.num_heads), int(layers[0].linear1.weight.shape[0])
+        m = cls(d_model, nhead, len(layers), d_ff, bool(getattr(decoder, "return_intermediate", False)))
+        missing, unexpected = m.load_state_dict(decoder.state_dict(), strict=False)
+        if missing or unexpected:
+            raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: state-dict keys differ (missing {missing}, unexpected {unexpected})")
+        m.to(device=w.device, dtype=w.dtype)
+        m.train(decoder.training)
+        return m
+
+    def set_option(self, key: str, value: int) -> None:
+        """Behaviour option of this module's native context (include/hoigen_amd.h), e.g. ``detr_ffn``, ``detr_attn_chunk``."""
+        self._ctx.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self._ctx.get_option(key)
+
+    def _load(self, device: torch.device) -> int:
+        h = self._ctx.get(device)
+        sig = (h, _sig(self.parameters()))
+        if sig != self._sig:
+            t = _lib.tensor
+            arr = (_lib.hg_detr_dec_layer_weights * self.num_layers)()
+            for i, l in enumerate(self.layers):
+                arr[i] = _lib.hg_detr_dec_layer_weights(
+                    t(l.self_attn.in_proj_weight), t(l.self_attn.in_proj_bias), t(l.self_attn.out_proj.weight), t(l.self_attn.out_proj.bias),
+                    t(l.linear1.weight), t(l.linear1.bias), t(l.linear2.weight), t(l.linear2.bias), t(l.norm1.weight), t(l.norm1.bias),
+                    t(l.norm2.weight), t(l.norm2.bias), t(l.multihead_attn.in_proj_weight), t(l.multihead_attn.in_proj_bias),
+                    t(l.multihead_attn.out_proj.weight), t(l.multihead_attn.out_proj.bias), t(l.norm3.weight), t(l.norm3.bias))
+            norm = self.norm
+            w = _lib.hg_detr_decoder_weights(self.d_model, self.nhead, self.dim_feedforward, self.num_layers, 0, 0,
+                                             t(norm.weight if norm is not None else None), t(norm.bias if norm is not None else None), arr)
+            self._ctx.check(_lib.lib().hg_load_detr_decoder(h, C.byref(w)), "hg_load_detr_decoder")
+            self._sig = sig
+        return h
+
+    def _run(self, tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask, memory_key_padding_mask, pos, query_pos, want_trace: bool,
+             out: Optional[torch.Tensor] = None):
+        for name, m in (("tgt_mask", tgt_mask), ("memory_mask", memory_mask), ("tgt_key_padding_mask", tgt_key_padding_mask)):
+            if m is not None:
+                raise RuntimeError(f"hoigen_amd: TransformerDecoder: `{name}` is not implemented; the detector passes None "
+                                   "(detr/models/transformer.py:57-58) and masks padding with memory_key_padding_mask")
+        _require_cuda(memory, "TransformerDecoder memory")
+        D = self.d_model
+        if memory.dim() != 3 or memory.shape[2] != D:
+            raise RuntimeError(f"hoigen_amd: TransformerDecoder: memory must be [S, B, {D}] (got {tuple(memory.shape)})")
+        S, B, _ = memory.shape
+        dev = memory.device
+
+        def f32(t):      # fp32 with a channel stride of 1 (a permuted view of a batch-first buffer passes as it is)
+            t = t.detach()
+            return t if t.dtype == torch.float32 and t.stride(-1) == 1 else t.to(torch.float32).contiguous()
+
+        if query_pos is None:
+            if tgt is None:
+                raise RuntimeError("hoigen_amd: TransformerDecoder: tgt and query_pos are both None: the number of queries is unknown")
+            query_pos = torch.zeros(tgt.shape[0], D, device=dev)
+        _require_cuda(query_pos, "TransformerDecoder query_pos")
+        qp = f32(query_pos)
+        if qp.dim() not in (2, 3) or qp.shape[-1] != D or (qp.dim() == 3 and qp.shape[1] != B):
+            raise RuntimeError(f"hoigen_amd: TransformerDecoder: query_pos must be [Q, {D}] or [Q, B = {B}, {D}] (got {tuple(qp.shape)})")
+        Q = int(qp.shape[0])
+        h = self._load(dev)
+        a = _lib.hg_detr_decoder_args()
+        a.query_pos = qp.data_ptr()
+        a.query_pos_stride[:] = [qp.stride(1) if qp.dim() == 3 else 0, qp.stride(0), 1]
+        tg = None
+        if tgt is not None:
+            _require_cuda(tgt, "TransformerDecoder tgt")
+            if tuple(tgt.shape) != (Q, B, D):
+                raise RuntimeError(f"hoigen_amd: TransformerDecoder: tgt must be [Q, B, C] = [{Q}, {B}, {D}] (got {tuple(tgt.shape)})")
+            tg = f32(tgt)
+            a.tgt = tg.data_ptr()
+            a.tgt_stride[:] = [tg.stride(1), tg.stride(0), 1]
+        mem = f32(memory)
+        a.memory = mem.data_ptr()
+        a.memory_stride[:] = [mem.stride(1), mem.stride(0), 1]
+        p = None
+        if pos is not None:
+            _require_cuda(pos, "TransformerDecoder pos")
+            p = f32(pos).expand(S, B, D)
+            a.pos = p.data_ptr()
+            a.pos_stride[:] = [p.stride(1), p.stride(0), 1]
+        kpm = None
+        if memory_key_padding_mask is not None:
+            _require_cuda(memory_key_padding_mask, "TransformerDecoder memory_key_padding_mask")
+            if tuple(memory_key_padding_mask.shape) != (B, S):
+                raise RuntimeError(f"hoigen_amd: TransformerDecoder: memory_key_padding_mask must be [B, S] = [{B}, {S}] "
+                                   f"(got {tuple(memory_key_padding_mask.shape)})")
+            kpm = memory_key_padding_mask.detach().to(torch.uint8).contiguous()
+            a.memory_mask = kpm.data_ptr()
+        L = self.num_layers if self.return_intermediate else 1
+        if out is None:
+            out = torch.empty(L, Q, B, D, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (L, Q, B, D) or out.dtype != torch.float32 or out.stride(3) != 1 or out.device != dev:
+            raise RuntimeError("hoigen_amd: TransformerDecoder: out must be an fp32 [L, Q, B, C] tensor (or view) on memory's device with channel stride 1")
+        trace = torch.empty(self.num_layers, B * Q, D, device=dev, dtype=torch.float32) if want_trace else None
+        a.out, a.trace = out.data_ptr(), (trace.data_ptr() if trace is not None else None)
+        a.out_stride[:] = [out.stride(0), out.stride(2), out.stride(1), 1]
+        a.B, a.S, a.Q, a.return_intermediate = B, S, Q, int(self.return_intermediate)
+        self._ctx.check(_lib.lib().hg_detr_decoder(h, C.byref(a), _stream_ptr(dev)), "hg_detr_decoder")
+        return out, trace
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, tgt, memory, tgt_mask: Optional[torch.Tensor] = None, memory_mask: Optional[torch.Tensor] = None,
+                tgt_key_padding_mask: Optional[torch.Tensor] = None, memory_key_padding_mask: Optional[torch.Tensor] = None,
+                pos: Optional[torch.Tensor] = None, query_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._run(tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask, memory_key_padding_mask, pos, query_pos, False)[0]
+
+    @_inference_only
+    @torch.no_grad()
+    def forward_trace(self, tgt, memory, tgt_mask=None, memory_mask=None, tgt_key_padding_mask=None, memory_key_padding_mask=None, pos=None,
+                      query_pos=None, out=None):
+        """(hs [L, Q, B, C], trace [num_layers, B * Q, C]: the stream after every layer - after norm3, before the final norm -,
+        batch-major) - for the tests.  ``tgt`` may be None (zeros, nothing read); ``out``: an fp32 [L, Q, B, C] tensor or view to write into."""
+        return self._run(tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask, memory_key_padding_mask, pos, query_pos, True, out)
+
+
+class Transformer(nn.Module):
+    """detr/models/transformer.py:18-59: ``forward(src [B, C, H, W], mask [B, H, W], query_embed [Q, C], pos_embed [B, C, H, W])`` returns
+    ``(hs [L, B, Q, C], memory [B, C, H, W])``.  Both halves share one native context.  src and pos_embed are channel-major maps and the
+    native calls want a channel stride of 1: each is transposed to [B, S, C] once (pos_embed once for both halves); memory travels from the
+    encoder to the decoder as a [B, S, C] buffer through strides, hs is written in [L, B, Q, C] order, and the returned memory is the
+    [B, C, H, W] view of that buffer, as the reference's is of its own."""
+
+    def __init__(self, d_model: int = 256, nhead: int = 8, num_encoder_layers: int = 6, num_decoder_layers: int = 6,
+                 dim_feedforward: int = 2048, return_intermediate_dec: bool = False):
+        super().__init__()
+        self.encoder = TransformerEncoder(d_model, nhead, num_encoder_layers, dim_feedforward)
+        self.decoder = TransformerDecoder(d_model, nhead, num_decoder_layers, dim_feedforward, return_intermediate_dec)
+        self.decoder._ctx = self.encoder._ctx
+        self.d_model, self.nhead = d_model, nhead
+
+    @classmethod
+    def from_module(cls, transformer: nn.Module) -> "Transformer":
+        enc, dec = TransformerEncoder.from_module(transformer.encoder), TransformerDecoder.from_module(transformer.decoder)
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.encoder, m.decoder = enc, dec
+        dec._ctx = enc._ctx
+        m.d_model, m.nhead = enc.d_model, enc.nhead
+        m.train(transformer.training)
+        return m
+
+    def set_option(self, key: str, value: int) -> None:
+        self.encoder.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self.encoder.get_option(key)
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, src, mask, query_embed, pos_embed):
+        _require_cuda(src, "Transformer src")
+        if src.dim() != 4 or src.shape[1] != self.d_model or pos_embed.shape != src.shape:
+            raise RuntimeError(f"hoigen_amd: Transformer: src and pos_embed must be [B, {self.d_model}, H, W] (got {tuple(src.shape)}, "
+                               f"{tuple(pos_embed.shape)})")
+        B, Cc, H, W = src.shape
+        S = H * W
+        src_s = src.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous().permute(1, 0, 2)          # [S, B, C] views of
+        pos_s = pos_embed.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous().permute(1, 0, 2)    # [B, S, C] buffers
+        kpm = mask.flatten(1) if mask is not None else None
+        mem = torch.empty(B, S, Cc, device=src.device, dtype=torch.float32)
+        self.encoder._run(src_s, None, kpm, pos_s, False, mem.permute(1, 0, 2))
+        L = self.decoder.num_layers if self.decoder.return_intermediate else 1
+        hs = torch.empty(L, B, query_embed.shape[0], Cc, device=src.device, dtype=torch.float32)
+        self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
+        return hs, mem.permute(0, 2, 1).view(B, Cc, H, W)

@@ -519,6 +519,54 @@ typedef struct {
     int64_t src_stride[3], pos_stride[3], out_stride[3];      /* elements: batch, token, channel */
 } hg_detr_encoder_args;
 int hg_detr_encoder(hg_ctx*, const hg_detr_encoder_args* args, void* stream);
+
+/* ---- DETR transformer decoder (detr/models/transformer.py:86-124 TransformerDecoder over :212-233 TransformerDecoderLayer.forward_post;
+ * the second half of the detector's transformer(...) call, transformer.py:56-58) ----------------------------------------------------------
+ * Per layer: q = k = tgt + query_pos, v = tgt, self-attention, residual, norm1; cross-attention with q = tgt + query_pos, k = memory +
+ * pos, v = memory under memory_key_padding_mask, residual, norm2; linear1 -> ReLU -> linear2, residual, norm3.  The decoder's final
+ * norm is applied to what leaves (every layer with return_intermediate, else the last), never to the stream.
+ *
+ * hg_load_detr_decoder: a slot of its own (a context may hold an encoder, a decoder or both).  A layer is the encoder layer's twelve
+ * tensors, multihead_attn's four and norm3; refused (HG_ERR_INVALID with a message) as by hg_load_detr_encoder, and where the final
+ * norm is missing.  The K rows of every layer's multihead_attn.in_proj_weight are kept as ONE fp16 [n_layers * d_model, d_model] matrix
+ * and the V rows likewise: memory is the same for every layer, so a call computes all cross-attention keys and values in two GEMMs. */
+typedef struct {
+    hg_tensor in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+        norm1_weight, norm1_bias, norm2_weight, norm2_bias;       /* self_attn.*, linear1, linear2, norm1, norm2 */
+    hg_tensor cross_in_proj_weight, cross_in_proj_bias, cross_out_proj_weight, cross_out_proj_bias;      /* multihead_attn.* */
+    hg_tensor norm3_weight, norm3_bias;
+} hg_detr_dec_layer_weights;
+typedef struct {
+    int32_t d_model, heads, d_ff, n_layers;
+    int32_t normalize_before;              /* must be 0 */
+    int32_t activation;                    /* 0 = relu; anything else is refused */
+    hg_tensor norm_weight, norm_bias;      /* the decoder's final norm: required */
+    const hg_detr_dec_layer_weights* layers;   /* HOST array [n_layers] */
+} hg_detr_decoder_weights;
+int hg_load_detr_decoder(hg_ctx*, const hg_detr_decoder_weights*);
+/* hg_detr_decoder: DEVICE fp32 tensors with element strides.  tgt [B, Q, C] (batch, query, channel), nullable = zeros (what the detector
+ * passes; nothing is read then); query_pos likewise, required, a batch stride of 0 broadcasts a [Q, C] embedding; memory and pos
+ * (nullable) [B, S, C] (batch, token, channel) as in hg_detr_encoder_args; memory_mask uint8 [B, S], 1 = padded token, nullable;
+ * out (layer, batch, query, channel): layers 0 .. n_layers - 1 with return_intermediate, else the last layer at layer index 0 and
+ * nothing else.  trace (nullable) fp32 [n_layers, B * Q, d_model]: the stream after every layer (after norm3), batch-major.  An image
+ * whose memory is all padding gets NaN in its own queries, as nn.MultiheadAttention gives, and no other image is touched.
+ * Asynchronous on `stream`, no host wait; the workspace is grow-only.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message
+ * and nothing launched for B, S or Q below 1, S or Q above 1792, B * max(S, Q) > 2^20, a channel stride other than 1, a null memory,
+ * query_pos or out, and for option detr_ffn = 2 on a shape the split kernel does not cover. */
+typedef struct {
+    const float* tgt;
+    const float* query_pos;
+    const float* memory;
+    const float* pos;
+    const uint8_t* memory_mask;
+    float* out;
+    float* trace;
+    int32_t B, S, Q, return_intermediate;
+    int64_t tgt_stride[3], query_pos_stride[3];            /* elements: batch, query, channel */
+    int64_t memory_stride[3], pos_stride[3];               /* elements: batch, token, channel */
+    int64_t out_stride[4];                                 /* elements: layer, batch, query, channel */
+} hg_detr_decoder_args;
+int hg_detr_decoder(hg_ctx*, const hg_detr_decoder_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -603,6 +651,11 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      smaller slabs, a wider grid (one image of 950 tokens: 240 or 120 workgroups instead of 64) that stages K and V more often -
  *                      measured equal for one image and slower for a batch (profiles/detr_encoder.txt); 3 makes the calls that use it return
  *                      HG_ERR_INVALID.  Every value gives the same bits.
+ *   "detr_ffn"        [HG_DETR_FFN]        the FFN of a DETR decoder layer: 0 (default) the split-over-d_ff kernel (hoigen_amd/csrc/hg_detr_ffn.hip) where the
+ *                      shape allows (d_model 128 or 256) and the call has at most detr_ffn_max_m rows, the two GEMMs elsewhere; 1 always the two
+ *                      GEMMs; 2 always the split kernel (a shape it does not cover: HG_ERR_INVALID).  hg_detr_encoder never uses it.
+ *   "detr_ffn_max_m"  [HG_DETR_FFN_MAX_M]  rows (B * Q) up to which detr_ffn = 0 picks the split kernel (default 1000: measured faster by 25 - 31 us a layer
+ *                      from 100 to 950 rows, by no more than the spread of repeated runs at 2 888: profiles/detr_decoder.txt)
  *   "chunk_rows"      [HG_CHUNK_ROWS]      rows per VAE / mlp_net / cache-logits chunk (>= 256; default 32768; the last chunk of a
  *                      call absorbs a tail of up to an eighth of it)
  * Unknown keys and out-of-range values return HG_ERR_INVALID. */
@@ -624,7 +677,9 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_ATTENTION 100 /* M = sequences, N = tokens per sequence, K = heads */
 #define HG_PROF_QKV_ATTN 101  /* fused in_proj + attention: M = sequences, N = tokens per sequence, K = heads */
 #define HG_PROF_VAE_FUSED 102 /* CoOp-VAE as one kernel: M = rows, N = passes per item (3 Encoder + Generator, 2 Encoder, 1 Generator), K = hidden width of the first pass */
-#define HG_PROF_MLP_PAIR 103  /* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
+#define HG_PROF_DETR_FFN 104  /* the DETR decoder's split FFN kernel: M = rows, N = d_ff, K = d_model */
+#define HG_PROF_DETR_ROWS 105 /* row kernels of hg_detr_decoder (entries, post-norms, tails): M = rows, N = d_model, K = slices summed */
+#define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
     int32_t M, N, K;
@@ -710,6 +765,16 @@ int hg_test_attention(hg_ctx*, const float* qkv, const float* q0, const int32_t*
  * hg_profile_begin(HG_PROF_ATTENTION) the kernel launch is recorded. */
 int hg_test_detr_attention(hg_ctx*, const float* q, const float* k, const float* v, const uint8_t* mask, int n_seq, int Lq, int Lk,
                            int heads, int chunk, int layout, int ldo, float* out, void* stream);
+/* Test hook for the FFN of a DETR decoder layer with its tail (hoigen_amd/csrc/hg_detr_ffn.hip and detr_dec_tail_kernel;
+ * transformer.py:231-233): y = LayerNorm(x + linear2(relu(linear1(x)))) for x [M, D] fp32 on the device, w1 [F, D], b1 [F], w2 [D, F],
+ * b2 [D], norm_w / norm_b [D] fp32 (matrices and fp16(x) rounded inside, as the decoder holds them).  Option detr_ffn picks the path as
+ * in hg_detr_decoder (0: the default rule; 1: the two GEMMs; 2: the split kernel, HG_ERR_INVALID where it does not cover the shape).
+ * y [M, D] fp32: exactly M rows are written.  partials (nullable) fp32 [F / 128, M, D]: the split kernel's partial sums before the
+ * reduce (only where that kernel ran; HG_ERR_INVALID when asked for on the GEMM path).  1 <= M <= 2^20, D a multiple of 128 up to
+ * 512, F a multiple of 128.  Under hg_profile_begin the split kernel (HG_PROF_DETR_FFN) or the two GEMMs, and the tail
+ * (HG_PROF_DETR_ROWS), are recorded. */
+int hg_test_detr_ffn(hg_ctx*, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* norm_w,
+                     const float* norm_b, int M, int D, int F, float* y, float* partials, void* stream);
 
 /* Test hook for the fused in_proj + attention kernel (hoigen_amd/csrc/hg_qkv_attn.hip; the reference ops it replaces:
  * clipnet/model.py:171,181-183).  a [n_seq*L, D] fp32 (rounded to fp16 inside: the centred copy of the stream), w [3D, D] the
