@@ -189,6 +189,21 @@ class hg_detr_decoder_args(C.Structure):
                [(n, C.c_int64 * 3) for n in ("tgt_stride", "query_pos_stride", "memory_stride", "pos_stride")] + [("out_stride", C.c_int64 * 4)]
 
 
+# limits of one hg_detr_heads call (hoigen_amd/csrc/hg_kernels.h): logits, levels, images, queries
+HG_DETR_HEADS_MAX_C, HG_DETR_HEADS_MAX_L, HG_DETR_HEADS_MAX_B, HG_DETR_HEADS_MAX_Q = 256, 12, 64, 1792
+
+
+class hg_detr_heads_weights(C.Structure):
+    _fields_ = [(n, hg_tensor) for n in ("class_weight", "class_bias", "l0_w", "l0_b", "l1_w", "l1_b", "l2_w", "l2_b")] + \
+               [("d_model", C.c_int32), ("n_logits", C.c_int32), ("class_rows", C.POINTER(C.c_int32)), ("n_class_rows", C.c_int32)]
+
+
+class hg_detr_heads_args(C.Structure):
+    _fields_ = [("hs", C.c_void_p), ("hs_stride", C.c_int64 * 3), ("L", C.c_int32), ("B", C.c_int32), ("Q", C.c_int32),
+                ("target_sizes", C.POINTER(C.c_float))] + \
+               [(n, C.c_void_p) for n in ("pred_logits", "pred_boxes", "scores", "labels", "boxes")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -251,6 +266,8 @@ SIGNATURES = {
     "hg_detr_encoder": (_I, [_P, C.POINTER(hg_detr_encoder_args), _P]),
     "hg_load_detr_decoder": (_I, [_P, C.POINTER(hg_detr_decoder_weights)]),
     "hg_detr_decoder": (_I, [_P, C.POINTER(hg_detr_decoder_args), _P]),
+    "hg_load_detr_heads": (_I, [_P, C.POINTER(hg_detr_heads_weights)]),
+    "hg_detr_heads": (_I, [_P, C.POINTER(hg_detr_heads_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),

@@ -111,6 +111,7 @@ void hg_destroy(hg_ctx* c) {
     for (auto& m : c->prior) free_all(m.owned);
     free_all(c->detr.owned);
     free_all(c->detr_dec.owned);
+    free_all(c->detr_heads.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

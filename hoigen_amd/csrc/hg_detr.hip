@@ -38,6 +38,34 @@ int detr_f32(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, size_t n,
     return HG_OK;
 }
 
+// hg_load_detr_heads: `rows` rows of t [n_in, D] (all of them in order where rows is null) as fp16 [n_pad, D] (mat) or one value a row as
+// fp32 [n_pad] (!mat), zero behind the rows taken.  tmp holds the converted copy of the whole tensor until the load ends.
+int heads_rows(hg_ctx* c, std::vector<void*>& owned, std::vector<void*>& tmp, const hg_tensor& t, bool mat, int n_in, int D, const int32_t* rows,
+               int n_rows, int n_pad, void** out, const char* name) {
+    if (!t.ptr) return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: missing tensor %s", name);
+    if (t.dtype != HG_F16 && t.dtype != HG_F32) return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: bad dtype for %s", name);
+    const size_t row = mat ? (size_t)D * 2 : 4, n = (size_t)n_in * (mat ? D : 1);
+    void *full, *dst;
+    int rc = detr_alloc(c, tmp, n * (mat ? 2 : 4), &full);
+    if (rc) return rc;
+    if (mat) {
+        if (t.dtype == HG_F16) HG_HIP(hipMemcpy(full, t.ptr, n * 2, hipMemcpyDeviceToDevice));
+        else HG_HIP(launch_f32_to_f16((const float*)t.ptr, (half_t*)full, n, 0));
+    } else {
+        if (t.dtype == HG_F32) HG_HIP(hipMemcpy(full, t.ptr, n * 4, hipMemcpyDeviceToDevice));
+        else HG_HIP(launch_f16_to_f32((const half_t*)t.ptr, (float*)full, n, 0));
+    }
+    HG_HIP(hipDeviceSynchronize());
+    rc = detr_alloc(c, owned, n_pad * row, &dst);
+    if (rc) return rc;
+    HG_HIP(hipMemset(dst, 0, n_pad * row));
+    if (!rows) HG_HIP(hipMemcpy(dst, full, n_rows * row, hipMemcpyDeviceToDevice));
+    else
+        for (int i = 0; i < n_rows; ++i) HG_HIP(hipMemcpy((char*)dst + i * row, (const char*)full + rows[i] * row, row, hipMemcpyDeviceToDevice));
+    *out = dst;
+    return HG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,6 +172,74 @@ int hg_detr_encoder(hg_ctx* c, const hg_detr_encoder_args* a, void* stream) {
                                     a->trace ? a->trace + (size_t)l * M * D : nullptr, M, D, s));
     }
     HG_HIP(launch_detr_exit(x, a->out, a->out_stride[0], a->out_stride[1], B, S, D, s));
+    return HG_OK;
+}
+
+// detr/models/detr.py:37-38 (class_embed, bbox_embed = MLP(hidden_dim, hidden_dim, 4, 3)); class_rows: the reserve_indices of
+// upt_tip_cache_model_free_finetune_distill3.py:1600-1602
+int hg_load_detr_heads(hg_ctx* c, const hg_detr_heads_weights* w) {
+    if (!c) return HG_ERR_INVALID;
+    if (!w) return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: weights are required");
+    const int D = w->d_model, NL = w->n_logits;
+    if (D != 128 && D != 256) return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: d_model must be 128 or 256 (got %d)", D);
+    if (NL < 1 || NL > (1 << 16)) return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: n_logits = %d, 1 .. 65536", NL);
+    if (w->class_rows ? w->n_class_rows < 0 : w->n_class_rows != 0)
+        return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: n_class_rows = %d without class_rows, or negative", w->n_class_rows);
+    const int C1 = w->class_rows ? w->n_class_rows : NL;
+    if (C1 < 2 || C1 > DETR_HEADS_MAX_C)
+        return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: %d logits (classes + 1), 2 .. %d", C1, DETR_HEADS_MAX_C);
+    for (int i = 0; w->class_rows && i < C1; ++i)
+        if (w->class_rows[i] < 0 || w->class_rows[i] >= NL)
+            return fail(c, HG_ERR_INVALID, "hg_load_detr_heads: class_rows[%d] = %d is outside [0, %d)", i, w->class_rows[i], NL);
+    HG_ON_DEVICE(c);
+    DetrHeads& h = c->detr_heads;
+    HG_HIP(hipDeviceSynchronize());      // a call in flight may still read the weights this load replaces
+    free_all(h.owned);
+    h = DetrHeads{};
+    h.D = D; h.C1 = C1; h.C1p = (int)rup(C1, 16);
+    std::vector<void*> tmp;
+    int rc = 0;
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->class_weight, true, NL, D, w->class_rows, C1, h.C1p, (void**)&h.wc, "class_embed.weight"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->class_bias, false, NL, D, w->class_rows, C1, h.C1p, (void**)&h.bc, "class_embed.bias"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l0_w, true, D, D, nullptr, D, D, (void**)&h.w0, "bbox_embed.layers.0.weight"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l0_b, false, D, D, nullptr, D, D, (void**)&h.b0, "bbox_embed.layers.0.bias"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l1_w, true, D, D, nullptr, D, D, (void**)&h.w1, "bbox_embed.layers.1.weight"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l1_b, false, D, D, nullptr, D, D, (void**)&h.b1, "bbox_embed.layers.1.bias"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l2_w, true, 4, D, nullptr, 4, 16, (void**)&h.w2, "bbox_embed.layers.2.weight"));
+    keep_first(rc, heads_rows(c, h.owned, tmp, w->l2_b, false, 4, D, nullptr, 4, 16, (void**)&h.b2, "bbox_embed.layers.2.bias"));
+    (void)hipDeviceSynchronize();
+    free_all(tmp);
+    if (rc) {
+        free_all(h.owned);
+        h = DetrHeads{};
+        return rc;
+    }
+    h.loaded = true;
+    return HG_OK;
+}
+
+// upt_tip_cache_model_free_finetune_distill3.py:1598-1605 with detr/models/detr.py:274-282 behind the last line
+int hg_detr_heads(hg_ctx* c, const hg_detr_heads_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    const DetrHeads& h = c->detr_heads;
+    if (!h.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_detr_heads: no heads loaded (hg_load_detr_heads)");
+    if (!a || !a->hs || !a->target_sizes || !a->scores || !a->labels || !a->boxes)
+        return fail(c, HG_ERR_INVALID, "hg_detr_heads: hs, target_sizes, scores, labels and boxes are required");
+    if (a->L < 1 || a->L > DETR_HEADS_MAX_L) return fail(c, HG_ERR_INVALID, "hg_detr_heads: L = %d levels, 1 .. %d", a->L, DETR_HEADS_MAX_L);
+    if (a->B < 1 || a->B > DETR_HEADS_MAX_B) return fail(c, HG_ERR_INVALID, "hg_detr_heads: B = %d images, 1 .. %d", a->B, DETR_HEADS_MAX_B);
+    if (a->Q < 1 || a->Q > DETR_HEADS_MAX_Q) return fail(c, HG_ERR_INVALID, "hg_detr_heads: Q = %d queries, 1 .. %d", a->Q, DETR_HEADS_MAX_Q);
+    if ((uintptr_t)a->boxes & 15) return fail(c, HG_ERR_INVALID, "hg_detr_heads: boxes must be 16-byte aligned");
+    HG_ON_DEVICE(c);
+    DetrHeadsArgs k{};
+    const bool all = a->pred_logits || a->pred_boxes;
+    k.hs = a->hs; k.s_l = a->hs_stride[0]; k.s_b = a->hs_stride[1]; k.s_q = a->hs_stride[2];
+    k.wc = h.wc; k.bc = h.bc; k.w0 = h.w0; k.b0 = h.b0; k.w1 = h.w1; k.b1 = h.b1; k.w2 = h.w2; k.b2 = h.b2;
+    k.pred_logits = a->pred_logits; k.pred_boxes = a->pred_boxes; k.scores = a->scores; k.labels = a->labels; k.boxes = a->boxes;
+    k.D = h.D; k.C1 = h.C1; k.C1p = h.C1p; k.l0 = all ? 0 : a->L - 1; k.L = all ? a->L : 1; k.B = a->B; k.Q = a->Q;
+    k.vec4 = !((uintptr_t)a->hs & 15) && !(k.s_l & 3) && !(k.s_b & 3) && !(k.s_q & 3);
+    memcpy(k.sizes, a->target_sizes, sizeof(float) * 2 * a->B);
+    hipError_t he = launch_detr_heads(k, (hipStream_t)stream);
+    if (he != hipSuccess) return fail(c, HG_ERR_HIP, "hg_detr_heads: launch failed: %s", hipGetErrorString(he));
     return HG_OK;
 }
 

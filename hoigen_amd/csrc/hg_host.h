@@ -158,6 +158,13 @@ struct DetrDec {         // hg_load_detr_decoder
     float *bk_all = nullptr, *bv_all = nullptr, *nf_w = nullptr, *nf_b = nullptr;
     std::vector<void*> owned;
 };
+struct DetrHeads {       // hg_load_detr_heads: class_embed (rows gathered, padded to C1p = a multiple of 16) and bbox_embed (layers.2 padded to 16 rows)
+    bool loaded = false;
+    int D = 0, C1 = 0, C1p = 0;
+    half_t *wc = nullptr, *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
+    float *bc = nullptr, *b0 = nullptr, *b1 = nullptr, *b2 = nullptr;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -172,6 +179,7 @@ struct hg_ctx {
     Priors prior[HG_MAX_PRIOR_SLOTS];
     DetrEnc detr;
     DetrDec detr_dec;
+    DetrHeads detr_heads;
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h

@@ -195,6 +195,27 @@ inline size_t detr_ffn_partial_bytes(int M, int D, int F) { return (size_t)(F / 
 hipError_t launch_detr_ffn(const half_t* x16, const half_t* W1, const float* b1, const half_t* W2, float* partial, int M, int D, int F,
                            hipStream_t s);
 
+// ---- DETR's heads and PostProcess in one launch (hg_detr_heads.hip): class logits, the box MLP with its sigmoid, and - for the rows of
+// the last level computed - softmax, the foreground maximum and the scaled xyxy boxes.  hs fp32 through element strides (level, image,
+// query; channel stride 1), levels l0 .. l0 + L - 1 of it; wc [C1p, D] / bc [C1p] with C1p = C1 rounded up to 16, zero rows behind C1;
+// w0, w1 [D, D]; w2 [16, D] / b2 [16] with zero rows behind 4 (fp16 matrices, fp32 biases, 16-byte aligned).  pred_logits [L, B, Q, C1]
+// and pred_boxes [L, B, Q, 4] may be null; scores, labels [B, Q] and boxes [B, Q, 4] (16-byte aligned) may not.  sizes = (h, w) per image.
+// vec4: hs and its strides allow 16-byte loads.  A shape outside detr_heads_ok: hipErrorInvalidValue and nothing launched.
+static constexpr int DETR_HEADS_ROWS = 32, DETR_HEADS_MAX_C = 256, DETR_HEADS_MAX_L = 12, DETR_HEADS_MAX_B = 64, DETR_HEADS_MAX_Q = 1792;
+struct DetrHeadsArgs {
+    const float* hs;
+    long long s_l, s_b, s_q;
+    const half_t *wc, *w0, *w1, *w2;
+    const float *bc, *b0, *b1, *b2;
+    float *pred_logits, *pred_boxes, *scores;
+    int32_t* labels;
+    float* boxes;
+    int D, C1, C1p, l0, L, B, Q, vec4;
+    float sizes[2 * DETR_HEADS_MAX_B];
+};
+bool detr_heads_ok(int D, int C1, int L, int B, int Q);
+hipError_t launch_detr_heads(const DetrHeadsArgs& a, hipStream_t s);
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

@@ -5,8 +5,10 @@ hg_detr_decoder).
 
     self.detector.transformer = Transformer.from_module(self.detector.transformer)
 
-is the whole integration; the two halves can be swapped on their own as well.  Inference only; tensors must live on a
-HIP device.
+is the whole integration; the two halves can be swapped on their own as well.  ``DetectionHeads`` is what follows the
+transformer in the detector (upt_tip_cache_model_free_finetune_distill3.py:1598-1605): ``class_embed``, ``bbox_embed`` with its sigmoid
+and ``PostProcess`` in one launch (hg_detr_heads.hip: hg_load_detr_heads, hg_detr_heads).  Inference only; tensors must live on a HIP
+device.
 """
 from __future__ import annotations
 
@@ -375,3 +377,137 @@ class Transformer(nn.Module):
         hs = torch.empty(L, B, query_embed.shape[0], Cc, device=src.device, dtype=torch.float32)
         self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
         return hs, mem.permute(0, 2, 1).view(B, Cc, H, W)
+
+
+class BoxMLP(nn.Module):
+    """Parameters of the reference's ``MLP(D, D, 4, 3)`` (detr/models/detr.py:293-305): ``layers.{0,1,2}.weight`` / ``bias``."""
+
+    def __init__(self, d_model: int):
+        super().__init__()
+        self.num_layers = 3
+        self.layers = nn.ModuleList([Linear(d_model, d_model), Linear(d_model, d_model), Linear(d_model, 4)])
+
+
+class DetectionHeads(nn.Module):
+    """The statements between the detector's transformer and the region proposals
+    (upt_tip_cache_model_free_finetune_distill3.py:1598-1605) in one native launch (hoigen_amd/csrc/hg_detr_heads.hip: hg_load_detr_heads,
+    hg_detr_heads): ``class_embed(hs)``, ``bbox_embed(hs).sigmoid()``, the V-COCO column selection ``[..., reserve_indices]`` and
+    ``PostProcess`` (detr/models/detr.py:258-290).
+
+        heads = DetectionHeads.from_modules(self.detector.class_embed, self.detector.bbox_embed, reserve_indices)
+        results = heads.detect(hs, image_sizes)
+
+    Parameters ``class_embed.weight`` / ``bias`` and ``bbox_embed.layers.{0,1,2}.weight`` / ``bias``, the detector's own keys.  With
+    ``reserve_indices`` the logits are those rows of ``class_embed`` in that order; the last of them is the no-object column.
+    Inference only; tensors must live on a HIP device."""
+
+    def __init__(self, d_model: int = 256, num_logits: int = 92, reserve_indices=None):
+        super().__init__()
+        self.d_model, self.num_logits = d_model, num_logits
+        self.class_embed = Linear(d_model, num_logits)
+        self.bbox_embed = BoxMLP(d_model)
+        self.reserve_indices = None if reserve_indices is None else [int(i) for i in reserve_indices]
+        self._ctx = _Ctx()
+        self._sig = None
+
+    @property
+    def n_out(self) -> int:
+        """C1: the logits a row has (classes + 1)"""
+        return self.num_logits if self.reserve_indices is None else len(self.reserve_indices)
+
+    @classmethod
+    def from_modules(cls, class_embed: nn.Module, bbox_embed: nn.Module, reserve_indices=None) -> "DetectionHeads":
+        """From the reference's ``class_embed`` (an ``nn.Linear``: ``weight``, ``bias``) and ``bbox_embed`` (its ``MLP``:
+        ``layers.{0,1,2}.weight`` / ``bias``), or any modules with those state-dict keys."""
+        cw = class_embed.state_dict()
+        bw = bbox_embed.state_dict()
+        if sorted(cw) != ["bias", "weight"] or cw["weight"].dim() != 2:
+            raise RuntimeError(f"hoigen_amd: DetectionHeads.from_modules: class_embed must hold a [C1, D] `weight` and a `bias` (got {sorted(cw)})")
+        C1, D = (int(v) for v in cw["weight"].shape)
+        want = sorted(f"layers.{i}.{k}" for i in range(3) for k in ("weight", "bias"))
+        if sorted(bw) != want:
+            raise RuntimeError("hoigen_amd: DetectionHeads.from_modules: bbox_embed must be the three-layer MLP(D, D, 4, 3) of "
+                               f"detr/models/detr.py:38 with keys {want} (got {sorted(bw)})")
+        shapes = [tuple(bw[f"layers.{i}.weight"].shape) for i in range(3)]
+        if shapes != [(D, D), (D, D), (4, D)]:
+            raise RuntimeError(f"hoigen_amd: DetectionHeads.from_modules: bbox_embed must be of width D -> D -> D -> 4 with D = {D}, the "
+                               f"width of class_embed (got weights {shapes})")
+        m = cls(D, C1, reserve_indices)
+        if m.reserve_indices is not None and any(i < 0 or i >= C1 for i in m.reserve_indices):
+            raise RuntimeError(f"hoigen_amd: DetectionHeads.from_modules: reserve_indices must lie in [0, {C1})")
+        m.class_embed.load_state_dict(cw)
+        m.bbox_embed.load_state_dict(bw)
+        w = cw["weight"]
+        m.to(device=w.device, dtype=w.dtype)
+        m.train(class_embed.training)
+        return m
+
+    def _load(self, device: torch.device) -> int:
+        h = self._ctx.get(device)
+        sig = (h, _sig(self.parameters()), tuple(self.reserve_indices or ()))
+        if sig != self._sig:
+            t = lambda p: _lib.tensor(p.detach().contiguous())
+            ls = self.bbox_embed.layers
+            rows = self.reserve_indices
+            arr = (C.c_int32 * len(rows))(*rows) if rows is not None else None
+            w = _lib.hg_detr_heads_weights(t(self.class_embed.weight), t(self.class_embed.bias), t(ls[0].weight), t(ls[0].bias), t(ls[1].weight),
+                                           t(ls[1].bias), t(ls[2].weight), t(ls[2].bias), self.d_model, self.num_logits, arr,
+                                           len(rows) if rows is not None else 0)
+            self._ctx.check(_lib.lib().hg_load_detr_heads(h, C.byref(w)), "hg_load_detr_heads")
+            self._sig = sig
+        return h
+
+    def _run(self, hs, target_sizes, want_all: bool):
+        _require_cuda(hs, "DetectionHeads hs")
+        if hs.dim() != 4 or hs.shape[3] != self.d_model:
+            raise RuntimeError(f"hoigen_amd: DetectionHeads: hs must be [L, B, Q, {self.d_model}] (got {tuple(hs.shape)})")
+        L, B, Q, _ = hs.shape
+        x = hs.detach()
+        if x.dtype != torch.float32 or x.stride(3) != 1:
+            x = x.to(torch.float32).contiguous()
+        if target_sizes is None:
+            sizes = [(1.0, 1.0)] * B
+        elif isinstance(target_sizes, torch.Tensor):
+            sizes = target_sizes.detach().to("cpu", torch.float32).reshape(-1, 2).tolist()
+        else:
+            sizes = [(float(h_), float(w_)) for h_, w_ in target_sizes]
+        if len(sizes) != B:
+            raise RuntimeError(f"hoigen_amd: DetectionHeads: target_sizes must hold one (h, w) for each of the {B} images (got {len(sizes)})")
+        h = self._load(x.device)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        C1 = self.n_out
+        logits = torch.empty(L, B, Q, C1, **f32) if want_all else None
+        pboxes = torch.empty(L, B, Q, 4, **f32) if want_all else None
+        scores, boxes = torch.empty(B, Q, **f32), torch.empty(B, Q, 4, **f32)
+        labels = torch.empty(B, Q, device=x.device, dtype=torch.int32)
+        a = _lib.hg_detr_heads_args()
+        a.hs, a.L, a.B, a.Q = x.data_ptr(), L, B, Q
+        a.hs_stride[:] = [x.stride(0), x.stride(1), x.stride(2)]
+        a.target_sizes = (C.c_float * (2 * B))(*[v for hw in sizes for v in hw])
+        a.pred_logits, a.pred_boxes = (logits.data_ptr(), pboxes.data_ptr()) if want_all else (None, None)
+        a.scores, a.labels, a.boxes = scores.data_ptr(), labels.data_ptr(), boxes.data_ptr()
+        self._ctx.check(_lib.lib().hg_detr_heads(h, C.byref(a), _stream_ptr(x.device)), "hg_detr_heads")
+        return logits, pboxes, scores, labels, boxes
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, hs):
+        """``(outputs_class [L, B, Q, C1], outputs_coord [L, B, Q, 4])`` fp32, as upt...:1598-1602 produce them from ``hs [L, B, Q, D]``."""
+        logits, pboxes = self._run(hs, None, True)[:2]
+        return logits, pboxes
+
+    @_inference_only
+    @torch.no_grad()
+    def detect(self, hs, target_sizes, with_outputs: bool = False):
+        """What ``PostProcess.forward({'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1]}, target_sizes)`` returns
+        (upt...:1604-1605): a list of B dicts ``scores [Q]`` fp32, ``labels [Q]`` int64 (as ``torch.max`` gives them) and ``boxes [Q, 4]``
+        fp32 in pixels, per-image views of packed buffers.  Only the last level of ``hs`` is computed unless ``with_outputs``, which also
+        returns ``{'pred_logits', 'pred_boxes'}`` of the last level.  ``target_sizes``: a host sequence of (h, w), or a tensor [B, 2];
+        the sizes travel in the launch's arguments, so a DEVICE tensor costs one copy to the host (and its wait) - pass the host list
+        the caller built it from where there is one."""
+        logits, pboxes, scores, labels, boxes = self._run(hs, target_sizes, with_outputs)
+        labels = labels.to(torch.int64)
+        results = [{"scores": s, "labels": l, "boxes": b} for s, l, b in zip(scores, labels, boxes)]
+        if with_outputs:
+            return results, {"pred_logits": logits[-1], "pred_boxes": pboxes[-1]}
+        return results

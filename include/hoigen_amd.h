@@ -567,6 +567,49 @@ typedef struct {
     int64_t out_stride[4];                                 /* elements: layer, batch, query, channel */
 } hg_detr_decoder_args;
 int hg_detr_decoder(hg_ctx*, const hg_detr_decoder_args* args, void* stream);
+
+/* ---- DETR heads and PostProcess (upt_tip_cache_model_free_finetune_distill3.py:1598-1605: class_embed(hs), bbox_embed(hs).sigmoid(),
+ * the V-COCO row selection and the postprocessor; detr/models/detr.py:37-38 the two heads, :293-305 MLP, :269-282 PostProcess.forward,
+ * detr/util/box_ops.py:9-13 box_cxcywh_to_xyxy) in ONE launch (hoigen_amd/csrc/hg_detr_heads.hip) -------------------------------------
+ *
+ * hg_load_detr_heads (detr.py:37-38; state-dict keys weight / bias of class_embed and layers.{0,1,2}.weight / bias of bbox_embed, an
+ * MLP(d_model, d_model, 4, 3)): a slot of its own beside the encoder's and the decoder's.  class_rows (HOST, nullable) is the V-COCO
+ * path, outputs_class[..., reserve_indices] at upt...:1600-1602: those rows of class_weight and class_bias are gathered here, so the
+ * number of logits C1 becomes n_class_rows (else n_logits); the LAST of them is the no-object column.  The fp16 copies of the matrices
+ * are made here.  Synchronous.  HG_ERR_INVALID with a message for d_model outside {128, 256}, C1 outside 2 .. 256, a class_rows index
+ * outside [0, n_logits) (the slot keeps what it held), and for a missing tensor or a dtype other than fp32 / fp16 (the slot is then empty). */
+typedef struct {
+    hg_tensor class_weight, class_bias;    /* [n_logits, d_model], [n_logits] */
+    hg_tensor l0_w, l0_b, l1_w, l1_b;      /* [d_model, d_model], [d_model] each */
+    hg_tensor l2_w, l2_b;                  /* [4, d_model], [4] */
+    int32_t d_model, n_logits;
+    const int32_t* class_rows;             /* HOST [n_class_rows], nullable */
+    int32_t n_class_rows;
+} hg_detr_heads_weights;
+int hg_load_detr_heads(hg_ctx*, const hg_detr_heads_weights*);
+/* hg_detr_heads (upt...:1598-1605): hs DEVICE fp32 [L, B, Q, d_model] through element strides hs_stride = (level, image, query), channel
+ * stride 1 (no alignment beyond a float's).  Per row: logits = fp16(hs) Wc^T + bc, pred_box = sigmoid(MLP(fp16(hs))) with fp16 hidden
+ * layers, fp32 accumulation.  PostProcess on level L - 1 (detr.py:274-282): softmax over all C1 logits, score and label = the maximum
+ * over the first C1 - 1 (ties to the lower index), boxes = box_cxcywh_to_xyxy(pred_box) * (w, h, w, h) of the row's image, each
+ * operation rounded on its own in fp32.  target_sizes: HOST float [B, 2] = (h, w), as hg_region_priors takes its image_sizes; it
+ * travels in the launch's arguments.
+ *   pred_logits [L, B, Q, C1], pred_boxes [L, B, Q, 4]   fp32, nullable; when BOTH are null only level L - 1 is computed
+ *   scores [B, Q], labels int32 [B, Q], boxes [B, Q, 4] (16-byte aligned)     required
+ * Asynchronous on `stream`; no host wait, no allocation, no workspace.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message
+ * and nothing launched for L outside 1 .. 12, B outside 1 .. 64, Q outside 1 .. 1792, a null hs, target_sizes, scores, labels or boxes,
+ * or boxes off a 16-byte boundary. */
+typedef struct {
+    const float* hs;
+    int64_t hs_stride[3];                  /* elements: level, image, query */
+    int32_t L, B, Q;
+    const float* target_sizes;
+    float* pred_logits;
+    float* pred_boxes;
+    float* scores;
+    int32_t* labels;
+    float* boxes;
+} hg_detr_heads_args;
+int hg_detr_heads(hg_ctx*, const hg_detr_heads_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
