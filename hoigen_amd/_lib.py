@@ -204,6 +204,21 @@ class hg_detr_heads_args(C.Structure):
                [(n, C.c_void_p) for n in ("pred_logits", "pred_boxes", "scores", "labels", "boxes")]
 
 
+# limits of one hg_detr_neck call (hoigen_amd/csrc/hg_kernels.h): input channels, images, image-mask side
+HG_DETR_NECK_MAX_CIN, HG_DETR_NECK_MAX_B, HG_DETR_NECK_MAX_IMG = 4096, 64, 8192
+
+
+class hg_detr_neck_weights(C.Structure):
+    _fields_ = [("weight", hg_tensor), ("bias", hg_tensor), ("cin", C.c_int32), ("d_model", C.c_int32), ("num_pos_feats", C.c_int32),
+                ("temperature", C.c_float), ("normalize", C.c_int32), ("scale", C.c_float)]
+
+
+class hg_detr_neck_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64 * 3), ("image_mask", C.c_void_p), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("src", C.c_void_p), ("src_stride", C.c_int64 * 2),
+                ("pos", C.c_void_p), ("pos_stride", C.c_int64 * 2), ("mask", C.c_void_p)]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -223,7 +238,7 @@ class hg_test_elem_args(C.Structure):
 
 
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
-HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS = 104, 105
+HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
 
 _P = C.c_void_p
 _I = C.c_int
@@ -268,6 +283,8 @@ SIGNATURES = {
     "hg_detr_decoder": (_I, [_P, C.POINTER(hg_detr_decoder_args), _P]),
     "hg_load_detr_heads": (_I, [_P, C.POINTER(hg_detr_heads_weights)]),
     "hg_detr_heads": (_I, [_P, C.POINTER(hg_detr_heads_args), _P]),
+    "hg_load_detr_neck": (_I, [_P, C.POINTER(hg_detr_neck_weights)]),
+    "hg_detr_neck": (_I, [_P, C.POINTER(hg_detr_neck_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),

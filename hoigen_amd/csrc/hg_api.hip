@@ -40,6 +40,7 @@ const Option OPTIONS[] = {
     {"detr_attn_waves", "HG_DETR_ATTN_WAVES", &hg_ctx::opt_detr_attn_waves, false, 0, 4, "0, 1, 2 or 4"},
     {"detr_ffn", "HG_DETR_FFN", &hg_ctx::opt_detr_ffn, false, 0, 2, "0, 1 or 2"},
     {"detr_ffn_max_m", "HG_DETR_FFN_MAX_M", &hg_ctx::opt_detr_ffn_max_m, false, 0, 1 << 20, "0 .. 2^20"},
+    {"detr_neck_split", "HG_DETR_NECK_SPLIT", &hg_ctx::opt_detr_neck_split, false, 0, 64, "0 .. 64"},
     {"mlp_pair_fault", "HG_MLP_PAIR_FAULT", &hg_ctx::opt_mlp_pair_fault, false, 0, 1, "0 or 1"},
 };
 const Option* find_option(const char* key) {
@@ -112,6 +113,7 @@ void hg_destroy(hg_ctx* c) {
     free_all(c->detr.owned);
     free_all(c->detr_dec.owned);
     free_all(c->detr_heads.owned);
+    free_all(c->detr_neck.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

@@ -243,4 +243,99 @@ int hg_detr_heads(hg_ctx* c, const hg_detr_heads_args* a, void* stream) {
     return HG_OK;
 }
 
+// detr/models/detr.py:40 (input_proj = nn.Conv2d(backbone.num_channels, hidden_dim, kernel_size=1)) and
+// detr/models/position_encoding.py:17-26, :37-38 (PositionEmbeddingSine's attributes and its dim_t)
+int hg_load_detr_neck(hg_ctx* c, const hg_detr_neck_weights* w) {
+    if (!c) return HG_ERR_INVALID;
+    if (!w) return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: weights are required");
+    const int D = w->d_model, Cin = w->cin;
+    if (D != 128 && D != 256) return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: d_model must be 128 or 256 (got %d)", D);
+    if (Cin < 64 || Cin % 64 || Cin > DETR_NECK_MAX_CIN)
+        return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: cin must be a multiple of 64 up to %d (got %d)", DETR_NECK_MAX_CIN, Cin);
+    if (w->num_pos_feats != D / 2)
+        return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: num_pos_feats = %d, and pos has d_model = %d channels: it must be d_model / 2", w->num_pos_feats, D);
+    if (!(w->temperature > 0.f)) return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: temperature must be positive");
+    if (!w->weight.ptr || !w->bias.ptr) return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: missing tensor %s", w->weight.ptr ? "bias" : "weight");
+    for (const hg_tensor* t : {&w->weight, &w->bias})
+        if (t->dtype != HG_F16 && t->dtype != HG_F32) return fail(c, HG_ERR_INVALID, "hg_load_detr_neck: bad dtype for %s", t == &w->bias ? "bias" : "weight");
+    HG_ON_DEVICE(c);
+    DetrNeck& n = c->detr_neck;
+    HG_HIP(hipDeviceSynchronize());      // a call in flight may still read the weights this load replaces
+    free_all(n.owned);
+    n = DetrNeck{};
+    n.D = D; n.Cin = Cin; n.normalize = w->normalize != 0; n.scale = w->scale;
+    int rc = 0;
+    keep_first(rc, detr_f16(c, n.owned, w->weight, (size_t)D * Cin, &n.w, 0, "input_proj.weight"));
+    keep_first(rc, detr_f32(c, n.owned, w->bias, D, &n.bias, 0, "input_proj.bias"));
+    void* tab = nullptr;
+    keep_first(rc, detr_alloc(c, n.owned, (size_t)(D / 2) * 4, &tab));
+    if (rc) {
+        free_all(n.owned);
+        n = DetrNeck{};
+        return rc;
+    }
+    // dim_t[i] = fp32(temperature ** (2 * (i // 2) / num_pos_feats))      (position_encoding.py:37-38)
+    std::vector<float> dim_t(D / 2);
+    for (int i = 0; i < D / 2; ++i) dim_t[i] = (float)pow((double)w->temperature, 2.0 * (i / 2) / (double)(D / 2));
+    HG_HIP(hipMemcpy(tab, dim_t.data(), dim_t.size() * 4, hipMemcpyHostToDevice));
+    HG_HIP(hipDeviceSynchronize());
+    n.dim_t = (float*)tab;
+    n.loaded = true;
+    return HG_OK;
+}
+
+// Slices of Cin where option detr_neck_split = 0.  A work item is a tile of 32 tokens and a slice, and it walks its slice block by block,
+// so a launch of few tiles is as long as one walk of all of Cin: measured at Cin 2048 (profiles/detr_neck.txt), one slice takes 65 - 69 us
+// from 30 to 182 tiles and 86 us at 264; 8 slices take 31 us at 30 tiles and 41 - 47 us at 120 and 182 (4 slices: 43 - 45 us, within
+// the spread), 2 slices 73 us at 264 - the launch that adds the partial sums included; gaps of 13 to 33 us against spreads of 1 to 6.
+// So: double the slices while there are fewer than 512 work items, up to 8.
+static int detr_neck_default_split(int Cin, int B, int S) {
+    const int tiles = B * ((S + DETR_NECK_TOKENS - 1) / DETR_NECK_TOKENS);
+    int n = 1;
+    while (n < 8 && tiles * n < 512 && Cin % (128 * n) == 0) n *= 2;
+    return n;
+}
+
+// upt_tip_cache_model_free_finetune_distill3.py:1594-1597: backbone.py:78 (the mask), position_encoding.py:28-48, input_proj (detr.py:65),
+// and transformer.py:50-51 (the flatten / permute that the batch-first outputs make unnecessary)
+int hg_detr_neck(hg_ctx* c, const hg_detr_neck_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    const DetrNeck& n = c->detr_neck;
+    if (!n.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_detr_neck: no neck loaded (hg_load_detr_neck)");
+    if (!a || !a->x || !a->src) return fail(c, HG_ERR_INVALID, "hg_detr_neck: x and src are required");
+    if ((a->pos || a->mask) && !a->image_mask) return fail(c, HG_ERR_INVALID, "hg_detr_neck: pos and mask need image_mask");
+    if (a->B < 1 || a->B > DETR_NECK_MAX_B) return fail(c, HG_ERR_INVALID, "hg_detr_neck: B = %d images, 1 .. %d", a->B, DETR_NECK_MAX_B);
+    if (a->H < 1 || a->W < 1 || (long long)a->H * a->W > DETR_ATTN_MAX_L)
+        return fail(c, HG_ERR_INVALID, "hg_detr_neck: H x W = %d x %d tokens, 1 .. %d", a->H, a->W, DETR_ATTN_MAX_L);
+    if (a->image_mask && (a->Hi < 1 || a->Wi < 1 || a->Hi > DETR_NECK_MAX_IMG || a->Wi > DETR_NECK_MAX_IMG))
+        return fail(c, HG_ERR_INVALID, "hg_detr_neck: image_mask is Hi x Wi = %d x %d, 1 .. %d each", a->Hi, a->Wi, DETR_NECK_MAX_IMG);
+    if (a->x_stride[2] != 1) return fail(c, HG_ERR_INVALID, "hg_detr_neck: the token stride of x must be 1 (got %lld)", (long long)a->x_stride[2]);
+    const int S = a->H * a->W, opt = c->opt_detr_neck_split;
+    const int nsplit = opt ? opt : detr_neck_default_split(n.Cin, a->B, S);
+    if (n.Cin % (64 * nsplit))
+        return fail(c, HG_ERR_INVALID, "hg_detr_neck: option detr_neck_split = %d, and cin = %d is not that many slices of a multiple of 64", nsplit, n.Cin);
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    DetrNeckArgs k{};
+    if (nsplit > 1) {
+        int rc = ensure(c, c->detr_neck_ws, detr_neck_partial_bytes(nsplit, a->B, S, n.D));
+        if (rc) return rc;
+        k.partial = (float*)c->detr_neck_ws.p;
+    }
+    k.x = a->x; k.x_sb = a->x_stride[0]; k.x_sc = a->x_stride[1];
+    k.w = n.w; k.bias = n.bias; k.dim_t = n.dim_t; k.image_mask = a->image_mask;
+    k.src = a->src; k.src_sb = a->src_stride[0]; k.src_ss = a->src_stride[1];
+    k.pos = a->pos; k.pos_sb = a->pos ? a->pos_stride[0] : 0; k.pos_ss = a->pos ? a->pos_stride[1] : 0;
+    k.mask = a->mask; k.scale = n.scale; k.normalize = n.normalize;
+    k.Cin = n.Cin; k.D = n.D; k.B = a->B; k.H = a->H; k.W = a->W; k.Hi = a->image_mask ? a->Hi : 1; k.Wi = a->image_mask ? a->Wi : 1;
+    k.nsplit = nsplit; k.kslice = n.Cin / nsplit;
+    k.vec4 = !((uintptr_t)a->x & 15) && !(k.x_sb & 3) && !(k.x_sc & 3) && !(S & 3);
+    k.ovec4 = !((uintptr_t)a->src & 15) && !(k.src_sb & 3) && !(k.src_ss & 3);
+    ProfScope ps(c, s, HG_PROF_DETR_NECK, a->B * S, nsplit, n.Cin);
+    hipError_t he = launch_detr_neck(k, s);
+    ps.finish();
+    if (he != hipSuccess) return fail(c, HG_ERR_HIP, "hg_detr_neck: launch failed: %s", hipGetErrorString(he));
+    return HG_OK;
+}
+
 }  // extern "C"

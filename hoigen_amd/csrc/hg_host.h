@@ -165,6 +165,14 @@ struct DetrHeads {       // hg_load_detr_heads: class_embed (rows gathered, padd
     float *bc = nullptr, *b0 = nullptr, *b1 = nullptr, *b2 = nullptr;
     std::vector<void*> owned;
 };
+struct DetrNeck {        // hg_load_detr_neck: input_proj's weight as fp16 [D, Cin], its bias, and the sine embedding's dim_t table [D / 2]
+    bool loaded = false;
+    int D = 0, Cin = 0, normalize = 0;
+    float scale = 0.f;
+    half_t* w = nullptr;
+    float *bias = nullptr, *dim_t = nullptr;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -180,6 +188,7 @@ struct hg_ctx {
     DetrEnc detr;
     DetrDec detr_dec;
     DetrHeads detr_heads;
+    DetrNeck detr_neck;
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
@@ -193,6 +202,7 @@ struct hg_ctx {
     Buf prebatch;        // hg_preprocess_batch: per-crop headers and weight tables, sized from n and n_px alone
     Buf detr_ws;         // hg_detr_encoder: the fp32 stream, the batch-major pos, and the fp16 operands x, x + pos, q | k, v, attention output, FFN hidden
     Buf detr_dec_ws;     // hg_detr_decoder: memory's fp16 copies and every layer's cross-attention K and V, the decoder stream and its fp16 operands, the split FFN's partial sums
+    Buf detr_neck_ws;    // hg_detr_neck: the fp32 partial sums of a split over Cin
     Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
@@ -238,6 +248,7 @@ struct hg_ctx {
                                      // 1 the two GEMMs, 2 the split kernel or HG_ERR_INVALID
     int opt_detr_ffn_max_m = 1000;   // ... rows (B * Q) up to which 0 picks the split kernel: it wins by 25 - 31 us a layer from 100 to 950 rows; at 2 888 rows
                                      // by 7 us, which is the spread of repeated runs (profiles/detr_decoder.txt)
+    int opt_detr_neck_split = 0;     // slices of Cin of hg_detr_neck's projection: 0 the rule of detr_neck_default_split (hg_detr.hip), 1 no split, n that many
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
     int n_cu = 256;
     // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became
@@ -265,7 +276,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws}
+     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

@@ -216,6 +216,31 @@ struct DetrHeadsArgs {
 bool detr_heads_ok(int D, int C1, int L, int B, int Q);
 hipError_t launch_detr_heads(const DetrHeadsArgs& a, hipStream_t s);
 
+// ---- DETR's neck (hg_detr_neck.hip): src = fp16(x) fp16(W)^T + bias, the key-padding mask on the feature grid and the sine embedding.
+// x fp32 [B, Cin, H W] through element strides x_sb (image) and x_sc (channel), token stride 1, no alignment beyond a float's; w fp16
+// [D, Cin] and bias fp32 [D] (16-byte aligned); image_mask bytes [B, Hi, Wi], non-zero = padded; dim_t fp32 [D / 2].  src and pos fp32
+// through element strides (image, token), channel stride 1; mask uint8 [B, H W]; pos and mask may be null.  nsplit slices of kslice =
+// Cin / nsplit channels (a multiple of 64) each: with nsplit > 1 the slices go to partial, fp32 [nsplit][B H W][D] (16-byte aligned), and
+// a second launch adds them in ascending order.  vec4: x and its strides allow 16-byte loads and H W is a multiple of 4; ovec4: src and
+// its strides allow 16-byte stores.  A shape outside detr_neck_ok: hipErrorInvalidValue and nothing launched.
+static constexpr int DETR_NECK_TOKENS = 32, DETR_NECK_MAX_CIN = 4096, DETR_NECK_MAX_B = 64, DETR_NECK_MAX_IMG = 8192;
+struct DetrNeckArgs {
+    const float* x;
+    long long x_sb, x_sc;
+    const half_t* w;
+    const float *bias, *dim_t;
+    const unsigned char* image_mask;
+    float *src, *pos;
+    long long src_sb, src_ss, pos_sb, pos_ss;
+    unsigned char* mask;
+    float* partial;
+    float scale;
+    int Cin, D, B, H, W, Hi, Wi, normalize, nsplit, kslice, vec4, ovec4;
+};
+bool detr_neck_ok(int Cin, int D, int B, int H, int W, int Hi, int Wi);
+inline size_t detr_neck_partial_bytes(int nsplit, int B, int S, int D) { return nsplit > 1 ? (size_t)nsplit * B * S * D * 4 : 0; }
+hipError_t launch_detr_neck(const DetrNeckArgs& a, hipStream_t s);
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

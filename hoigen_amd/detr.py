@@ -7,8 +7,10 @@ hg_detr_decoder).
 
 is the whole integration; the two halves can be swapped on their own as well.  ``DetectionHeads`` is what follows the
 transformer in the detector (upt_tip_cache_model_free_finetune_distill3.py:1598-1605): ``class_embed``, ``bbox_embed`` with its sigmoid
-and ``PostProcess`` in one launch (hg_detr_heads.hip: hg_load_detr_heads, hg_detr_heads).  Inference only; tensors must live on a HIP
-device.
+and ``PostProcess`` in one launch (hg_detr_heads.hip: hg_load_detr_heads, hg_detr_heads).  ``DetectorNeck`` is what precedes it
+(upt...:1594-1597): ``input_proj``, ``PositionEmbeddingSine`` and the mask on the feature grid in one call (hg_detr_neck.hip:
+hg_load_detr_neck, hg_detr_neck), whose batch-first outputs ``Transformer.forward_tokens`` takes; ``Detector`` is lines 1594-1605 as one
+object.  Inference only; tensors must live on a HIP device.
 """
 from __future__ import annotations
 
@@ -378,6 +380,27 @@ class Transformer(nn.Module):
         self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
         return hs, mem.permute(0, 2, 1).view(B, Cc, H, W)
 
+    @_inference_only
+    @torch.no_grad()
+    def forward_tokens(self, src, mask, query_embed, pos, hw):
+        """``forward`` on what ``DetectorNeck`` returns: ``src`` and ``pos`` batch-first ``[B, S, C]`` fp32 with channel stride 1,
+        ``mask [B, S]``, ``hw = (H, W)`` with H W = S.  Encoder and decoder read both through strides, so nothing is transposed or
+        copied.  Returns what ``forward`` returns: ``(hs [L, B, Q, C], memory [B, C, H, W])``."""
+        _require_cuda(src, "Transformer src")
+        H, W = (int(v) for v in hw)
+        if src.dim() != 3 or src.shape[2] != self.d_model or pos.shape != src.shape or src.shape[1] != H * W:
+            raise RuntimeError(f"hoigen_amd: Transformer.forward_tokens: src and pos must be [B, S = H W = {H * W}, {self.d_model}] "
+                               f"(got {tuple(src.shape)}, {tuple(pos.shape)})")
+        B, S, Cc = src.shape
+        kpm = mask.reshape(B, S) if mask is not None else None
+        mem = torch.empty(B, S, Cc, device=src.device, dtype=torch.float32)
+        pos_s = pos.permute(1, 0, 2)
+        self.encoder._run(src.permute(1, 0, 2), None, kpm, pos_s, False, mem.permute(1, 0, 2))
+        L = self.decoder.num_layers if self.decoder.return_intermediate else 1
+        hs = torch.empty(L, B, query_embed.shape[0], Cc, device=src.device, dtype=torch.float32)
+        self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
+        return hs, mem.permute(0, 2, 1).view(B, Cc, H, W)
+
 
 class BoxMLP(nn.Module):
     """Parameters of the reference's ``MLP(D, D, 4, 3)`` (detr/models/detr.py:293-305): ``layers.{0,1,2}.weight`` / ``bias``."""
@@ -511,3 +534,175 @@ class DetectionHeads(nn.Module):
         if with_outputs:
             return results, {"pred_logits": logits[-1], "pred_boxes": pboxes[-1]}
         return results
+
+
+class DetectorNeck(nn.Module):
+    """What stands between the detector's ResNet body and its transformer (upt_tip_cache_model_free_finetune_distill3.py:1594-1597) in
+    one native call (hoigen_amd/csrc/hg_detr_neck.hip: hg_load_detr_neck, hg_detr_neck): the padding mask on the feature grid
+    (detr/models/backbone.py:78), ``PositionEmbeddingSine`` (detr/models/position_encoding.py:28-48), ``input_proj``
+    (detr/models/detr.py:40, :65) and the flatten / permute of detr/models/transformer.py:50-51 - the outputs are batch-first, which is
+    what ``Transformer.forward_tokens`` takes.
+
+        neck = DetectorNeck.from_modules(self.detector.input_proj, self.detector.backbone[1])
+        src, pos, mask, hw = neck(features, image_mask)
+
+    Parameters ``input_proj.weight`` ``[D, Cin, 1, 1]`` / ``bias``, the detector's own keys.  Inference only; tensors must live on a HIP
+    device."""
+
+    def __init__(self, in_channels: int = 2048, d_model: int = 256, num_pos_feats: Optional[int] = None, temperature: float = 10000.0,
+                 normalize: bool = True, scale: Optional[float] = None):
+        super().__init__()
+        import math
+        self.in_channels, self.d_model = int(in_channels), int(d_model)
+        self.num_pos_feats = self.d_model // 2 if num_pos_feats is None else int(num_pos_feats)
+        self.temperature, self.normalize = float(temperature), bool(normalize)
+        self.scale = 2 * math.pi if scale is None else float(scale)
+        self.input_proj = nn.Conv2d(self.in_channels, self.d_model, kernel_size=1)      # a parameter holder: never called
+        self._ctx = _Ctx()
+        self._sig = None
+
+    @classmethod
+    def from_modules(cls, input_proj: nn.Module, position_embedding: nn.Module) -> "DetectorNeck":
+        """From the reference's ``input_proj`` (an ``nn.Conv2d(Cin, D, kernel_size=1)``) and ``PositionEmbeddingSine`` (or any module
+        with its attributes ``num_pos_feats``, ``temperature``, ``normalize``, ``scale``)."""
+        missing = [k for k in ("num_pos_feats", "temperature", "normalize", "scale") if not hasattr(position_embedding, k)]
+        if missing:
+            raise RuntimeError(f"hoigen_amd: DetectorNeck.from_modules: the position embedding ({type(position_embedding).__name__}) has no "
+                               f"{missing}: only PositionEmbeddingSine (position_encoding.py:12-48) is implemented, not the learned embedding")
+        w = getattr(input_proj, "weight", None)
+        if w is None or w.dim() != 4 or tuple(w.shape[2:]) != (1, 1):
+            raise RuntimeError("hoigen_amd: DetectorNeck.from_modules: input_proj must be a 1 x 1 convolution with a [D, Cin, 1, 1] weight "
+                               f"(got {None if w is None else tuple(w.shape)})")
+        pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if pair(getattr(input_proj, "stride", 1)) != (1, 1) or getattr(input_proj, "groups", 1) != 1 or \
+                pair(getattr(input_proj, "padding", 0)) != (0, 0) or pair(getattr(input_proj, "dilation", 1)) != (1, 1):
+            raise RuntimeError("hoigen_amd: DetectorNeck.from_modules: input_proj must have stride 1, groups 1, no padding and no dilation "
+                               f"(got stride {input_proj.stride}, groups {input_proj.groups}, padding {input_proj.padding}): only the "
+                               "1 x 1 projection of detr/models/detr.py:40 is implemented")
+        if getattr(input_proj, "bias", None) is None:
+            raise RuntimeError("hoigen_amd: DetectorNeck.from_modules: input_proj has no bias; detr/models/detr.py:40 builds it with one")
+        D, Cin = int(w.shape[0]), int(w.shape[1])
+        if int(position_embedding.num_pos_feats) != D // 2 or D % 2:
+            raise RuntimeError(f"hoigen_amd: DetectorNeck.from_modules: num_pos_feats = {position_embedding.num_pos_feats}, and input_proj "
+                               f"has {D} output channels: pos and src are added, so num_pos_feats must be out_channels / 2")
+        m = cls(Cin, D, position_embedding.num_pos_feats, position_embedding.temperature, position_embedding.normalize,
+                position_embedding.scale)
+        m.input_proj.load_state_dict({"weight": w.detach(), "bias": input_proj.bias.detach()})
+        m.to(device=w.device, dtype=w.dtype)
+        m.train(input_proj.training)
+        return m
+
+    def set_option(self, key: str, value: int) -> None:
+        """Behaviour option of this module's native context (include/hoigen_amd.h), e.g. ``detr_neck_split``."""
+        self._ctx.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self._ctx.get_option(key)
+
+    def _load(self, device: torch.device) -> int:
+        h = self._ctx.get(device)
+        sig = (h, _sig(self.parameters()), self.num_pos_feats, self.temperature, self.normalize, self.scale)
+        if sig != self._sig:
+            t = lambda p: _lib.tensor(p.detach().contiguous())
+            w = _lib.hg_detr_neck_weights(t(self.input_proj.weight), t(self.input_proj.bias), self.in_channels, self.d_model,
+                                          self.num_pos_feats, self.temperature, int(self.normalize), self.scale)
+            self._ctx.check(_lib.lib().hg_load_detr_neck(h, C.byref(w)), "hg_load_detr_neck")
+            self._sig = sig
+        return h
+
+    def _run(self, features, image_mask, want_pos: bool = True, want_mask: bool = True, out=None):
+        _require_cuda(features, "DetectorNeck features")
+        if features.dim() != 4 or features.shape[1] != self.in_channels:
+            raise RuntimeError(f"hoigen_amd: DetectorNeck: features must be [B, {self.in_channels}, H, W] (got {tuple(features.shape)})")
+        B, _, H, W = features.shape
+        S = H * W
+        if S > MAX_TOKENS:
+            raise RuntimeError(f"hoigen_amd: DetectorNeck: a {H} x {W} grid is {S} tokens, at most {MAX_TOKENS}")
+        x = features.detach()
+        if x.dtype != torch.float32 or x.stride(3) != 1 or x.stride(2) != W:      # tokens must be contiguous within a channel: never transposed
+            x = x.to(torch.float32).contiguous()
+        im = None
+        if want_pos or want_mask:
+            if image_mask is None or image_mask.dim() != 3 or image_mask.shape[0] != B:
+                raise RuntimeError(f"hoigen_amd: DetectorNeck: image_mask must be [B = {B}, Hi, Wi] "
+                                   f"(got {None if image_mask is None else tuple(image_mask.shape)})")
+            _require_cuda(image_mask, "DetectorNeck image_mask")
+            if image_mask.dtype not in (torch.bool, torch.uint8):
+                raise RuntimeError(f"hoigen_amd: DetectorNeck: image_mask must be bool or uint8 (got {image_mask.dtype})")
+            im = image_mask.detach().contiguous()
+        h = self._load(x.device)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        D = self.d_model
+        src, pos, mask = out if out is not None else (None, None, None)
+        src = torch.empty(B, S, D, **f32) if src is None else src
+        pos = (torch.empty(B, S, D, **f32) if pos is None else pos) if want_pos else None
+        mask = (torch.empty(B, S, device=x.device, dtype=torch.bool) if mask is None else mask) if want_mask else None
+        for name, t in (("src", src), ("pos", pos)):
+            if t is not None and (tuple(t.shape) != (B, S, D) or t.dtype != torch.float32 or t.stride(2) != 1 or t.device != x.device):
+                raise RuntimeError(f"hoigen_amd: DetectorNeck: {name} must be an fp32 [B, S, C] tensor (or view) on the features' device with channel stride 1")
+        a = _lib.hg_detr_neck_args()
+        a.x, a.B, a.H, a.W = x.data_ptr(), B, H, W
+        a.x_stride[:] = [x.stride(0), x.stride(1), x.stride(3)]
+        if im is not None:
+            a.image_mask, a.Hi, a.Wi = im.data_ptr(), im.shape[1], im.shape[2]
+        a.src = src.data_ptr()
+        a.src_stride[:] = [src.stride(0), src.stride(1)]
+        if pos is not None:
+            a.pos = pos.data_ptr()
+            a.pos_stride[:] = [pos.stride(0), pos.stride(1)]
+        if mask is not None:
+            if tuple(mask.shape) != (B, S) or mask.dtype not in (torch.bool, torch.uint8) or not mask.is_contiguous():
+                raise RuntimeError("hoigen_amd: DetectorNeck: mask must be a contiguous bool or uint8 [B, S] tensor")
+            a.mask = mask.data_ptr()
+        self._ctx.check(_lib.lib().hg_detr_neck(h, C.byref(a), _stream_ptr(x.device)), "hg_detr_neck")
+        return src, pos, mask, (H, W)
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, features, image_mask):
+        """``features [B, Cin, H, W]`` (the body's map; fp32 with contiguous tokens is read where it lies, anything else is converted
+        once), ``image_mask [B, Hi, Wi]`` bool or uint8 (the NestedTensor's).  Returns ``(src [B, S, D], pos [B, S, D], mask bool [B, S],
+        (H, W))``."""
+        return self._run(features, image_mask)
+
+
+class Detector(nn.Module):
+    """The detector's forward at upt_tip_cache_model_free_finetune_distill3.py:1594-1605 as one object: the backbone's body stays the
+    torch module it is, and ``DetectorNeck``, ``Transformer`` and ``DetectionHeads`` run behind it on one native context.
+
+        det = Detector.from_module(self.detector, reserve_indices)
+        results, hs, memory = det(images.tensors, images.mask, image_sizes)
+
+    ``body``: any module mapping ``[B, 3, Hi, Wi]`` to ``[B, Cin, H, W]`` or to the ``{'0': ...}`` dict ``IntermediateLayerGetter``
+    returns.  ``query_embed``: the detector's ``nn.Embedding`` (its ``weight`` is read)."""
+
+    def __init__(self, body: nn.Module, neck: DetectorNeck, transformer: Transformer, heads: DetectionHeads, query_embed: nn.Module):
+        super().__init__()
+        self.body, self.neck, self.transformer, self.heads, self.query_embed = body, neck, transformer, heads, query_embed
+        transformer.decoder._ctx = heads._ctx = neck._ctx = transformer.encoder._ctx
+
+    @classmethod
+    def from_module(cls, detr: nn.Module, reserve_indices=None) -> "Detector":
+        backbone = detr.backbone
+        m = cls(backbone[0].body, DetectorNeck.from_modules(detr.input_proj, backbone[1]), Transformer.from_module(detr.transformer),
+                DetectionHeads.from_modules(detr.class_embed, detr.bbox_embed, reserve_indices), detr.query_embed)
+        m.train(detr.training)
+        return m
+
+    def set_option(self, key: str, value: int) -> None:
+        self.neck.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self.neck.get_option(key)
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, tensors, mask, image_sizes):
+        """``tensors [B, 3, Hi, Wi]`` and ``mask [B, Hi, Wi]`` of the NestedTensor, ``image_sizes``: (h, w) per image as
+        ``DetectionHeads.detect`` takes them.  Returns ``(results, hs [L, B, Q, C], memory [B, C, H, W])``."""
+        feats = self.body(tensors)
+        if isinstance(feats, dict):
+            feats = feats[sorted(feats)[-1]]      # the last level: IntermediateLayerGetter's {'0': layer4}
+        src, pos, kpm, hw = self.neck._run(feats, mask)
+        hs, memory = self.transformer.forward_tokens(src, kpm, self.query_embed.weight, pos, hw)
+        return self.heads.detect(hs, image_sizes), hs, memory

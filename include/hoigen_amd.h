@@ -610,6 +610,53 @@ typedef struct {
     float* boxes;
 } hg_detr_heads_args;
 int hg_detr_heads(hg_ctx*, const hg_detr_heads_args* args, void* stream);
+
+/* ---- DETR neck: what stands between the ResNet body and the transformer (upt_tip_cache_model_free_finetune_distill3.py:1594-1597:
+ * the padding mask on the feature grid, detr/models/backbone.py:78; PositionEmbeddingSine.forward, detr/models/position_encoding.py:28-48;
+ * input_proj, detr/models/detr.py:40 and :65; the flatten(2).permute(2, 0, 1) of detr/models/transformer.py:50-51) in one call
+ * (hoigen_amd/csrc/hg_detr_neck.hip) ----------------------------------------------------------------------------------------------------
+ *
+ * hg_load_detr_neck (detr.py:40, position_encoding.py:17-26): a slot of its own beside the encoder's, the decoder's and the heads'.
+ * weight is input_proj.weight, [d_model, cin] or the conv's [d_model, cin, 1, 1] (the same bytes), bias [d_model].  The fp16 copy of the
+ * weight and the table dim_t[i] = fp32(temperature ** (2 * (i / 2) / num_pos_feats)) (position_encoding.py:37-38, computed on the
+ * host in double) are made here.  Synchronous.  HG_ERR_INVALID with a message for d_model outside {128, 256}, cin no multiple of 64 or
+ * above 4096, num_pos_feats != d_model / 2, a temperature <= 0 (the slot keeps what it held), a missing tensor or a dtype other than
+ * fp32 / fp16. */
+typedef struct {
+    hg_tensor weight, bias;
+    int32_t cin, d_model, num_pos_feats;
+    float temperature;
+    int32_t normalize;                     /* position_encoding.py:21 */
+    float scale;                           /* position_encoding.py:26: 2 pi where the module was given none */
+} hg_detr_neck_weights;
+int hg_load_detr_neck(hg_ctx*, const hg_detr_neck_weights*);
+/* hg_detr_neck (upt...:1594-1597).  x: the body's map, DEVICE fp32 [B, cin, H, W] through element strides x_stride = (image, channel,
+ * token); the token stride must be 1, nothing else is assumed - no alignment beyond a float's - and x is read where it lies, never
+ * copied.  image_mask: the NestedTensor's mask, DEVICE bytes [B, Hi, Wi] contiguous (uint8 or bool), non-zero = padded.
+ *   src [B, H W, d_model]   fp32 through src_stride = (image, token) in elements, channel stride 1 (the [S, B, C] view works too):
+ *                           fp16(x[b, :, s]) . fp16(W)^T + bias, fp32 accumulation (detr.py:65 with transformer.py:50)
+ *   pos [B, H W, d_model]   fp32 likewise through pos_stride, nullable: PositionEmbeddingSine on the downsampled mask, every operation
+ *                           of the argument rounded once in fp32 in the reference's order, then sinf / cosf (transformer.py:51)
+ *   mask [B, H W]           uint8 contiguous, 1 = padded, nullable: F.interpolate(m[None].float(), size=(H, W)).to(bool)[0] bit for bit -
+ *                           source row min((int)floorf(y * ((float)Hi / (float)H)), Hi - 1), columns likewise (backbone.py:78)
+ * A null pos or mask is not computed; image_mask, Hi and Wi are read only where one of them is wanted.  Asynchronous on `stream`; no
+ * host wait; the workspace (the partial sums of a split, option "detr_neck_split") is grow-only.  For a given shape and option value the
+ * result is a fixed function of the inputs.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message and nothing launched for B
+ * outside 1 .. 64, H W outside 1 .. 1792, Hi or Wi outside 1 .. 8192, a token stride of x other than 1, a null x or src, pos or mask
+ * without image_mask, and a detr_neck_split the loaded cin does not admit. */
+typedef struct {
+    const float* x;
+    int64_t x_stride[3];                   /* elements: image, channel, token (= 1) */
+    const uint8_t* image_mask;
+    int32_t Hi, Wi;
+    int32_t B, H, W;
+    float* src;
+    int64_t src_stride[2];                 /* elements: image, token */
+    float* pos;
+    int64_t pos_stride[2];
+    uint8_t* mask;
+} hg_detr_neck_args;
+int hg_detr_neck(hg_ctx*, const hg_detr_neck_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -699,6 +746,10 @@ int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, 
  *                      GEMMs; 2 always the split kernel (a shape it does not cover: HG_ERR_INVALID).  hg_detr_encoder never uses it.
  *   "detr_ffn_max_m"  [HG_DETR_FFN_MAX_M]  rows (B * Q) up to which detr_ffn = 0 picks the split kernel (default 1000: measured faster by 25 - 31 us a layer
  *                      from 100 to 950 rows, by no more than the spread of repeated runs at 2 888: profiles/detr_decoder.txt)
+ *   "detr_neck_split" [HG_DETR_NECK_SPLIT] slices of cin over which hg_detr_neck's projection is split (hoigen_amd/csrc/hg_detr_neck.hip): 0 (default) a rule
+ *                      by the number of 32-token tiles (profiles/detr_neck.txt); 1 no split, one launch; n = 2 .. 64:
+ *                      n slices, whose fp32 partial sums a second launch adds in ascending order.  cin must be n multiples of 64, else the
+ *                      calls that use it return HG_ERR_INVALID.  For one shape and value the result is a fixed function of the inputs.
  *   "chunk_rows"      [HG_CHUNK_ROWS]      rows per VAE / mlp_net / cache-logits chunk (>= 256; default 32768; the last chunk of a
  *                      call absorbs a tail of up to an eighth of it)
  * Unknown keys and out-of-range values return HG_ERR_INVALID. */
@@ -722,6 +773,7 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_VAE_FUSED 102 /* CoOp-VAE as one kernel: M = rows, N = passes per item (3 Encoder + Generator, 2 Encoder, 1 Generator), K = hidden width of the first pass */
 #define HG_PROF_DETR_FFN 104  /* the DETR decoder's split FFN kernel: M = rows, N = d_ff, K = d_model */
 #define HG_PROF_DETR_ROWS 105 /* row kernels of hg_detr_decoder (entries, post-norms, tails): M = rows, N = d_model, K = slices summed */
+#define HG_PROF_DETR_NECK 106 /* hg_detr_neck's launch(es): M = rows (B * H * W), N = slices of cin, K = cin */
 #define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
