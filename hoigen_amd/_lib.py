@@ -237,6 +237,10 @@ class hg_test_elem_args(C.Structure):
     _fields_ = [("p", C.c_void_p * 9), ("n", C.c_uint64), ("i", C.c_int32 * 6)]
 
 
+class hg_test_detr_rows_args(C.Structure):
+    _fields_ = [("p", C.c_void_p * 12), ("s", C.c_int64 * 4), ("i", C.c_int32 * 4)]
+
+
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
 
@@ -301,6 +305,7 @@ SIGNATURES = {
     "hg_test_text_stream": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "hg_test_adapter": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_elem": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
+    "hg_test_detr_rows": (_I, [_P, _I, C.POINTER(hg_test_detr_rows_args), _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

@@ -530,4 +530,31 @@ int hg_test_elem(hg_ctx* c, int op, const hg_test_elem_args* x, void* stream) {
     return HG_OK;
 }
 
+// One launcher of hg_detr_rows.hip with the caller's own device buffers (include/hoigen_amd.h has the table of operands;
+// tests/test_gpu_detr_rows.py, tests/test_gpu_detr_wiring.py).
+int hg_test_detr_rows(hg_ctx* c, int op, const hg_test_detr_rows_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x) return fail(c, HG_ERR_INVALID, "hg_test_detr_rows: args are required");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    void* const* p = x->p;
+    const int64_t* st = x->s;
+    const int32_t* i = x->i;
+    auto F = [&](int k) { return (float*)p[k]; };
+    auto H = [&](int k) { return (half_t*)p[k]; };
+    hipError_t e;
+    switch (op) {
+        case 0: e = launch_detr_entry(F(0), F(1), st[0], st[1], st[2], st[3], i[0], i[1], i[2], F(2), H(3), H(4), F(5), s); break;
+        case 1: e = launch_detr_postnorm(F(0), F(1), F(2), F(3), H(4), H(5), F(6), i[0], i[1], s); break;
+        case 2: e = launch_detr_exit(F(0), F(1), st[0], st[1], i[0], i[1], i[2], s); break;
+        case 3: e = launch_detr_dec_entry(F(0), st[0], st[1], F(1), st[2], st[3], i[0], i[1], i[2], F(2), H(3), H(4), F(5), s); break;
+        case 4: e = launch_detr_dec_tail(F(0), F(1), F(2), i[0], F(3), F(4), F(5), H(6), H(7), F(8), F(9), F(10), F(11), st[0], st[1], i[1], i[2],
+                                         i[3], s); break;
+        default: return fail(c, HG_ERR_INVALID, "hg_test_detr_rows: op must be 0 .. 4");
+    }
+    if (e == hipErrorInvalidValue) return fail(c, HG_ERR_INVALID, "hg_test_detr_rows: op %d refused by its launcher: %s", op, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_detr_rows: op %d failed: %s", op, hipGetErrorString(e));
+    return HG_OK;
+}
+
 }  // extern "C"

@@ -979,6 +979,26 @@ typedef struct {
 } hg_test_elem_args;
 int hg_test_elem(hg_ctx*, int op, const hg_test_elem_args* args, void* stream);
 
+/* Test hook for the row kernels of the DETR encoder and decoder (hoigen_amd/csrc/hg_detr_rows.hip): ONE launch_detr_* call with the
+ * caller's device pointers, in the kernels' own types (fp32, fp16 - nothing is converted on the way), on the caller's stream.  No
+ * workspace of the context is used, no option read, no loaded model touched.  HG_ERR_INVALID, with the HIP error in hg_last_error, where
+ * the launcher refuses the call (nothing was launched then); HG_ERR_HIP for any other HIP error.  Unused pointers are NULL, unused
+ * strides and ints 0.  The vector kernels (1, 4) ask 16-byte alignment of every pointer but copy and out (a float's).
+ *   op            p[0 ..]                                                                      s[0 ..] (elements)   i[0 ..]
+ *   0  entry      src, pos, x, x16 (fp16), xp16 (fp16), posb                                   sb, ss, pb, ps       B, S, D
+ *   1  postnorm   x (in place), w, b, posb, x16 (fp16), xp16 (fp16), copy                                           M, D
+ *   2  exit       x, out                                                                       ob, os               B, S, D
+ *   3  dec_entry  tgt, qpos, x, x16 (fp16), xp16 (fp16), qposb                                 tb, tq, qb, qq       B, Q, D
+ *   4  dec_tail   x (in place), b2, partial, w3, b3, qposb, x16 (fp16), xp16 (fp16), copy,     ob, oq               n_slices, Q, M, D
+ *                 wf, bf, out
+ * (pointers fp32 where no type is given; the launchers' own argument names, hoigen_amd/csrc/hg_kernels.h) */
+typedef struct {
+    void* p[12];
+    int64_t s[4];
+    int32_t i[4];
+} hg_test_detr_rows_args;
+int hg_test_detr_rows(hg_ctx*, int op, const hg_test_detr_rows_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,13 @@ from hoigen_amd import synth
 
 FULL = dict(d_model=256, heads=8, d_ff=2048, layers=6)          # the detector's encoder
 SMALL = dict(d_model=128, heads=4, d_ff=256, layers=2)
+
+
+def wide(d_model):
+    """one layer at a width beyond the detector's: 384 (12 heads), 512 (16), 640 (20; the encoder alone), d_ff 256"""
+    return dict(d_model=d_model, heads=d_model // 32, d_ff=256, layers=1)
+
+
 # the fixture's case (tests/golden/make_golden_detr_encoder.py): B = 3 on a 13 x 17 grid; image 0 unpadded, 1 visible on 10 x 12, 2 on 4 x 5
 G18 = dict(B=3, gh=13, gw=17, visible=((13, 17), (10, 12), (4, 5)), wseed=18, xseed=180)
 

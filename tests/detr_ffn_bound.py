@@ -162,12 +162,14 @@ def _to_f16(v, truncate=False, flush=False):
 
 
 def _wave_ln(v, g, b):
-    """LayerNorm of the rows of v [M, D] fp32 as one wave computes it (D a multiple of 4 up to 512)"""
+    """LayerNorm of the rows of v [M, D] fp32 as one wave computes it (D a multiple of 4: two pieces a lane up to 512 - the tail's
+    registers -, and as many as detr_postnorm_kernel's `i += 64` loops make trips beyond)"""
     M, D = v.shape
     n4 = D // 4
-    lanes = np.zeros((M, 2, 64, 4), np.float32)      # [row, piece t, lane, e]: column 4 (lane + 64 t) + e
-    lanes.reshape(M, 128, 4)[:, :n4] = v.reshape(M, n4, 4)
-    have = (np.arange(128) < n4).reshape(2, 64)
+    P = max(2, -(-n4 // 64))
+    lanes = np.zeros((M, P, 64, 4), np.float32)      # [row, piece t, lane, e]: column 4 (lane + 64 t) + e
+    lanes.reshape(M, P * 64, 4)[:, :n4] = v.reshape(M, n4, 4)
+    have = (np.arange(P * 64) < n4).reshape(P, 64)
 
     def wsum(x):
         for o in (32, 16, 8, 4, 2, 1):
@@ -175,12 +177,12 @@ def _wave_ln(v, g, b):
         return x[:, :1]
 
     s = np.zeros((M, 64), np.float32)
-    for t in range(2):
+    for t in range(P):
         p = (lanes[:, t, :, 0] + lanes[:, t, :, 1]) + (lanes[:, t, :, 2] + lanes[:, t, :, 3])
         s = np.where(have[t], s + p, s)
     mean = wsum(s) / np.float32(D)
     sq = np.zeros((M, 64), np.float32)
-    for t in range(2):
+    for t in range(P):
         for e in range(4):
             dd = lanes[:, t, :, e] - mean
             sq = np.where(have[t], _fma(dd, dd, sq), sq)

@@ -78,6 +78,20 @@ def test_small_lengths_every_mask_within_the_bound(ctx, family):
     assert not fails, "\n".join(fails)
 
 
+@pytest.mark.parametrize("heads", (8, 16))
+def test_the_detectors_head_counts_within_the_bound(ctx, heads):
+    """8 heads (the detector) and 16 (d_model 512): the (sequence, head) decomposition of the block index, held to the per-element bound"""
+    top, where, fails = 0.0, None, []
+    for family in ("randn", "ramp"):
+        for L in (33, 97):
+            w, f = one_case(ctx, family, 2, L, L, heads, "rect", ldo=heads * 32 + 8)
+            fails += f
+            if w > top:
+                top, where = w, (family, L)
+    print(f"DETR_ATTN_RATIO heads {heads} n_seq 2 L 33, 97 rect: worst |err| / B {top:.3f} at {where}")
+    assert not fails, "\n".join(fails)
+
+
 @pytest.mark.parametrize("family", db.FAMILIES)
 def test_large_lengths_within_the_bound(ctx, family):
     """the resident form up to 1 280 keys, the chunked form beyond; each length under the rectangle mask and one more"""

@@ -83,6 +83,45 @@ def test_small_model_every_layer_against_fp64(small, gh, gw):
     print(f"DETR_DEC small {gh}x{gw}: worst rel L2 (tensor or row, any layer) {worst:.2e}")
 
 
+@pytest.mark.parametrize("d_model", (384, 512))
+def test_wider_models_against_fp64(d_model):
+    """d_model 384 and 512 (12 and 16 heads; one layer, d_ff 256), the widths hg_load_detr_decoder takes beyond the detector's: the
+    tail's second register piece (partly filled at 384), the stacked K / V GEMMs, on the default FFN rule and on the two GEMMs, with
+    and without the memory's pos"""
+    cfg = ec.wide(d_model)
+    m, sd = build(cfg, 50 + d_model // 128)
+    B, gh, gw, Q = 2, 5, 7, 33
+    qe, mem, pos = dd.inputs(B, gh, gw, Q, d_model, 500 + d_model)
+    mask = ec.mask_of("rect", B, gh, gw)
+    try:
+        for option in (0, 1):
+            m.set_option("detr_ffn", option)
+            for p in (pos, None):
+                want_s, want_hs = dd.decoder_fp64(sd, cfg, mem, p, mask, qe)
+                hs, trace = m.forward_trace(None, dev(mem), memory_key_padding_mask=dev(mask), pos=dev(p), query_pos=dev(qe))
+                worst = check_all(hs, trace, want_s, want_hs, f"d_model {d_model} detr_ffn {option} pos {p is not None}")
+                print(f"DETR_DEC d_model {d_model} heads {cfg['heads']} detr_ffn {option} pos {p is not None}: worst rel L2 {worst:.2e}")
+    finally:
+        m.set_option("detr_ffn", 0)
+
+
+@pytest.mark.parametrize("option", [1, 2])
+def test_memory_pos_none_against_fp64(small, option):
+    m, sd = small
+    cfg = dd.SMALL
+    m.set_option("detr_ffn", option)
+    try:
+        for Q, B, kind in ((1, 1, "none"), (33, 3, "rect"), (33, 2, "perimage")):
+            qe, mem, _ = dd.inputs(B, 5, 7, Q, cfg["d_model"], 60 + Q + B)
+            mask = ec.mask_of(kind, B, 5, 7)
+            want_s, want_hs = dd.decoder_fp64(sd, cfg, mem, None, mask, qe)
+            hs, trace = m.forward_trace(None, dev(mem), memory_key_padding_mask=dev(mask), pos=None, query_pos=dev(qe))
+            worst = check_all(hs, trace, want_s, want_hs, f"memory pos None Q {Q} B {B} {kind} detr_ffn {option}")
+            print(f"DETR_DEC small memory pos None Q {Q} B {B} {kind} detr_ffn {option}: worst rel L2 {worst:.2e}")
+    finally:
+        m.set_option("detr_ffn", 0)
+
+
 @pytest.mark.parametrize("option", [1, 2])
 def test_an_image_without_a_visible_memory_token_is_nan_alone(small, option):
     m, sd = small

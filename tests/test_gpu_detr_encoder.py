@@ -71,6 +71,37 @@ def test_small_model_every_layer_against_fp64(small, gh, gw):
     print(f"DETR_ENC small {gh}x{gw}: worst rel L2 (tensor or row, any layer) {worst:.2e}")
 
 
+@pytest.mark.parametrize("d_model", (384, 512, 640))
+def test_wider_models_against_fp64(d_model):
+    """d_model 384, 512 and 640 (12, 16 and 20 heads; one layer, d_ff 256): the second and third trips of the post-norm's loops, the GEMMs
+    at N = 768 .. 1280 and the attention's head counts, with and without pos.  hg_load_detr_encoder takes every multiple of 128: 640
+    stands for the widths beyond the decoder's 512."""
+    cfg = dc.wide(d_model)
+    m, sd = build(cfg, 30 + d_model // 128)
+    B, gh, gw = 2, 5, 7
+    src, pos = dc.inputs(B, gh, gw, d_model, 300 + d_model)
+    mask = dc.mask_of("rect", B, gh, gw)
+    for p in (pos, None):
+        want = dc.encoder_fp64(sd, cfg, src, p, mask)
+        out, trace = m.forward_trace(dev(src), src_key_padding_mask=dev(mask), pos=dev(p))
+        worst = check_trace(trace, want, f"d_model {d_model} pos {p is not None}")
+        assert torch.equal(out.transpose(0, 1).reshape(-1, d_model), trace[-1])
+        print(f"DETR_ENC d_model {d_model} heads {cfg['heads']} pos {p is not None}: worst rel L2 (tensor or row) {worst:.2e}")
+
+
+@pytest.mark.parametrize("kind", ("none", "rect", "perimage"))
+def test_pos_none_against_fp64(small, kind):
+    m, sd = small
+    cfg = dc.SMALL
+    for B, (gh, gw) in ((1, (5, 7)), (3, (13, 17))):
+        src, _ = dc.inputs(B, gh, gw, cfg["d_model"], 40 + B)
+        mask = dc.mask_of(kind, B, gh, gw)
+        want = dc.encoder_fp64(sd, cfg, src, None, mask)
+        _, trace = m.forward_trace(dev(src), src_key_padding_mask=dev(mask), pos=None)
+        worst = check_trace(trace, want, f"pos None B {B} {gh}x{gw} {kind}")
+        print(f"DETR_ENC small pos None B {B} {gh}x{gw} {kind}: worst rel L2 (tensor or row, any layer) {worst:.2e}")
+
+
 def test_full_width_against_the_reference_fixture(full):
     m, _ = full
     g, cfg = dc.G18, dc.FULL
