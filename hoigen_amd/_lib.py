@@ -219,6 +219,39 @@ class hg_detr_neck_args(C.Structure):
                 ("pos", C.c_void_p), ("pos_stride", C.c_int64 * 2), ("mask", C.c_void_p)]
 
 
+# limits of hg_load_resnet_stages / hg_resnet_stages (hoigen_amd/csrc/hg_kernels.h): channels, input channels of a 3 x 3, side, images, blocks
+HG_RESNET_MAX_C, HG_RESNET_MAX_C3, HG_RESNET_MAX_SIDE, HG_RESNET_MAX_B, HG_RESNET_MAX_BLOCKS = 2048, 512, 1024, 64, 64
+
+
+class hg_resnet_conv(C.Structure):
+    _fields_ = [("weight", C.c_void_p)] + [(n, C.c_int32) for n in ("cout", "cin", "kh", "kw", "stride_h", "stride_w", "pad_h", "pad_w",
+                                                                   "dil_h", "dil_w", "groups", "has_bias")]
+
+
+class hg_resnet_norm(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "bias", "running_mean", "running_var")] + [("eps", C.c_double)]
+
+
+class hg_resnet_block(C.Structure):
+    _fields_ = [(n, hg_resnet_conv) for n in ("conv1", "conv2", "conv3", "down_conv")] + \
+               [(n, hg_resnet_norm) for n in ("bn1", "bn2", "bn3", "down_bn")] + [("has_downsample", C.c_int32), ("ends_level", C.c_int32)]
+
+
+class hg_resnet_weights(C.Structure):
+    _fields_ = [("blocks", C.POINTER(hg_resnet_block)), ("n_blocks", C.c_int32)]
+
+
+class hg_resnet_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64 * 3), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("first_block", C.c_int32), ("last_block", C.c_int32), ("out", C.c_void_p), ("out_stride", C.c_int64 * 2),
+                ("trace", C.POINTER(C.c_void_p))]
+
+
+class hg_test_resnet_conv_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w", "scale", "bias", "identity", "out32", "out16")] + \
+               [(n, C.c_int32) for n in ("B", "H", "W", "cin", "cout", "k", "stride", "epi", "tile")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -243,6 +276,7 @@ class hg_test_detr_rows_args(C.Structure):
 
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
+HG_PROF_RESNET_CONV = 107
 
 _P = C.c_void_p
 _I = C.c_int
@@ -289,6 +323,9 @@ SIGNATURES = {
     "hg_detr_heads": (_I, [_P, C.POINTER(hg_detr_heads_args), _P]),
     "hg_load_detr_neck": (_I, [_P, C.POINTER(hg_detr_neck_weights)]),
     "hg_detr_neck": (_I, [_P, C.POINTER(hg_detr_neck_args), _P]),
+    "hg_load_resnet_stages": (_I, [_P, C.POINTER(hg_resnet_weights)]),
+    "hg_resnet_out_shape": (_I, [C.POINTER(hg_resnet_weights), _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "hg_resnet_stages": (_I, [_P, C.POINTER(hg_resnet_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -306,6 +343,7 @@ SIGNATURES = {
     "hg_test_adapter": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_elem": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
     "hg_test_detr_rows": (_I, [_P, _I, C.POINTER(hg_test_detr_rows_args), _P]),
+    "hg_test_resnet_conv": (_I, [_P, C.POINTER(hg_test_resnet_conv_args), _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

@@ -241,6 +241,32 @@ bool detr_neck_ok(int Cin, int D, int B, int H, int W, int Hi, int Wi);
 inline size_t detr_neck_partial_bytes(int nsplit, int B, int S, int D) { return nsplit > 1 ? (size_t)nsplit * B * S * D * 4 : 0; }
 hipError_t launch_detr_neck(const DetrNeckArgs& a, hipStream_t s);
 
+// ---- ResNet bottleneck convolutions (hg_resnet_conv.hip): out = epilogue(conv(x, w)) as one implicit GEMM over NHWC fp16 activations.
+// x fp16 [B, H, W, Cin]; w fp16 in fragment order (launch_resnet_pack from torch's fp32 [Cout, Cin, R, R]); scale, bias fp32 [Cout];
+// identity fp32 [B Ho Wo, Cout] (epi 3); out32 fp32 / out16 fp16 [B Ho Wo, Cout]; every pointer 16-byte aligned.  R in {1, 3}, stride in
+// {1, 2}, pad (R - 1) / 2, Ho / Wo = resnet_out_size.  epi 1 relu(fmaf) -> out16; 2 fmaf -> out32; 3 relu(fmaf + identity) -> both.
+// tile: output pixels of a work item, 0 = resnet_conv_tile's rule, else 32 or 128 (same bits either way).  A shape outside
+// resnet_conv_ok: hipErrorInvalidValue and nothing launched.
+static constexpr int RESNET_MAX_C = 2048, RESNET_MAX_C3 = 512, RESNET_MAX_SIDE = 1024, RESNET_MAX_B = 64, RESNET_MAX_BLOCKS = 64;
+struct ResnetConvArgs {
+    const half_t *x, *w;
+    const float *scale, *bias, *identity;
+    float* out32;
+    half_t* out16;
+    int B, H, W, Cin, Ho, Wo, Cout, R, stride, epi, tile;
+};
+inline int resnet_out_size(int H, int R, int stride) { return (H + 2 * ((R - 1) / 2) - R) / stride + 1; }
+bool resnet_conv_ok(const ResnetConvArgs& a);
+int resnet_conv_tile(long long M, int Cout);
+hipError_t launch_resnet_conv(const ResnetConvArgs& a, hipStream_t s);
+// w fp32 [Cout, Cin, R, R] -> the fp16 fragments; flag[0] = 1 where a weight is not finite or beyond fp16's range
+hipError_t launch_resnet_pack(const float* w, half_t* out, int Cout, int Cin, int R, int* flag, hipStream_t s);
+// x fp32 [B, C, H, W] through element strides (image, channel, row), column stride 1 -> fp32 and fp16 NHWC
+hipError_t launch_resnet_entry(const float* x, long long sb, long long sc, long long sr, int B, int C, int H, int W, float* o32, half_t* o16,
+                               hipStream_t s);
+// x fp32 NHWC [B, S, C] -> out fp32 [B, C, S] through element strides (image, channel), token stride 1
+hipError_t launch_resnet_exit(const float* x, int B, int C, int S, float* out, long long sb, long long sc, hipStream_t s);
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

@@ -1,0 +1,251 @@
+// The bottleneck stages of a ResNet on the HIP path (torchvision's Bottleneck under the reference's FrozenBatchNorm2d,
+// detr/models/backbone.py:19-55, :83-93): the weight loader, the output-shape rule and the block runner.  Host code only; the kernels
+// are in hg_resnet_conv.hip.
+#include "hg_host.h"
+
+namespace {
+
+const char* const kConvName[4] = {"conv1", "conv2", "conv3", "downsample.0"};
+const char* const kNormName[4] = {"bn1", "bn2", "bn3", "downsample.1"};
+
+const hg_resnet_conv& conv_of(const hg_resnet_block& b, int k) { return k == 0 ? b.conv1 : k == 1 ? b.conv2 : k == 2 ? b.conv3 : b.down_conv; }
+const hg_resnet_norm& norm_of(const hg_resnet_block& b, int k) { return k == 0 ? b.bn1 : k == 1 ? b.bn2 : k == 2 ? b.bn3 : b.down_bn; }
+
+// what the kernel covers, from the descriptor's integers alone
+int check_conv(hg_ctx* c, int blk, const char* name, const hg_resnet_conv& v) {
+    const char* f = "hg_load_resnet_stages: blocks[%d].%s: ";
+    char head[96];
+    snprintf(head, sizeof head, f, blk, name);
+    if (v.kh != v.kw || (v.kh != 1 && v.kh != 3)) return fail(c, HG_ERR_INVALID, "%sa %d x %d kernel; only 1 x 1 and 3 x 3 are implemented", head, v.kh, v.kw);
+    if (v.dil_h != 1 || v.dil_w != 1)
+        return fail(c, HG_ERR_INVALID, "%sdilation (%d, %d); only dilation 1 is implemented (the reference's --dilation, DC5, is off by default)", head,
+                    v.dil_h, v.dil_w);
+    if (v.groups != 1) return fail(c, HG_ERR_INVALID, "%sgroups = %d; only groups = 1 is implemented", head, v.groups);
+    if (v.has_bias) return fail(c, HG_ERR_INVALID, "%sthe convolution has a bias; a ResNet's convolutions have none", head);
+    if (v.stride_h != v.stride_w || (v.stride_h != 1 && v.stride_h != 2))
+        return fail(c, HG_ERR_INVALID, "%sstride (%d, %d); only 1 and 2, the same on both axes, are implemented", head, v.stride_h, v.stride_w);
+    if (v.pad_h != (v.kh - 1) / 2 || v.pad_w != (v.kh - 1) / 2)
+        return fail(c, HG_ERR_INVALID, "%spadding (%d, %d) under a %d x %d kernel; only (k - 1) / 2 is implemented", head, v.pad_h, v.pad_w, v.kh, v.kw);
+    if (v.cin < 64 || v.cin % 64 || v.cin > RESNET_MAX_C || v.cout < 64 || v.cout % 64 || v.cout > RESNET_MAX_C)
+        return fail(c, HG_ERR_INVALID, "%s%d -> %d channels; both must be multiples of 64 up to %d", head, v.cin, v.cout, RESNET_MAX_C);
+    if (v.kh == 3 && v.cin > RESNET_MAX_C3) return fail(c, HG_ERR_INVALID, "%sa 3 x 3 kernel over %d input channels, at most %d", head, v.cin, RESNET_MAX_C3);
+    return HG_OK;
+}
+
+int check_blocks(hg_ctx* c, const hg_resnet_weights* w) {
+    if (!w || !w->blocks) return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: weights are required");
+    if (w->n_blocks < 1 || w->n_blocks > RESNET_MAX_BLOCKS)
+        return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: %d blocks, 1 .. %d", w->n_blocks, RESNET_MAX_BLOCKS);
+    for (int i = 0; i < w->n_blocks; ++i) {
+        const hg_resnet_block& b = w->blocks[i];
+        for (int k = 0; k < (b.has_downsample ? 4 : 3); ++k) {
+            int rc = check_conv(c, i, kConvName[k], conv_of(b, k));
+            if (rc) return rc;
+        }
+        if (b.conv2.cin != b.conv1.cout || b.conv3.cin != b.conv2.cout)
+            return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d]: the channels do not chain (conv1 %d -> %d, conv2 %d -> %d, conv3 %d -> %d)", i,
+                        b.conv1.cin, b.conv1.cout, b.conv2.cin, b.conv2.cout, b.conv3.cin, b.conv3.cout);
+        const int stride = b.conv1.stride_h * b.conv2.stride_h * b.conv3.stride_h;
+        if (!b.has_downsample) {
+            if (b.conv3.cout != b.conv1.cin || stride != 1)
+                return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d] has no downsample, and maps %d channels to %d at stride %d: the identity does not fit",
+                            i, b.conv1.cin, b.conv3.cout, stride);
+        } else if (b.down_conv.cin != b.conv1.cin || b.down_conv.cout != b.conv3.cout || b.down_conv.stride_h != stride || b.down_conv.kh != 1) {
+            return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d].downsample.0 is %d x %d, %d -> %d at stride %d; the block needs 1 x 1, %d -> %d at stride %d",
+                        i, b.down_conv.kh, b.down_conv.kw, b.down_conv.cin, b.down_conv.cout, b.down_conv.stride_h, b.conv1.cin, b.conv3.cout, stride);
+        }
+        if (i && b.conv1.cin != w->blocks[i - 1].conv3.cout)
+            return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d] takes %d channels, blocks[%d] gives %d", i, b.conv1.cin, i - 1,
+                        w->blocks[i - 1].conv3.cout);
+        for (int k = 0; k < (b.has_downsample ? 4 : 3); ++k) {
+            const hg_resnet_norm& n = norm_of(b, k);
+            if (!conv_of(b, k).weight || !n.weight || !n.bias || !n.running_mean || !n.running_var)
+                return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d]: missing tensor of %s / %s", i, kConvName[k], kNormName[k]);
+            if (!(n.eps >= 0.0) || n.eps > 1.0) return fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d].%s: eps = %g", i, kNormName[k], n.eps);
+        }
+    }
+    return HG_OK;
+}
+
+int resnet_alloc(hg_ctx* c, std::vector<void*>& owned, size_t bytes, void** out) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    if (e != hipSuccess) return fail(c, HG_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    owned.push_back(p);
+    *out = p;
+    return HG_OK;
+}
+
+// one convolution and its norm: the packed fp16 weight, and scale / bias made in double and rounded to fp32 (backbone.py:45-55)
+int load_conv(hg_ctx* c, std::vector<void*>& owned, const hg_resnet_conv& v, const hg_resnet_norm& n, int* flag, ResnetConvW& d) {
+    d.cin = v.cin; d.cout = v.cout; d.R = v.kh; d.stride = v.stride_h;
+    const size_t nw = (size_t)v.cout * v.cin * v.kh * v.kh;
+    void *pw, *ps, *pb;
+    int rc = resnet_alloc(c, owned, nw * 2, &pw);
+    if (!rc) rc = resnet_alloc(c, owned, (size_t)v.cout * 4, &ps);
+    if (!rc) rc = resnet_alloc(c, owned, (size_t)v.cout * 4, &pb);
+    if (rc) return rc;
+    HG_HIP(launch_resnet_pack(v.weight, (half_t*)pw, v.cout, v.cin, v.kh, flag, 0));
+    std::vector<float> h[4], scale(v.cout), bias(v.cout);
+    const float* src[4] = {n.weight, n.bias, n.running_mean, n.running_var};
+    for (int k = 0; k < 4; ++k) {
+        h[k].resize(v.cout);
+        HG_HIP(hipMemcpy(h[k].data(), src[k], (size_t)v.cout * 4, hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < v.cout; ++i) {
+        const double s = (double)h[0][i] / sqrt((double)h[3][i] + n.eps);
+        scale[i] = (float)s;
+        bias[i] = (float)((double)h[1][i] - (double)h[2][i] * s);
+    }
+    HG_HIP(hipMemcpy(ps, scale.data(), (size_t)v.cout * 4, hipMemcpyHostToDevice));
+    HG_HIP(hipMemcpy(pb, bias.data(), (size_t)v.cout * 4, hipMemcpyHostToDevice));
+    d.w = (half_t*)pw; d.scale = (float*)ps; d.bias = (float*)pb;
+    return HG_OK;
+}
+
+struct Hw {
+    int H, W;
+};
+Hw conv_out(Hw in, int R, int stride) { return Hw{resnet_out_size(in.H, R, stride), resnet_out_size(in.W, R, stride)}; }
+
+}  // namespace
+
+extern "C" {
+
+// torchvision's Bottleneck (conv1, bn1, conv2, bn2, conv3, bn3, downsample) for every block of layer1 .. layer4 (backbone.py:83-93)
+int hg_load_resnet_stages(hg_ctx* c, const hg_resnet_weights* w) {
+    if (!c) return HG_ERR_INVALID;
+    int rc = check_blocks(c, w);
+    if (rc) return rc;
+    HG_ON_DEVICE(c);
+    HG_HIP(hipDeviceSynchronize());      // a call in flight may still read the weights this load replaces
+    ResnetStages n;
+    n.blocks.resize(w->n_blocks);
+    void* flags = nullptr;
+    rc = resnet_alloc(c, n.owned, (size_t)w->n_blocks * 4 * sizeof(int), &flags);
+    if (!rc) {
+        hipError_t e = hipMemset(flags, 0, (size_t)w->n_blocks * 4 * sizeof(int));
+        if (e != hipSuccess) rc = fail(c, HG_ERR_HIP, "hg_load_resnet_stages: hipMemset failed: %s", hipGetErrorString(e));
+    }
+    for (int i = 0; !rc && i < w->n_blocks; ++i) {
+        const hg_resnet_block& b = w->blocks[i];
+        ResnetBlockW& d = n.blocks[i];
+        d.down = b.has_downsample != 0;
+        ResnetConvW* dst[4] = {&d.c1, &d.c2, &d.c3, &d.cd};
+        for (int k = 0; !rc && k < (d.down ? 4 : 3); ++k) rc = load_conv(c, n.owned, conv_of(b, k), norm_of(b, k), (int*)flags + 4 * i + k, *dst[k]);
+    }
+    std::vector<int> hf((size_t)w->n_blocks * 4, 0);
+    if (!rc) {
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(hf.data(), flags, hf.size() * sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, HG_ERR_HIP, "hg_load_resnet_stages: reading the weights failed: %s", hipGetErrorString(e));
+    }
+    for (size_t i = 0; !rc && i < hf.size(); ++i)
+        if (hf[i])
+            rc = fail(c, HG_ERR_INVALID, "hg_load_resnet_stages: blocks[%d].%s.weight holds a value that is not finite or rounds beyond fp16's range (65504)",
+                      (int)(i / 4), kConvName[i % 4]);
+    if (rc) {
+        (void)hipDeviceSynchronize();
+        free_all(n.owned);
+        return rc;
+    }
+    free_all(c->resnet.owned);
+    c->resnet = std::move(n);
+    c->resnet.loaded = true;
+    return HG_OK;
+}
+
+int hg_resnet_out_shape(const hg_resnet_weights* w, int first_block, int last_block, int H, int W, int32_t* C, int32_t* Ho, int32_t* Wo) {
+    if (!w || !w->blocks || first_block < 0 || last_block < first_block || last_block >= w->n_blocks || H < 1 || W < 1) return HG_ERR_INVALID;
+    Hw s{H, W};
+    for (int i = first_block; i <= last_block; ++i) {
+        const hg_resnet_block& b = w->blocks[i];
+        for (int k = 0; k < 3; ++k) {
+            const hg_resnet_conv& v = conv_of(b, k);
+            if (v.stride_h < 1 || v.stride_w < 1) return HG_ERR_INVALID;
+            s = Hw{(s.H + 2 * v.pad_h - v.dil_h * (v.kh - 1) - 1) / v.stride_h + 1, (s.W + 2 * v.pad_w - v.dil_w * (v.kw - 1) - 1) / v.stride_w + 1};
+            if (s.H < 1 || s.W < 1) return HG_ERR_INVALID;
+        }
+    }
+    if (C) *C = w->blocks[last_block].conv3.cout;
+    if (Ho) *Ho = s.H;
+    if (Wo) *Wo = s.W;
+    return HG_OK;
+}
+
+// layer1 .. layer4 of backbone.py:83-93 under IntermediateLayerGetter (:69-73): every block is torchvision's Bottleneck.forward
+int hg_resnet_stages(hg_ctx* c, const hg_resnet_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    const ResnetStages& r = c->resnet;
+    if (!r.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_resnet_stages: no stages loaded (hg_load_resnet_stages)");
+    if (!a || !a->x || !a->out) return fail(c, HG_ERR_INVALID, "hg_resnet_stages: x and out are required");
+    if (a->B < 1 || a->B > RESNET_MAX_B) return fail(c, HG_ERR_INVALID, "hg_resnet_stages: B = %d images, 1 .. %d", a->B, RESNET_MAX_B);
+    if (a->H < 1 || a->W < 1 || a->H > RESNET_MAX_SIDE || a->W > RESNET_MAX_SIDE)
+        return fail(c, HG_ERR_INVALID, "hg_resnet_stages: H x W = %d x %d, 1 .. %d each", a->H, a->W, RESNET_MAX_SIDE);
+    const int nb = (int)r.blocks.size(), first = a->first_block, last = a->last_block;
+    if (first < 0 || last < first || last >= nb)
+        return fail(c, HG_ERR_INVALID, "hg_resnet_stages: blocks %d .. %d of %d loaded", first, last, nb);
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t B = (size_t)a->B;
+    // the workspace (include/hoigen_amd.h states the rule): walk the range once for the largest buffers
+    size_t E = B * a->H * a->W * r.blocks[first].c1.cin, T1 = 0, T2 = 0;
+    {
+        Hw s0{a->H, a->W};
+        for (int i = first; i <= last; ++i) {
+            const ResnetBlockW& b = r.blocks[i];
+            const Hw s1 = conv_out(s0, b.c1.R, b.c1.stride), s2 = conv_out(s1, b.c2.R, b.c2.stride), s3 = conv_out(s2, b.c3.R, b.c3.stride);
+            T1 = std::max(T1, B * s1.H * s1.W * b.c1.cout);
+            T2 = std::max(T2, B * s2.H * s2.W * b.c2.cout);
+            E = std::max(E, B * s3.H * s3.W * b.c3.cout);
+            s0 = s3;
+        }
+    }
+    E = rup(E, 64); T1 = rup(T1, 64); T2 = rup(T2, 64);
+    int rc = ensure(c, c->resnet_ws, 2 * 4 * E + 2 * 2 * E + 4 * E + 2 * T1 + 2 * T2);
+    if (rc) return rc;
+    char* ws = (char*)c->resnet_ws.p;
+    float* x32[2] = {(float*)ws, (float*)(ws + 4 * E)};
+    float* ds32 = (float*)(ws + 8 * E);
+    half_t* x16[2] = {(half_t*)(ws + 12 * E), (half_t*)(ws + 14 * E)};
+    half_t *t1 = (half_t*)(ws + 16 * E), *t2 = (half_t*)(ws + 16 * E + 2 * T1);
+
+    auto conv = [&](const ResnetConvW& w, const half_t* x, Hw in, Hw out, int epi, const float* identity, float* o32, half_t* o16) -> int {
+        ResnetConvArgs k{};
+        k.x = x; k.w = w.w; k.scale = w.scale; k.bias = w.bias; k.identity = identity; k.out32 = o32; k.out16 = o16;
+        k.B = a->B; k.H = in.H; k.W = in.W; k.Cin = w.cin; k.Ho = out.H; k.Wo = out.W; k.Cout = w.cout; k.R = w.R; k.stride = w.stride; k.epi = epi;
+        ProfScope ps(c, s, HG_PROF_RESNET_CONV, a->B * out.H * out.W, w.cout, w.R * w.R * w.cin);
+        hipError_t he = launch_resnet_conv(k, s);
+        ps.finish();
+        if (he != hipSuccess) return fail(c, HG_ERR_HIP, "hg_resnet_stages: convolution launch failed: %s", hipGetErrorString(he));
+        return HG_OK;
+    };
+
+    Hw cur{a->H, a->W};
+    int p = 0;
+    HG_HIP(launch_resnet_entry(a->x, a->x_stride[0], a->x_stride[1], a->x_stride[2], a->B, r.blocks[first].c1.cin, cur.H, cur.W, x32[0], x16[0], s));
+    for (int i = first; i <= last; ++i) {
+        const ResnetBlockW& b = r.blocks[i];
+        const Hw s1 = conv_out(cur, b.c1.R, b.c1.stride), s2 = conv_out(s1, b.c2.R, b.c2.stride), s3 = conv_out(s2, b.c3.R, b.c3.stride);
+        // out = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + identity)      (torchvision's Bottleneck.forward)
+        if ((rc = conv(b.c1, x16[p], cur, s1, 1, nullptr, nullptr, t1))) return rc;
+        if ((rc = conv(b.c2, t1, s1, s2, 1, nullptr, nullptr, t2))) return rc;
+        const float* identity = x32[p];
+        if (b.down) {
+            const Hw sd = conv_out(cur, b.cd.R, b.cd.stride);
+            if (sd.H != s3.H || sd.W != s3.W)
+                return fail(c, HG_ERR_INVALID, "hg_resnet_stages: blocks[%d]: the downsample gives %d x %d, the block %d x %d", i, sd.H, sd.W, s3.H, s3.W);
+            if ((rc = conv(b.cd, x16[p], cur, sd, 2, nullptr, ds32, nullptr))) return rc;
+            identity = ds32;
+        }
+        if ((rc = conv(b.c3, t2, s2, s3, 3, identity, x32[p ^ 1], x16[p ^ 1]))) return rc;
+        p ^= 1;
+        cur = s3;
+        float* tr = a->trace ? a->trace[i - first] : nullptr;
+        if (tr) HG_HIP(launch_resnet_exit(x32[p], a->B, b.c3.cout, cur.H * cur.W, tr, (long long)b.c3.cout * cur.H * cur.W, (long long)cur.H * cur.W, s));
+    }
+    HG_HIP(launch_resnet_exit(x32[p], a->B, r.blocks[last].c3.cout, cur.H * cur.W, a->out, a->out_stride[0], a->out_stride[1], s));
+    return HG_OK;
+}
+
+}  // extern "C"

@@ -557,4 +557,43 @@ int hg_test_detr_rows(hg_ctx* c, int op, const hg_test_detr_rows_args* x, void* 
     return HG_OK;
 }
 
+// ONE launch of the bottleneck convolution (hg_resnet_conv.hip) from fp32 tensors, the loader's packing included (include/hoigen_amd.h;
+// tests/test_gpu_resnet_conv.py).  x's fp16 copy is an allocation of exactly its size.
+int hg_test_resnet_conv(hg_ctx* c, const hg_test_resnet_conv_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x || !x->x || !x->w || !x->scale || !x->bias) return fail(c, HG_ERR_INVALID, "hg_test_resnet_conv: x, w, scale and bias are required");
+    ResnetConvArgs k{};
+    k.B = x->B; k.H = x->H; k.W = x->W; k.Cin = x->cin; k.Cout = x->cout; k.R = x->k; k.stride = x->stride; k.epi = x->epi; k.tile = x->tile;
+    if ((k.R != 1 && k.R != 3) || (k.stride != 1 && k.stride != 2) || k.H < 1 || k.W < 1 || k.B < 1)
+        return fail(c, HG_ERR_INVALID, "hg_test_resnet_conv: k must be 1 or 3, stride 1 or 2, B, H, W at least 1");
+    k.Ho = resnet_out_size(k.H, k.R, k.stride); k.Wo = resnet_out_size(k.W, k.R, k.stride);
+    // placeholders for the pointers the check wants; replaced below
+    k.x = (const half_t*)x->x; k.w = (const half_t*)x->w; k.scale = x->scale; k.bias = x->bias; k.identity = x->identity;
+    k.out32 = x->out32; k.out16 = (half_t*)x->out16;
+    if (!resnet_conv_ok(k)) return fail(c, HG_ERR_INVALID, "hg_test_resnet_conv: the launcher refuses this shape, epilogue or tile");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t nx = (size_t)k.B * k.H * k.W * k.Cin, nw = (size_t)k.Cout * k.Cin * k.R * k.R, no = (size_t)k.B * k.Ho * k.Wo * k.Cout;
+    std::vector<void*> tmp;
+    void *x16 = nullptr, *w16 = nullptr, *o16 = nullptr, *flag = nullptr;
+    hipError_t e = hipMalloc(&x16, nx * 2);
+    if (e == hipSuccess) { tmp.push_back(x16); e = hipMalloc(&w16, nw * 2); }
+    if (e == hipSuccess) { tmp.push_back(w16); e = hipMalloc(&o16, no * 2); }
+    if (e == hipSuccess) { tmp.push_back(o16); e = hipMalloc(&flag, 16); }
+    if (e == hipSuccess) { tmp.push_back(flag); e = hipMemsetAsync(flag, 0, 16, s); }
+    if (e == hipSuccess) e = launch_f32_to_f16(x->x, (half_t*)x16, nx, s);
+    if (e == hipSuccess) e = launch_resnet_pack(x->w, (half_t*)w16, k.Cout, k.Cin, k.R, (int*)flag, s);
+    if (e == hipSuccess) {
+        k.x = (const half_t*)x16; k.w = (const half_t*)w16; k.out16 = (half_t*)o16;
+        ProfScope ps(c, s, HG_PROF_RESNET_CONV, k.B * k.Ho * k.Wo, k.Cout, k.R * k.R * k.Cin);
+        e = launch_resnet_conv(k, s);
+    }
+    if (e == hipSuccess && k.epi != 2) e = launch_f16_to_f32((const half_t*)o16, x->out16, no, s);
+    hipError_t e2 = hipStreamSynchronize(s);
+    free_all(tmp);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_resnet_conv: %s", hipGetErrorString(e));
+    return HG_OK;
+}
+
 }  // extern "C"

@@ -22,6 +22,7 @@ from torch import nn
 
 from . import _lib
 from .model import LayerNorm, Linear, MultiheadAttention, _Ctx, _inference_only, _require_cuda, _sig, _stream_ptr
+from .resnet import NativeBody, ResNetStages  # noqa: F401  (the body's native stages: hoigen_amd/resnet.py)
 
 MAX_TOKENS = _lib.HG_DETR_ATTN_MAX_L
 
@@ -668,7 +669,9 @@ class DetectorNeck(nn.Module):
 
 class Detector(nn.Module):
     """The detector's forward at upt_tip_cache_model_free_finetune_distill3.py:1594-1605 as one object: the backbone's body stays the
-    torch module it is, and ``DetectorNeck``, ``Transformer`` and ``DetectionHeads`` run behind it on one native context.
+    torch module it is, and ``DetectorNeck``, ``Transformer`` and ``DetectionHeads`` run behind it on one native context.  With
+    ``native_stages=True`` the body becomes ``NativeBody``: its stem stays torch, ``layer1`` .. ``layer4`` run on the same context
+    (hoigen_amd/resnet.py).
 
         det = Detector.from_module(self.detector, reserve_indices)
         results, hs, memory = det(images.tensors, images.mask, image_sizes)
@@ -680,11 +683,14 @@ class Detector(nn.Module):
         super().__init__()
         self.body, self.neck, self.transformer, self.heads, self.query_embed = body, neck, transformer, heads, query_embed
         transformer.decoder._ctx = heads._ctx = neck._ctx = transformer.encoder._ctx
+        if isinstance(body, NativeBody):
+            body.stages._ctx = transformer.encoder._ctx
 
     @classmethod
-    def from_module(cls, detr: nn.Module, reserve_indices=None) -> "Detector":
+    def from_module(cls, detr: nn.Module, reserve_indices=None, native_stages: bool = False) -> "Detector":
         backbone = detr.backbone
-        m = cls(backbone[0].body, DetectorNeck.from_modules(detr.input_proj, backbone[1]), Transformer.from_module(detr.transformer),
+        body = NativeBody.from_module(backbone[0].body) if native_stages else backbone[0].body
+        m = cls(body, DetectorNeck.from_modules(detr.input_proj, backbone[1]), Transformer.from_module(detr.transformer),
                 DetectionHeads.from_modules(detr.class_embed, detr.bbox_embed, reserve_indices), detr.query_embed)
         m.train(detr.training)
         return m

@@ -1,0 +1,344 @@
+"""ResNet bottleneck stages façade: ``layer1`` .. ``layer4`` of the detector's body - torchvision's ResNet-50 under the reference's
+``FrozenBatchNorm2d`` (detr/models/backbone.py:19-55, :83-93; chosen at inference.py:950 and main_tip_finetune.py:1057), which also runs
+as the DINO backbone on the 224-pixel crops (upt_tip_cache_model_free_finetune_distill3.py:1617) - on one implicit-GEMM convolution
+(hoigen_amd/csrc/hg_resnet_conv.hip: hg_load_resnet_stages, hg_resnet_stages).
+
+    stages = ResNetStages.from_module(self.detector.backbone[0].body)
+    body = NativeBody.from_module(self.detector.backbone[0].body)          # torch stem + the native stages, returns {'0': map}
+
+The stem (``conv1`` 7 x 7, ``bn1``, ReLU, max-pool) stays torch.  torchvision is not imported: the source module is read by its attribute
+names.  Inference only; tensors must live on a HIP device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib
+from .model import _Ctx, _inference_only, _require_cuda, _stream_ptr
+
+LEVELS = ("layer1", "layer2", "layer3", "layer4")
+_CONVS = (("conv1", "bn1"), ("conv2", "bn2"), ("conv3", "bn3"))
+
+
+def _pair(v) -> Tuple[int, int]:
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+class _ConvDesc:
+    """The integers of one convolution, as hg_resnet_conv takes them."""
+
+    def __init__(self, name: str, conv: nn.Module):
+        w = getattr(conv, "weight", None)
+        if w is None or w.dim() != 4:
+            raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} has no [Cout, Cin, k, k] weight "
+                               f"(got {type(conv).__name__}, weight {None if w is None else tuple(w.shape)})")
+        self.name = name
+        self.cout, cin_g, self.kh, self.kw = (int(v) for v in w.shape)
+        self.groups = int(getattr(conv, "groups", 1))
+        self.cin = cin_g * self.groups
+        self.stride, self.padding, self.dilation = _pair(getattr(conv, "stride", 1)), _pair(getattr(conv, "padding", 0)), _pair(getattr(conv, "dilation", 1))
+        self.has_bias = getattr(conv, "bias", None) is not None
+
+    def check(self) -> None:
+        """What hg_load_resnet_stages refuses, refused here with the same words (no device needed)."""
+        head = f"hoigen_amd: ResNetStages.from_module: {self.name}: "
+        k = self.kh
+        if self.kh != self.kw or k not in (1, 3):
+            raise RuntimeError(head + f"a {self.kh} x {self.kw} kernel; only 1 x 1 and 3 x 3 are implemented")
+        if self.dilation != (1, 1):
+            raise RuntimeError(head + f"dilation {self.dilation}; only dilation 1 is implemented (the reference's --dilation, DC5, is off by default)")
+        if self.groups != 1:
+            raise RuntimeError(head + f"groups = {self.groups}; only groups = 1 is implemented")
+        if self.has_bias:
+            raise RuntimeError(head + "the convolution has a bias; a ResNet's convolutions have none")
+        if self.stride[0] != self.stride[1] or self.stride[0] not in (1, 2):
+            raise RuntimeError(head + f"stride {self.stride}; only 1 and 2, the same on both axes, are implemented")
+        if self.padding != ((k - 1) // 2, (k - 1) // 2):
+            raise RuntimeError(head + f"padding {self.padding} under a {k} x {k} kernel; only (k - 1) / 2 is implemented")
+        m = _lib.HG_RESNET_MAX_C
+        if self.cin < 64 or self.cin % 64 or self.cin > m or self.cout < 64 or self.cout % 64 or self.cout > m:
+            raise RuntimeError(head + f"{self.cin} -> {self.cout} channels; both must be multiples of 64 up to {m}")
+        if k == 3 and self.cin > _lib.HG_RESNET_MAX_C3:
+            raise RuntimeError(head + f"a 3 x 3 kernel over {self.cin} input channels, at most {_lib.HG_RESNET_MAX_C3}")
+
+    def struct(self, ptr: Optional[int]) -> "_lib.hg_resnet_conv":
+        return _lib.hg_resnet_conv(ptr, self.cout, self.cin, self.kh, self.kw, self.stride[0], self.stride[1], self.padding[0], self.padding[1],
+                                   self.dilation[0], self.dilation[1], self.groups, int(self.has_bias))
+
+
+class FrozenNorm(nn.Module):
+    """Holder of a frozen norm's four vectors under the reference's names (backbone.py:32-36) and its eps (:50)."""
+
+    def __init__(self, n: int, eps: float = 1e-5):
+        super().__init__()
+        self.register_buffer("weight", torch.ones(n))
+        self.register_buffer("bias", torch.zeros(n))
+        self.register_buffer("running_mean", torch.zeros(n))
+        self.register_buffer("running_var", torch.ones(n))
+        self.eps = float(eps)
+
+
+class ConvWeight(nn.Module):
+    """Holder of a convolution's weight and integers; never called."""
+
+    def __init__(self, d: _ConvDesc):
+        super().__init__()
+        self.register_buffer("weight", torch.empty(d.cout, d.cin, d.kh, d.kw))
+        self.desc = d
+
+
+class BottleneckParams(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.downsample = None
+
+
+def _read_norm(name: str, norm: nn.Module, channels: int) -> FrozenNorm:
+    missing = [k for k in ("weight", "bias", "running_mean", "running_var") if getattr(norm, k, None) is None]
+    if missing:
+        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} ({type(norm).__name__}) has no {missing}: a frozen norm or an "
+                           "nn.BatchNorm2d with running statistics is needed")
+    if isinstance(norm, nn.modules.batchnorm._BatchNorm) and norm.training:
+        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} ({type(norm).__name__}) is in training mode and would normalise with "
+                           "batch statistics; call eval() on the body first (the reference freezes its norms, backbone.py:19-55)")
+    if int(norm.weight.numel()) != channels:
+        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} has {int(norm.weight.numel())} channels, its convolution gives {channels}")
+    eps = float(getattr(norm, "eps", 1e-5))      # FrozenBatchNorm2d holds no eps attribute: 1e-5 inside forward (backbone.py:50)
+    if not (0.0 <= eps <= 1.0):
+        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name}: eps = {eps}")
+    m = FrozenNorm(channels, eps)
+    for k in ("weight", "bias", "running_mean", "running_var"):
+        getattr(m, k).data = getattr(norm, k).detach().to(torch.float32).clone()
+    return m
+
+
+class ResNetStages(nn.Module):
+    """``layer1`` .. ``layer4`` (or a range of them) of a bottleneck ResNet in one native call.  ``forward(x)`` takes the stem's
+    ``[B, 64, H, W]`` map and returns the last level's map - ``[B, 2048, H / 8, W / 8]`` for ResNet-50's four levels (each stride-2 level
+    gives ``(H - 1) // 2 + 1``) - as fp32 NCHW; ``forward_trace`` also returns every block's output.  Arithmetic: fp16 operands, fp32
+    accumulation in a fixed order, the norm as one ``fmaf`` on fp32 scale / bias made in double, the identity chain in fp32 (DESIGN.md
+    section 20)."""
+
+    def __init__(self):
+        super().__init__()
+        self.level_names: List[str] = []
+        self.level_ends: List[int] = []      # index of each level's last block
+        self._ctx = _Ctx()
+        self._sig = None
+        self._keep = None
+
+    @classmethod
+    def from_module(cls, body: nn.Module, levels: Tuple[int, int] = (1, 4)) -> "ResNetStages":
+        """From a torchvision-style ResNet or the ``IntermediateLayerGetter`` around it: attributes ``layer1`` .. ``layer4``, every block
+        with ``conv1, bn1, conv2, bn2, conv3, bn3`` and an optional ``downsample`` of two children.  ``levels = (first, last)``, 1-based
+        and inclusive, selects a range (``(4, 4)``: ``layer4`` alone, fed with ``layer3``'s map)."""
+        first, last = int(levels[0]), int(levels[1])
+        if not (1 <= first <= last <= 4):
+            raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: levels = {tuple(levels)}; 1 <= first <= last <= 4")
+        m = cls()
+        n_blocks, prev_cout, device, training = 0, None, None, False
+        for name in LEVELS[first - 1:last]:
+            level = getattr(body, name, None)
+            if level is None:
+                raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: the body ({type(body).__name__}) has no {name}")
+            blocks = nn.ModuleList()
+            for i, blk in enumerate(level):
+                where = f"{name}.{i}"
+                if not hasattr(blk, "conv3"):
+                    raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where} ({type(blk).__name__}) has no conv3: BasicBlock "
+                                       "(resnet18 / resnet34) is not implemented, only the bottleneck block of resnet50 / 101 / 152")
+                p = BottleneckParams()
+                for cn, bn in _CONVS:
+                    if not hasattr(blk, cn) or not hasattr(blk, bn):
+                        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where} ({type(blk).__name__}) has no {cn} / {bn}")
+                    d = _ConvDesc(f"{where}.{cn}", getattr(blk, cn))
+                    d.check()
+                    holder = ConvWeight(d)
+                    holder.weight.data = getattr(blk, cn).weight.detach().to(torch.float32).clone()
+                    setattr(p, cn, holder)
+                    setattr(p, bn, _read_norm(f"{where}.{bn}", getattr(blk, bn), d.cout))
+                c1, c2, c3 = p.conv1.desc, p.conv2.desc, p.conv3.desc
+                if c2.cin != c1.cout or c3.cin != c2.cout:
+                    raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where}: the channels do not chain (conv1 {c1.cin} -> {c1.cout}, "
+                                       f"conv2 {c2.cin} -> {c2.cout}, conv3 {c3.cin} -> {c3.cout})")
+                stride = c1.stride[0] * c2.stride[0] * c3.stride[0]
+                down = getattr(blk, "downsample", None)
+                if down is None:
+                    if c3.cout != c1.cin or stride != 1:
+                        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where} has no downsample, and maps {c1.cin} channels to "
+                                           f"{c3.cout} at stride {stride}: the identity does not fit")
+                else:
+                    kids = list(down.children()) if isinstance(down, nn.Module) else list(down)
+                    if len(kids) != 2:
+                        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where}.downsample has {len(kids)} children; a convolution "
+                                           "and a norm are needed")
+                    d = _ConvDesc(f"{where}.downsample.0", kids[0])
+                    d.check()
+                    if d.cin != c1.cin or d.cout != c3.cout or d.stride[0] != stride or d.kh != 1:
+                        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where}.downsample.0 is {d.kh} x {d.kw}, {d.cin} -> {d.cout} at "
+                                           f"stride {d.stride[0]}; the block needs 1 x 1, {c1.cin} -> {c3.cout} at stride {stride}")
+                    holder = ConvWeight(d)
+                    holder.weight.data = kids[0].weight.detach().to(torch.float32).clone()
+                    p.downsample = nn.Sequential(holder, _read_norm(f"{where}.downsample.1", kids[1], d.cout))
+                if prev_cout is not None and c1.cin != prev_cout:
+                    raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {where} takes {c1.cin} channels, its predecessor gives {prev_cout}")
+                prev_cout = c3.cout
+                device = blk.conv1.weight.device
+                training = training or bool(getattr(blk, "training", False))
+                blocks.append(p)
+                n_blocks += 1
+            if not len(blocks):
+                raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} has no blocks")
+            setattr(m, name, blocks)
+            m.level_names.append(name)
+            m.level_ends.append(n_blocks - 1)
+        if n_blocks > _lib.HG_RESNET_MAX_BLOCKS:
+            raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {n_blocks} blocks, at most {_lib.HG_RESNET_MAX_BLOCKS}")
+        m.to(device)
+        m.train(getattr(body, "training", training))
+        return m
+
+    # ---- the blocks in order, and their descriptors
+    def blocks(self) -> List[BottleneckParams]:
+        return [b for name in self.level_names for b in getattr(self, name)]
+
+    @property
+    def in_channels(self) -> int:
+        return self.blocks()[0].conv1.desc.cin
+
+    def _descriptors(self, with_pointers: bool):
+        """(hg_resnet_weights, what must stay alive while it is used)"""
+        blocks = self.blocks()
+        arr = (_lib.hg_resnet_block * len(blocks))()
+        keep = [arr]
+
+        def ptr(t):
+            if not with_pointers:
+                return None
+            _require_cuda(t, "ResNetStages weights")
+            t = t.detach().to(torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        def norm(n):
+            return _lib.hg_resnet_norm(ptr(n.weight), ptr(n.bias), ptr(n.running_mean), ptr(n.running_var), n.eps)
+
+        ends = set(self.level_ends)
+        for i, b in enumerate(blocks):
+            a = arr[i]
+            a.conv1, a.conv2, a.conv3 = (getattr(b, cn).desc.struct(ptr(getattr(b, cn).weight)) for cn, _ in _CONVS)
+            a.bn1, a.bn2, a.bn3 = norm(b.bn1), norm(b.bn2), norm(b.bn3)
+            if b.downsample is not None:
+                a.down_conv, a.down_bn, a.has_downsample = b.downsample[0].desc.struct(ptr(b.downsample[0].weight)), norm(b.downsample[1]), 1
+            a.ends_level = int(i in ends)
+        return _lib.hg_resnet_weights(arr, len(blocks)), keep
+
+    def out_shape(self, H: int, W: int, first_block: int = 0, last_block: Optional[int] = None) -> Tuple[int, int, int]:
+        """(C, H, W) behind blocks ``first_block .. last_block`` (default: all) for an ``H x W`` input - hg_resnet_out_shape, pure host."""
+        w, keep = self._descriptors(False)
+        last = len(keep[0]) - 1 if last_block is None else last_block
+        c, h, ww = C.c_int32(), C.c_int32(), C.c_int32()
+        rc = _lib.lib().hg_resnet_out_shape(C.byref(w), first_block, last, H, W, C.byref(c), C.byref(h), C.byref(ww))
+        if rc:
+            raise RuntimeError(f"hoigen_amd: hg_resnet_out_shape({first_block}, {last}, {H}, {W}) failed ({rc})")
+        return c.value, h.value, ww.value
+
+    def set_option(self, key: str, value: int) -> None:
+        self._ctx.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self._ctx.get_option(key)
+
+    def _load(self, device: torch.device) -> int:
+        h = self._ctx.get(device)
+        sig = (h, tuple((t.data_ptr(), t._version) for t in self.buffers()), tuple(b.bn1.eps for b in self.blocks()))
+        if sig != self._sig:
+            w, keep = self._descriptors(True)
+            self._ctx.check(_lib.lib().hg_load_resnet_stages(h, C.byref(w)), "hg_load_resnet_stages")
+            self._sig = sig
+        return h
+
+    def _run(self, x: torch.Tensor, first_block: int = 0, last_block: Optional[int] = None, out: Optional[torch.Tensor] = None,
+             want_trace: bool = False):
+        _require_cuda(x, "ResNetStages x")
+        blocks = self.blocks()
+        last = len(blocks) - 1 if last_block is None else int(last_block)
+        first = int(first_block)
+        if not (0 <= first <= last < len(blocks)):
+            raise RuntimeError(f"hoigen_amd: ResNetStages: blocks {first} .. {last} of {len(blocks)}")
+        cin = blocks[first].conv1.desc.cin
+        if x.dim() != 4 or x.shape[1] != cin:
+            raise RuntimeError(f"hoigen_amd: ResNetStages: x must be [B, {cin}, H, W] (got {tuple(x.shape)})")
+        B, _, H, W = (int(v) for v in x.shape)
+        if not (1 <= B <= _lib.HG_RESNET_MAX_B) or not (1 <= H <= _lib.HG_RESNET_MAX_SIDE) or not (1 <= W <= _lib.HG_RESNET_MAX_SIDE):
+            raise RuntimeError(f"hoigen_amd: ResNetStages: B = {B} (1 .. {_lib.HG_RESNET_MAX_B}), H x W = {H} x {W} (1 .. {_lib.HG_RESNET_MAX_SIDE} each)")
+        x = x.detach()
+        if x.dtype != torch.float32 or x.stride(3) != 1:
+            x = x.to(torch.float32).contiguous()
+        h = self._load(x.device)
+        Co, Ho, Wo = self.out_shape(H, W, first, last)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        if out is None:
+            out = torch.empty(B, Co, Ho, Wo, **f32)
+        elif tuple(out.shape) != (B, Co, Ho, Wo) or out.dtype != torch.float32 or out.device != x.device or out.stride(3) != 1 or \
+                (Ho > 1 and out.stride(2) != Wo):
+            raise RuntimeError(f"hoigen_amd: ResNetStages: out must be an fp32 [{B}, {Co}, {Ho}, {Wo}] tensor (or view) on x's device whose "
+                               "tokens are contiguous within a channel")
+        a = _lib.hg_resnet_args()
+        a.x, a.B, a.H, a.W, a.first_block, a.last_block, a.out = x.data_ptr(), B, H, W, first, last, out.data_ptr()
+        a.x_stride[:] = [x.stride(0), x.stride(1), x.stride(2)]
+        a.out_stride[:] = [out.stride(0), out.stride(1)]
+        trace = None
+        if want_trace:
+            trace = [torch.empty(B, *self.out_shape(H, W, first, i), **f32) for i in range(first, last + 1)]
+            ptrs = (C.c_void_p * len(trace))(*[t.data_ptr() for t in trace])
+            a.trace = ptrs
+        self._ctx.check(_lib.lib().hg_resnet_stages(h, C.byref(a), _stream_ptr(x.device)), "hg_resnet_stages")
+        return out, trace
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``x [B, Cin, H, W]`` (fp32 with a column stride of 1 is read where it lies through its strides; anything else is converted
+        once) -> the last level's map, fp32 ``[B, C, Ho, Wo]``; ``out``: write into this tensor or view instead."""
+        return self._run(x, out=out)[0]
+
+    @_inference_only
+    @torch.no_grad()
+    def forward_blocks(self, x: torch.Tensor, first_block: int, last_block: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Blocks ``first_block .. last_block`` (inclusive, counted over the loaded levels) on the input of ``first_block``."""
+        return self._run(x, first_block, last_block, out)[0]
+
+    @_inference_only
+    @torch.no_grad()
+    def forward_trace(self, x: torch.Tensor, first_block: int = 0, last_block: Optional[int] = None):
+        """``(map, [every block's output])``."""
+        return self._run(x, first_block, last_block, want_trace=True)
+
+
+class NativeBody(nn.Module):
+    """The body the reference builds at backbone.py:69-73 with the stem in torch and the stages native: ``forward(images)`` returns
+    ``{'0': layer4's map}`` as ``IntermediateLayerGetter`` does, so it drops into ``Detector``."""
+
+    def __init__(self, stem: Sequence[nn.Module], stages: ResNetStages):
+        super().__init__()
+        self.stem = nn.Sequential(*stem)
+        self.stages = stages
+
+    @classmethod
+    def from_module(cls, body: nn.Module) -> "NativeBody":
+        missing = [k for k in ("conv1", "bn1", "relu", "maxpool") if getattr(body, k, None) is None]
+        if missing:
+            raise RuntimeError(f"hoigen_amd: NativeBody.from_module: the body ({type(body).__name__}) has no {missing}")
+        m = cls([body.conv1, body.bn1, body.relu, body.maxpool], ResNetStages.from_module(body))
+        m.train(getattr(body, "training", False))
+        return m
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor):
+        return {"0": self.stages._run(self.stem(images))[0]}

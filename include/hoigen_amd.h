@@ -657,6 +657,75 @@ typedef struct {
     uint8_t* mask;
 } hg_detr_neck_args;
 int hg_detr_neck(hg_ctx*, const hg_detr_neck_args* args, void* stream);
+
+/* ---- ResNet stages: the bottleneck blocks layer1 .. layer4 of the detector's body (detr/models/backbone.py:83-93 builds torchvision's
+ * ResNet-50 with the FrozenBatchNorm2d of :19-55; inference.py:950 and main_tip_finetune.py:1057 choose it; the same network runs as
+ * the DINO backbone at upt_tip_cache_model_free_finetune_distill3.py:1617) on one implicit-GEMM convolution
+ * (hoigen_amd/csrc/hg_resnet_conv.hip).  The stem - conv1 7 x 7, bn1, ReLU, max-pool - stays with the caller. ---------------------------
+ *
+ * A block is conv1 -> bn1 -> ReLU -> conv2 -> bn2 -> ReLU -> conv3 -> bn3, + identity, -> ReLU; identity = the block's input, or
+ * down_bn(down_conv(input)) where has_downsample.  Convolutions read fp16 operands (the weight rounded once, the activation rounded once)
+ * and accumulate in fp32 in a fixed order: taps (r, s) ascending, then input channels ascending.  A norm is not folded into the
+ * weights: scale = weight / sqrt(running_var + eps) and bias = bias - running_mean * scale are made on the host in double, rounded to
+ * fp32, and applied as fmaf(acc, scale, bias) (backbone.py:45-55).  Between blocks the stream is fp32, with an fp16 copy as the next
+ * convolution's operand; the identity is always read as fp32.  Inside a block conv1's and conv2's outputs exist as fp16 only.
+ *
+ * hg_load_resnet_stages: a slot of its own beside the DETR slots.  Every pointer is DEVICE fp32, contiguous; weight is torch's
+ * [cout, cin, kh, kw].  Strides are read from the convolutions, so the stride may sit on conv2 (torchvision, v1.5) or on conv1 (the
+ * original placement).  Synchronous.  HG_ERR_INVALID with a message, nothing launched for: n_blocks outside 1 .. 64;
+ * cin or cout no multiple of 64 or above 2048; a 3 x 3 with more than 512 input channels; a kernel other than 1 x 1 or 3 x 3; padding
+ * other than (k - 1) / 2; a stride outside {1, 2} or different per axis; dilation other than 1 (the reference's --dilation is store_true and off by
+ * default, detr/main.py:37; backbone.py:90); groups other than 1; a convolution with a bias; channel counts that do not chain (conv2.cin !=
+ * conv1.cout ..., a block's cin != its predecessor's cout); a missing downsample where the block changes the channel count or the
+ * size; a downsample whose stride is not the product of the block's strides; a null pointer.  HG_ERR_INVALID after the weights were
+ * read for a weight that is not finite or rounds beyond fp16's range.  After any failure the slot keeps what it held. */
+typedef struct {
+    const float* weight;                   /* [cout, cin, kh, kw] */
+    int32_t cout, cin, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, has_bias;
+} hg_resnet_conv;
+typedef struct {
+    const float* weight;
+    const float* bias;
+    const float* running_mean;
+    const float* running_var;              /* [channels] each */
+    double eps;                            /* FrozenBatchNorm2d: 1e-5 (backbone.py:50); nn.BatchNorm2d in eval(): its own */
+} hg_resnet_norm;
+typedef struct {
+    hg_resnet_conv conv1, conv2, conv3, down_conv;
+    hg_resnet_norm bn1, bn2, bn3, down_bn;
+    int32_t has_downsample;
+    int32_t ends_level;                    /* 1: the last block of layer1 / 2 / 3 / 4 (informational) */
+} hg_resnet_block;
+typedef struct {
+    const hg_resnet_block* blocks;
+    int32_t n_blocks;
+} hg_resnet_weights;
+int hg_load_resnet_stages(hg_ctx*, const hg_resnet_weights*);
+/* hg_resnet_out_shape: pure host, no context, reads the descriptors' integers only.  (C, H, W) behind blocks first .. last for an
+ * H x W input of block `first`: per convolution (H + 2 pad - k) / stride + 1 in integer division.  HG_ERR_INVALID for a range outside
+ * the blocks or H, W < 1. */
+int hg_resnet_out_shape(const hg_resnet_weights*, int first_block, int last_block, int H, int W, int32_t* C, int32_t* Ho, int32_t* Wo);
+/* hg_resnet_stages: blocks first_block .. last_block (inclusive) of the loaded stages.
+ *   x      DEVICE fp32 [B, cin of first_block, H, W] through element strides x_stride = (image, channel, row); the column stride is 1.
+ *          The stem's map for first_block = 0; layer3's map to run layer4 alone.  Read once, never copied as fp32 NCHW.
+ *   out    fp32 [B, C, Ho, Wo] through out_stride = (image, channel) in elements, token stride 1: what hg_detr_neck reads.
+ *   trace  nullable: HOST array of last_block - first_block + 1 DEVICE pointers (each nullable), block i's output as contiguous fp32
+ *          [B, C_i, H_i, W_i] - for the tests.
+ * Asynchronous on `stream`; no host wait.  The workspace is grow-only and owned by the context: with E = the largest B H W C of a
+ * block's input or output in the range, T1 / T2 = the largest conv1 / conv2 output, it is 2 x 4 E (the fp32 stream, in and out) +
+ * 2 x 2 E (its fp16 copy) + 4 E (the downsample's output) + 2 T1 + 2 T2 bytes.  The result is a fixed function of the inputs and an
+ * image's result does not depend on the rest of the batch.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message and nothing
+ * launched for B outside 1 .. 64, H or W outside 1 .. 1024, a block range outside the loaded blocks, a null x or out. */
+typedef struct {
+    const float* x;
+    int64_t x_stride[3];                   /* elements: image, channel, row */
+    int32_t B, H, W;
+    int32_t first_block, last_block;
+    float* out;
+    int64_t out_stride[2];                 /* elements: image, channel */
+    float* const* trace;
+} hg_resnet_args;
+int hg_resnet_stages(hg_ctx*, const hg_resnet_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -774,6 +843,7 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_DETR_FFN 104  /* the DETR decoder's split FFN kernel: M = rows, N = d_ff, K = d_model */
 #define HG_PROF_DETR_ROWS 105 /* row kernels of hg_detr_decoder (entries, post-norms, tails): M = rows, N = d_model, K = slices summed */
 #define HG_PROF_DETR_NECK 106 /* hg_detr_neck's launch(es): M = rows (B * H * W), N = slices of cin, K = cin */
+#define HG_PROF_RESNET_CONV 107 /* one convolution launch of hg_resnet_stages / hg_test_resnet_conv: M = output pixels (B * Ho * Wo), N = cout, K = k * k * cin */
 #define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
@@ -998,6 +1068,24 @@ typedef struct {
     int32_t i[4];
 } hg_test_detr_rows_args;
 int hg_test_detr_rows(hg_ctx*, int op, const hg_test_detr_rows_args* args, void* stream);
+
+/* Test hook for the bottleneck convolution (hoigen_amd/csrc/hg_resnet_conv.hip): ONE launch from fp32 device tensors, the loader's
+ * packing included.  x [B, H, W, cin] NHWC and w [cout, cin, k, k] (torch's order) are rounded to fp16 inside; x's fp16 copy is an
+ * allocation of exactly its size, so its first pixel is the first byte and its last pixel the last bytes of an allocation.  scale,
+ * bias [cout]; identity [B Ho Wo, cout] fp32 NHWC (epi 3).  epi 1: relu(fmaf(acc, scale, bias)) -> out16; 2: fmaf -> out32; 3:
+ * relu(fmaf + identity) -> out32 and out16.  out32 / out16 [B Ho Wo, cout] fp32 (the fp16 output comes back as fp32).  k in {1, 3},
+ * stride in {1, 2}; tile 0 (the rule), 32 or 128 output pixels a work item.  Synchronous.  HG_ERR_INVALID where the launcher refuses. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* scale;
+    const float* bias;
+    const float* identity;
+    float* out32;
+    float* out16;
+    int32_t B, H, W, cin, cout, k, stride, epi, tile;
+} hg_test_resnet_conv_args;
+int hg_test_resnet_conv(hg_ctx*, const hg_test_resnet_conv_args* args, void* stream);
 
 #ifdef __cplusplus
 }
