@@ -252,6 +252,25 @@ class hg_test_resnet_conv_args(C.Structure):
                [(n, C.c_int32) for n in ("B", "H", "W", "cin", "cout", "k", "stride", "epi", "tile")]
 
 
+class hg_resnet_stem_weights(C.Structure):
+    _fields_ = [("conv1", hg_resnet_conv), ("bn1", hg_resnet_norm)] + \
+               [(n, C.c_int32) for n in ("pool_kernel", "pool_stride", "pool_padding", "pool_dilation", "pool_ceil_mode")]
+
+
+class hg_resnet_stem_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64 * 3), ("B", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("out", C.c_void_p), ("out_stride", C.c_int64 * 2)]
+
+
+class hg_resnet_body_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64 * 3), ("B", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("last_block", C.c_int32), ("out", C.c_void_p), ("out_stride", C.c_int64 * 2), ("trace", C.POINTER(C.c_void_p))]
+
+
+class hg_test_resnet_stem_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w", "scale", "bias", "out32", "out16")] + [(n, C.c_int32) for n in ("B", "Hi", "Wi")]
+
+
 class hg_prof_rec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ms", C.c_float)]
 
@@ -277,6 +296,9 @@ class hg_test_detr_rows_args(C.Structure):
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
 HG_PROF_RESNET_CONV = 107
+HG_PROF_RESNET_STEM = 108
+# pooled pixels of a work item of hg_resnet_stem.hip (hoigen_amd/csrc/hg_kernels.h), and the largest image side of hg_resnet_stem
+HG_RESNET_STEM_TILE, HG_RESNET_STEM_MAX_SIDE = (4, 8), 4 * HG_RESNET_MAX_SIDE
 
 _P = C.c_void_p
 _I = C.c_int
@@ -326,6 +348,10 @@ SIGNATURES = {
     "hg_load_resnet_stages": (_I, [_P, C.POINTER(hg_resnet_weights)]),
     "hg_resnet_out_shape": (_I, [C.POINTER(hg_resnet_weights), _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hg_resnet_stages": (_I, [_P, C.POINTER(hg_resnet_args), _P]),
+    "hg_load_resnet_stem": (_I, [_P, C.POINTER(hg_resnet_stem_weights)]),
+    "hg_resnet_stem_out_shape": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "hg_resnet_stem": (_I, [_P, C.POINTER(hg_resnet_stem_args), _P]),
+    "hg_resnet_body": (_I, [_P, C.POINTER(hg_resnet_body_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -344,6 +370,7 @@ SIGNATURES = {
     "hg_test_elem": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
     "hg_test_detr_rows": (_I, [_P, _I, C.POINTER(hg_test_detr_rows_args), _P]),
     "hg_test_resnet_conv": (_I, [_P, C.POINTER(hg_test_resnet_conv_args), _P]),
+    "hg_test_resnet_stem": (_I, [_P, C.POINTER(hg_test_resnet_stem_args), _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

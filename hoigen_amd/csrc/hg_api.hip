@@ -115,6 +115,7 @@ void hg_destroy(hg_ctx* c) {
     free_all(c->detr_heads.owned);
     free_all(c->detr_neck.owned);
     free_all(c->resnet.owned);
+    free_all(c->resnet_stem.owned);
     Buf* bufs[] = HG_WORKSPACE_BUFS(c);
     for (Buf* b : bufs)
         if (b->p) (void)hipFree(b->p);

@@ -187,6 +187,11 @@ struct ResnetStages {    // hg_load_resnet_stages
     std::vector<ResnetBlockW> blocks;
     std::vector<void*> owned;
 };
+struct ResnetStem {      // hg_load_resnet_stem: conv1 as hg_resnet_stem.hip's fp16 fragments (launch_resnet_stem_pack), bn1 as scale and bias
+    bool loaded = false;
+    ResnetConvW conv;
+    std::vector<void*> owned;
+};
 }  // namespace hg_host
 using namespace hg_host;
 
@@ -204,6 +209,7 @@ struct hg_ctx {
     DetrHeads detr_heads;
     DetrNeck detr_neck;
     ResnetStages resnet;
+    ResnetStem resnet_stem;
     // workspace (grow-only)
     Buf x, h, qkv, att, fc, head16, tok32, small, i32, ad32, ad16, adkv, mr, mu, muc, stats, pre, pretab, cx, ca, ch, cf, cq;
     Buf hg;              // folded path with the LayerNorm weight in the activation copy (text tower): that copy, beside the stream's hi half in h
@@ -218,7 +224,8 @@ struct hg_ctx {
     Buf detr_ws;         // hg_detr_encoder: the fp32 stream, the batch-major pos, and the fp16 operands x, x + pos, q | k, v, attention output, FFN hidden
     Buf detr_dec_ws;     // hg_detr_decoder: memory's fp16 copies and every layer's cross-attention K and V, the decoder stream and its fp16 operands, the split FFN's partial sums
     Buf detr_neck_ws;    // hg_detr_neck: the fp32 partial sums of a split over Cin
-    Buf resnet_ws;       // hg_resnet_stages: the fp32 stream in and out, its fp16 copies, the downsample's output, conv1's and conv2's outputs
+    Buf resnet_ws;       // hg_resnet_stages / hg_resnet_body: the fp32 stream in and out, its fp16 copies, the downsample's output, conv1's and conv2's outputs
+    Buf resnet_stem_ws;  // hg_resnet_stem: the NHWC fp32 + fp16 pair the kernel writes, ahead of the NCHW copy the caller gets
     Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
     int text_rows_budget = 65536;      // rows (prompts x executed tokens) per pass of the text tower (text_chunk_prompts)
@@ -292,7 +299,8 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws, &(c)->resnet_ws}
+     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws, &(c)->resnet_ws, \
+     &(c)->resnet_stem_ws}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];

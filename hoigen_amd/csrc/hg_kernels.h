@@ -267,6 +267,29 @@ hipError_t launch_resnet_entry(const float* x, long long sb, long long sc, long 
 // x fp32 NHWC [B, S, C] -> out fp32 [B, C, S] through element strides (image, channel), token stride 1
 hipError_t launch_resnet_exit(const float* x, int B, int C, int S, float* out, long long sb, long long sc, hipStream_t s);
 
+// ---- ResNet stem (hg_resnet_stem.hip): maxpool3x3/2,pad1(relu(fmaf(conv7x7/2,pad3(x, w), scale, bias))) in one launch, 3 -> 64 channels.
+// x fp32 [B, 3, Hi, Wi] through element strides sb, sc, sr (image, channel, row), column stride 1, 4-byte aligned; w fp16 in fragment
+// order (launch_resnet_stem_pack from torch's fp32 [64, 3, 7, 7]); scale, bias fp32 [64]; out32 fp32 / out16 fp16 NHWC [B, Hp, Wp, 64],
+// 16-byte aligned.  Hc / Wc = resnet_stem_conv_size, Hp / Wp = resnet_stem_pool_size of those, at most RESNET_MAX_SIDE.  One tile shape:
+// RESNET_STEM_TILE_H x RESNET_STEM_TILE_W pooled pixels a work item.  Outside resnet_stem_ok: hipErrorInvalidValue and nothing launched.
+static constexpr int RESNET_STEM_TILE_H = 4, RESNET_STEM_TILE_W = 8;
+struct ResnetStemArgs {
+    const float* x;
+    long long sb, sc, sr;
+    const half_t* w;
+    const float *scale, *bias;
+    float* out32;
+    half_t* out16;
+    int B, Hi, Wi, Hc, Wc, Hp, Wp;
+};
+inline int resnet_stem_conv_size(int Hi) { return (Hi - 1) / 2 + 1; }      // (Hi + 2 * 3 - 7) / 2 + 1
+inline int resnet_stem_pool_size(int Hc) { return (Hc - 1) / 2 + 1; }      // (Hc + 2 * 1 - 3) / 2 + 1
+bool resnet_stem_ok(const ResnetStemArgs& a);
+hipError_t launch_resnet_stem(const ResnetStemArgs& a, hipStream_t s);
+// w fp32 [64, 3, 7, 7] -> the fp16 fragments (24 KiB); flag[0] = 1 where a weight is not finite or beyond fp16's range
+hipError_t launch_resnet_stem_pack(const float* w, half_t* out, int* flag, hipStream_t s);
+static constexpr size_t RESNET_STEM_W_HALFS = 4 * 6 * 512;
+
 // ---- fused in_proj + attention (hg_qkv_attn.hip): out = SDPA(LN-folded in_proj(x16)) with q, k, v kept in LDS ----------------
 // x16 [n_seq * L, lda]: centred fp16 copy of the stream; wp / bcs: the LayerNorm-folded in_proj weight, bias' and column sums
 // packed by launch_pack_qkv; mr [n_seq * L][2] = (row mean minus the copy's centre, rstd); out fp16 [n_seq * L, ldo].

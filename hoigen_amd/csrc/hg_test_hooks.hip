@@ -596,4 +596,44 @@ int hg_test_resnet_conv(hg_ctx* c, const hg_test_resnet_conv_args* x, void* stre
     return HG_OK;
 }
 
+// ONE launch of the stem (hg_resnet_stem.hip) from fp32 tensors, the loader's packing included (include/hoigen_amd.h;
+// tests/test_gpu_resnet_stem.py).  x is read where the caller put it.
+int hg_test_resnet_stem(hg_ctx* c, const hg_test_resnet_stem_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x || !x->x || !x->w || !x->scale || !x->bias || !x->out32 || !x->out16)
+        return fail(c, HG_ERR_INVALID, "hg_test_resnet_stem: x, w, scale, bias, out32 and out16 are required");
+    ResnetStemArgs k{};
+    k.B = x->B; k.Hi = x->Hi; k.Wi = x->Wi;
+    if (k.B < 1 || k.Hi < 1 || k.Wi < 1 || k.Hi > 4 * RESNET_MAX_SIDE || k.Wi > 4 * RESNET_MAX_SIDE)
+        return fail(c, HG_ERR_INVALID, "hg_test_resnet_stem: B, Hi, Wi at least 1, Hi and Wi at most %d", 4 * RESNET_MAX_SIDE);
+    k.Hc = resnet_stem_conv_size(k.Hi); k.Wc = resnet_stem_conv_size(k.Wi);
+    k.Hp = resnet_stem_pool_size(k.Hc); k.Wp = resnet_stem_pool_size(k.Wc);
+    k.x = x->x; k.sb = 3LL * k.Hi * k.Wi; k.sc = (long long)k.Hi * k.Wi; k.sr = k.Wi;
+    k.scale = x->scale; k.bias = x->bias; k.out32 = x->out32;
+    // placeholders for the pointers the check wants; replaced below
+    k.w = (const half_t*)x->scale; k.out16 = (half_t*)x->out32;
+    if (((uintptr_t)x->scale & 15) || !resnet_stem_ok(k)) return fail(c, HG_ERR_INVALID, "hg_test_resnet_stem: the launcher refuses this shape or alignment");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    const size_t no = (size_t)k.B * k.Hp * k.Wp * 64;
+    std::vector<void*> tmp;
+    void *w16 = nullptr, *o16 = nullptr, *flag = nullptr;
+    hipError_t e = hipMalloc(&w16, RESNET_STEM_W_HALFS * 2);
+    if (e == hipSuccess) { tmp.push_back(w16); e = hipMalloc(&o16, no * 2); }
+    if (e == hipSuccess) { tmp.push_back(o16); e = hipMalloc(&flag, 16); }
+    if (e == hipSuccess) { tmp.push_back(flag); e = hipMemsetAsync(flag, 0, 16, s); }
+    if (e == hipSuccess) e = launch_resnet_stem_pack(x->w, (half_t*)w16, (int*)flag, s);
+    if (e == hipSuccess) {
+        k.w = (const half_t*)w16; k.out16 = (half_t*)o16;
+        ProfScope ps(c, s, HG_PROF_RESNET_STEM, k.B * k.Hp * k.Wp, 64, 147);
+        e = launch_resnet_stem(k, s);
+    }
+    if (e == hipSuccess) e = launch_f16_to_f32((const half_t*)o16, x->out16, no, s);
+    hipError_t e2 = hipStreamSynchronize(s);
+    free_all(tmp);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_resnet_stem: %s", hipGetErrorString(e));
+    return HG_OK;
+}
+
 }  // extern "C"

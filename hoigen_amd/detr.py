@@ -22,7 +22,7 @@ from torch import nn
 
 from . import _lib
 from .model import LayerNorm, Linear, MultiheadAttention, _Ctx, _inference_only, _require_cuda, _sig, _stream_ptr
-from .resnet import NativeBody, ResNetStages  # noqa: F401  (the body's native stages: hoigen_amd/resnet.py)
+from .resnet import NativeBody, ResNetStages, ResNetStem  # noqa: F401  (the body's native stem and stages: hoigen_amd/resnet.py)
 
 MAX_TOKENS = _lib.HG_DETR_ATTN_MAX_L
 
@@ -671,7 +671,7 @@ class Detector(nn.Module):
     """The detector's forward at upt_tip_cache_model_free_finetune_distill3.py:1594-1605 as one object: the backbone's body stays the
     torch module it is, and ``DetectorNeck``, ``Transformer`` and ``DetectionHeads`` run behind it on one native context.  With
     ``native_stages=True`` the body becomes ``NativeBody``: its stem stays torch, ``layer1`` .. ``layer4`` run on the same context
-    (hoigen_amd/resnet.py).
+    (hoigen_amd/resnet.py); with ``native_stem=True`` as well the stem runs there too, and the body is one native call from the images.
 
         det = Detector.from_module(self.detector, reserve_indices)
         results, hs, memory = det(images.tensors, images.mask, image_sizes)
@@ -685,11 +685,16 @@ class Detector(nn.Module):
         transformer.decoder._ctx = heads._ctx = neck._ctx = transformer.encoder._ctx
         if isinstance(body, NativeBody):
             body.stages._ctx = transformer.encoder._ctx
+            if body.native_stem is not None:
+                body.native_stem._ctx = transformer.encoder._ctx
 
     @classmethod
-    def from_module(cls, detr: nn.Module, reserve_indices=None, native_stages: bool = False) -> "Detector":
+    def from_module(cls, detr: nn.Module, reserve_indices=None, native_stages: bool = False, *, native_stem: bool = False) -> "Detector":
+        if native_stem and not native_stages:
+            raise RuntimeError("hoigen_amd: Detector.from_module: native_stem=True needs native_stages=True: the native stem writes the "
+                               "stages' operands, and there is no native stem in front of torch stages")
         backbone = detr.backbone
-        body = NativeBody.from_module(backbone[0].body) if native_stages else backbone[0].body
+        body = NativeBody.from_module(backbone[0].body, native_stem=native_stem) if native_stages else backbone[0].body
         m = cls(body, DetectorNeck.from_modules(detr.input_proj, backbone[1]), Transformer.from_module(detr.transformer),
                 DetectionHeads.from_modules(detr.class_embed, detr.bbox_embed, reserve_indices), detr.query_embed)
         m.train(detr.training)

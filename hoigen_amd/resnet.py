@@ -6,7 +6,9 @@ as the DINO backbone on the 224-pixel crops (upt_tip_cache_model_free_finetune_d
     stages = ResNetStages.from_module(self.detector.backbone[0].body)
     body = NativeBody.from_module(self.detector.backbone[0].body)          # torch stem + the native stages, returns {'0': map}
 
-The stem (``conv1`` 7 x 7, ``bn1``, ReLU, max-pool) stays torch.  torchvision is not imported: the source module is read by its attribute
+The stem (``conv1`` 7 x 7, ``bn1``, ReLU, max-pool) stays torch by default; ``ResNetStem.from_module(body)`` is its one native launch
+(hoigen_amd/csrc/hg_resnet_stem.hip) and ``NativeBody.from_module(body, native_stem=True)`` runs stem and stages as one call
+(hg_resnet_body).  torchvision is not imported: the source module is read by its attribute
 names.  Inference only; tensors must live on a HIP device.
 """
 from __future__ import annotations
@@ -65,6 +67,23 @@ class _ConvDesc:
         if k == 3 and self.cin > _lib.HG_RESNET_MAX_C3:
             raise RuntimeError(head + f"a 3 x 3 kernel over {self.cin} input channels, at most {_lib.HG_RESNET_MAX_C3}")
 
+    def check_stem(self, head: str) -> None:
+        """What hg_load_resnet_stem refuses of conv1, refused here with the same words (no device needed)."""
+        if (self.kh, self.kw) != (7, 7):
+            raise RuntimeError(head + f"a {self.kh} x {self.kw} kernel; only 7 x 7 is implemented")
+        if self.dilation != (1, 1):
+            raise RuntimeError(head + f"dilation {self.dilation}; only dilation 1 is implemented")
+        if self.groups != 1:
+            raise RuntimeError(head + f"groups = {self.groups}; only groups = 1 is implemented")
+        if self.has_bias:
+            raise RuntimeError(head + "the convolution has a bias; a ResNet's convolutions have none")
+        if self.stride != (2, 2):
+            raise RuntimeError(head + f"stride {self.stride}; only (2, 2) is implemented")
+        if self.padding != (3, 3):
+            raise RuntimeError(head + f"padding {self.padding}; only (3, 3) is implemented")
+        if (self.cin, self.cout) != (3, 64):
+            raise RuntimeError(head + f"{self.cin} -> {self.cout} channels; only 3 -> 64 is implemented")
+
     def struct(self, ptr: Optional[int]) -> "_lib.hg_resnet_conv":
         return _lib.hg_resnet_conv(ptr, self.cout, self.cin, self.kh, self.kw, self.stride[0], self.stride[1], self.padding[0], self.padding[1],
                                    self.dilation[0], self.dilation[1], self.groups, int(self.has_bias))
@@ -97,19 +116,19 @@ class BottleneckParams(nn.Module):
         self.downsample = None
 
 
-def _read_norm(name: str, norm: nn.Module, channels: int) -> FrozenNorm:
+def _read_norm(name: str, norm: nn.Module, channels: int, who: str = "ResNetStages") -> FrozenNorm:
     missing = [k for k in ("weight", "bias", "running_mean", "running_var") if getattr(norm, k, None) is None]
     if missing:
-        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} ({type(norm).__name__}) has no {missing}: a frozen norm or an "
+        raise RuntimeError(f"hoigen_amd: {who}.from_module: {name} ({type(norm).__name__}) has no {missing}: a frozen norm or an "
                            "nn.BatchNorm2d with running statistics is needed")
     if isinstance(norm, nn.modules.batchnorm._BatchNorm) and norm.training:
-        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} ({type(norm).__name__}) is in training mode and would normalise with "
+        raise RuntimeError(f"hoigen_amd: {who}.from_module: {name} ({type(norm).__name__}) is in training mode and would normalise with "
                            "batch statistics; call eval() on the body first (the reference freezes its norms, backbone.py:19-55)")
     if int(norm.weight.numel()) != channels:
-        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name} has {int(norm.weight.numel())} channels, its convolution gives {channels}")
+        raise RuntimeError(f"hoigen_amd: {who}.from_module: {name} has {int(norm.weight.numel())} channels, its convolution gives {channels}")
     eps = float(getattr(norm, "eps", 1e-5))      # FrozenBatchNorm2d holds no eps attribute: 1e-5 inside forward (backbone.py:50)
     if not (0.0 <= eps <= 1.0):
-        raise RuntimeError(f"hoigen_amd: ResNetStages.from_module: {name}: eps = {eps}")
+        raise RuntimeError(f"hoigen_amd: {who}.from_module: {name}: eps = {eps}")
     m = FrozenNorm(channels, eps)
     for k in ("weight", "bias", "running_mean", "running_var"):
         getattr(m, k).data = getattr(norm, k).detach().to(torch.float32).clone()
@@ -320,25 +339,194 @@ class ResNetStages(nn.Module):
         return self._run(x, first_block, last_block, want_trace=True)
 
 
-class NativeBody(nn.Module):
-    """The body the reference builds at backbone.py:69-73 with the stem in torch and the stages native: ``forward(images)`` returns
-    ``{'0': layer4's map}`` as ``IntermediateLayerGetter`` does, so it drops into ``Detector``."""
+def _images(x: torch.Tensor, what: str) -> torch.Tensor:
+    """``[B, 3, Hi, Wi]`` on a HIP device; fp32 with a column stride of 1 is read where it lies, anything else is converted once"""
+    _require_cuda(x, what)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"hoigen_amd: {what} must be [B, 3, Hi, Wi] (got {tuple(x.shape)})")
+    B, _, Hi, Wi = (int(v) for v in x.shape)
+    m = _lib.HG_RESNET_STEM_MAX_SIDE
+    if not (1 <= B <= _lib.HG_RESNET_MAX_B) or not (1 <= Hi <= m) or not (1 <= Wi <= m):
+        raise RuntimeError(f"hoigen_amd: {what}: B = {B} (1 .. {_lib.HG_RESNET_MAX_B}), Hi x Wi = {Hi} x {Wi} (1 .. {m} each)")
+    x = x.detach()
+    if x.dtype != torch.float32 or x.stride(3) != 1:
+        x = x.to(torch.float32).contiguous()
+    return x
 
-    def __init__(self, stem: Sequence[nn.Module], stages: ResNetStages):
+
+class ResNetStem(nn.Module):
+    """``conv1`` (7 x 7 / 2, 3 -> 64), ``bn1``, ReLU and the 3 x 3 / 2 max-pool of a ResNet in one native launch
+    (hoigen_amd/csrc/hg_resnet_stem.hip).  ``forward(images)`` takes ``[B, 3, Hi, Wi]`` and returns the stem's map, fp32
+    ``[B, 64, Hp, Wp]``: what ``ResNetStages`` takes.  Arithmetic: image and weight rounded once to fp16, fp32 accumulation in a fixed
+    order, the norm as one ``fmaf``, ReLU, a max that keeps a NaN."""
+
+    def __init__(self):
+        super().__init__()
+        self.pool = (3, 2, 1, 1, 0)      # kernel, stride, padding, dilation, ceil_mode
+        self._ctx = _Ctx()
+        self._sig = None
+
+    @classmethod
+    def from_module(cls, body: nn.Module) -> "ResNetStem":
+        """From a torchvision-style ResNet or the ``IntermediateLayerGetter`` around it: attributes ``conv1``, ``bn1``, ``relu``,
+        ``maxpool``.  Refuses what hg_load_resnet_stem refuses, in its words, without a device."""
+        missing = [k for k in ("conv1", "bn1", "relu", "maxpool") if getattr(body, k, None) is None]
+        if missing:
+            raise RuntimeError(f"hoigen_amd: ResNetStem.from_module: the body ({type(body).__name__}) has no {missing}")
+        head = "hoigen_amd: ResNetStem.from_module: "
+        d = _ConvDesc("conv1", body.conv1)
+        d.check_stem(head + "conv1: ")
+        p = body.maxpool
+        if getattr(p, "kernel_size", None) is None:
+            raise RuntimeError(head + f"maxpool ({type(p).__name__}) has no kernel_size")
+
+        def one(v):      # an int where both axes agree, else the pair
+            a, b = _pair(v)
+            return a if a == b else (a, b)
+
+        k = one(p.kernel_size)
+        stride = getattr(p, "stride", None)
+        flat = (k, k if stride is None else one(stride), one(getattr(p, "padding", 0)), one(getattr(p, "dilation", 1)),
+                int(bool(getattr(p, "ceil_mode", False))))
+        if flat != (3, 2, 1, 1, 0):
+            raise RuntimeError(head + f"maxpool: kernel {flat[0]}, stride {flat[1]}, padding {flat[2]}, dilation {flat[3]}, ceil_mode {flat[4]}; "
+                               "only 3 / 2 / 1 with dilation 1 and ceil_mode off is implemented")
+        w = body.conv1.weight.detach().to(torch.float32)
+        if not bool((w.half().float().abs() <= 65504.0).all()):
+            raise RuntimeError(head + "conv1.weight holds a value that is not finite or rounds beyond fp16's range (65504)")
+        m = cls()
+        m.conv1 = ConvWeight(d)
+        m.conv1.weight.data = w.clone()
+        m.bn1 = _read_norm("bn1", body.bn1, d.cout, who="ResNetStem")
+        m.to(body.conv1.weight.device)
+        m.train(getattr(body, "training", False))
+        return m
+
+    def _weights(self, with_pointers: bool):
+        keep = []
+
+        def ptr(t):
+            if not with_pointers:
+                return None
+            _require_cuda(t, "ResNetStem weights")
+            t = t.detach().to(torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        n = self.bn1
+        w = _lib.hg_resnet_stem_weights(self.conv1.desc.struct(ptr(self.conv1.weight)),
+                                        _lib.hg_resnet_norm(ptr(n.weight), ptr(n.bias), ptr(n.running_mean), ptr(n.running_var), n.eps), *self.pool)
+        return w, keep
+
+    @staticmethod
+    def out_shape(Hi: int, Wi: int) -> Tuple[int, int, int]:
+        """(64, Hp, Wp) of an ``Hi x Wi`` image - hg_resnet_stem_out_shape, pure host."""
+        h, w = C.c_int32(), C.c_int32()
+        rc = _lib.lib().hg_resnet_stem_out_shape(Hi, Wi, C.byref(h), C.byref(w))
+        if rc:
+            raise RuntimeError(f"hoigen_amd: hg_resnet_stem_out_shape({Hi}, {Wi}) failed ({rc})")
+        return 64, h.value, w.value
+
+    def set_option(self, key: str, value: int) -> None:
+        self._ctx.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self._ctx.get_option(key)
+
+    def _load(self, device: torch.device) -> int:
+        h = self._ctx.get(device)
+        sig = (h, tuple((t.data_ptr(), t._version) for t in self.buffers()), self.bn1.eps)
+        if sig != self._sig:
+            w, keep = self._weights(True)
+            self._ctx.check(_lib.lib().hg_load_resnet_stem(h, C.byref(w)), "hg_load_resnet_stem")
+            self._sig = sig
+        return h
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``images [B, 3, Hi, Wi]`` (fp32 with a column stride of 1 is read where it lies through its strides; anything else is
+        converted once) -> the stem's map, fp32 ``[B, 64, Hp, Wp]``; ``out``: write into this tensor or view instead."""
+        x = _images(images, "ResNetStem images")
+        B, _, Hi, Wi = (int(v) for v in x.shape)
+        h = self._load(x.device)
+        Co, Hp, Wp = self.out_shape(Hi, Wi)
+        if out is None:
+            out = torch.empty(B, Co, Hp, Wp, device=x.device, dtype=torch.float32)
+        elif tuple(out.shape) != (B, Co, Hp, Wp) or out.dtype != torch.float32 or out.device != x.device or out.stride(3) != 1 or \
+                (Hp > 1 and out.stride(2) != Wp):
+            raise RuntimeError(f"hoigen_amd: ResNetStem: out must be an fp32 [{B}, {Co}, {Hp}, {Wp}] tensor (or view) on the images' device whose "
+                               "tokens are contiguous within a channel")
+        a = _lib.hg_resnet_stem_args()
+        a.x, a.B, a.Hi, a.Wi, a.out = x.data_ptr(), B, Hi, Wi, out.data_ptr()
+        a.x_stride[:] = [x.stride(0), x.stride(1), x.stride(2)]
+        a.out_stride[:] = [out.stride(0), out.stride(1)]
+        self._ctx.check(_lib.lib().hg_resnet_stem(h, C.byref(a), _stream_ptr(x.device)), "hg_resnet_stem")
+        return out
+
+
+class NativeBody(nn.Module):
+    """The body the reference builds at backbone.py:69-73 with the stages native: ``forward(images)`` returns ``{'0': layer4's map}`` as
+    ``IntermediateLayerGetter`` does, so it drops into ``Detector``.  The stem is the torch modules (``stem``) by default; with
+    ``native_stem=True`` it is ``ResNetStem`` on the stages' context and ``forward`` is one native call (hg_resnet_body)."""
+
+    def __init__(self, stem: Sequence[nn.Module], stages: ResNetStages, native_stem: Optional[ResNetStem] = None):
         super().__init__()
         self.stem = nn.Sequential(*stem)
         self.stages = stages
+        self.native_stem = native_stem
+        if native_stem is not None:
+            native_stem._ctx = stages._ctx
 
     @classmethod
-    def from_module(cls, body: nn.Module) -> "NativeBody":
+    def from_module(cls, body: nn.Module, native_stem: bool = False) -> "NativeBody":
         missing = [k for k in ("conv1", "bn1", "relu", "maxpool") if getattr(body, k, None) is None]
         if missing:
             raise RuntimeError(f"hoigen_amd: NativeBody.from_module: the body ({type(body).__name__}) has no {missing}")
-        m = cls([body.conv1, body.bn1, body.relu, body.maxpool], ResNetStages.from_module(body))
+        if native_stem:
+            m = cls([], ResNetStages.from_module(body), ResNetStem.from_module(body))
+        else:
+            m = cls([body.conv1, body.bn1, body.relu, body.maxpool], ResNetStages.from_module(body))
         m.train(getattr(body, "training", False))
         return m
+
+    def _run_body(self, images: torch.Tensor, last_block: Optional[int] = None, out: Optional[torch.Tensor] = None, want_trace: bool = False):
+        """hg_resnet_body: (map, every block's output or None)"""
+        st, sg = self.native_stem, self.stages
+        x = _images(images, "NativeBody images")
+        B, _, Hi, Wi = (int(v) for v in x.shape)
+        n = len(sg.blocks())
+        last = n - 1 if last_block is None else int(last_block)
+        if not (0 <= last < n):
+            raise RuntimeError(f"hoigen_amd: NativeBody: blocks 0 .. {last} of {n}")
+        if sg._ctx is not st._ctx:
+            raise RuntimeError("hoigen_amd: NativeBody: the stem and the stages must share one native context")
+        h = sg._load(x.device)
+        st._load(x.device)
+        _, Hp, Wp = st.out_shape(Hi, Wi)
+        Co, Ho, Wo = sg.out_shape(Hp, Wp, 0, last)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        if out is None:
+            out = torch.empty(B, Co, Ho, Wo, **f32)
+        elif tuple(out.shape) != (B, Co, Ho, Wo) or out.dtype != torch.float32 or out.device != x.device or out.stride(3) != 1 or \
+                (Ho > 1 and out.stride(2) != Wo):
+            raise RuntimeError(f"hoigen_amd: NativeBody: out must be an fp32 [{B}, {Co}, {Ho}, {Wo}] tensor (or view) on the images' device whose "
+                               "tokens are contiguous within a channel")
+        a = _lib.hg_resnet_body_args()
+        a.x, a.B, a.Hi, a.Wi, a.last_block, a.out = x.data_ptr(), B, Hi, Wi, last, out.data_ptr()
+        a.x_stride[:] = [x.stride(0), x.stride(1), x.stride(2)]
+        a.out_stride[:] = [out.stride(0), out.stride(1)]
+        trace = None
+        if want_trace:
+            trace = [torch.empty(B, *sg.out_shape(Hp, Wp, 0, i), **f32) for i in range(last + 1)]
+            ptrs = (C.c_void_p * len(trace))(*[t.data_ptr() for t in trace])
+            a.trace = ptrs
+        st._ctx.check(_lib.lib().hg_resnet_body(h, C.byref(a), _stream_ptr(x.device)), "hg_resnet_body")
+        return out, trace
 
     @_inference_only
     @torch.no_grad()
     def forward(self, images: torch.Tensor):
+        if self.native_stem is not None:
+            return {"0": self._run_body(images)[0]}
         return {"0": self.stages._run(self.stem(images))[0]}

@@ -661,7 +661,8 @@ int hg_detr_neck(hg_ctx*, const hg_detr_neck_args* args, void* stream);
 /* ---- ResNet stages: the bottleneck blocks layer1 .. layer4 of the detector's body (detr/models/backbone.py:83-93 builds torchvision's
  * ResNet-50 with the FrozenBatchNorm2d of :19-55; inference.py:950 and main_tip_finetune.py:1057 choose it; the same network runs as
  * the DINO backbone at upt_tip_cache_model_free_finetune_distill3.py:1617) on one implicit-GEMM convolution
- * (hoigen_amd/csrc/hg_resnet_conv.hip).  The stem - conv1 7 x 7, bn1, ReLU, max-pool - stays with the caller. ---------------------------
+ * (hoigen_amd/csrc/hg_resnet_conv.hip).  The stem - conv1 7 x 7, bn1, ReLU, max-pool - stays with the caller of hg_resnet_stages;
+ * hg_resnet_stem computes it and hg_resnet_body runs both (below). -----------------------------------------------------------------------
  *
  * A block is conv1 -> bn1 -> ReLU -> conv2 -> bn2 -> ReLU -> conv3 -> bn3, + identity, -> ReLU; identity = the block's input, or
  * down_bn(down_conv(input)) where has_downsample.  Convolutions read fp16 operands (the weight rounded once, the activation rounded once)
@@ -726,6 +727,61 @@ typedef struct {
     float* const* trace;
 } hg_resnet_args;
 int hg_resnet_stages(hg_ctx*, const hg_resnet_args* args, void* stream);
+
+/* ---- ResNet stem: conv1 7 x 7 / 2 pad 3 (3 -> 64), bn1, ReLU and the 3 x 3 / 2 pad 1 max-pool in front of the stages, as ONE launch
+ * (hoigen_amd/csrc/hg_resnet_stem.hip; backbone.py:83-93 under the FrozenBatchNorm2d of :19-55). -----------------------------------
+ *
+ * out = maxpool(relu(fmaf(conv(x, w), scale, bias))).  Arithmetic: every image value and every weight is rounded once to fp16 (RNE);
+ * the 147 products of a conv pixel are accumulated in fp32 from zero on the matrix unit in one fixed order, k = (c 7 + r) 8 + s ascending
+ * (c input channel, r tap row, s tap column; s = 7 and (c 7 + r) >= 21 are zero padding of K to 192 on both operands) - no split over K, no
+ * atomics, so a conv pixel is a fixed function of its own window; scale and bias are made on the host in double exactly as for the
+ * stages and applied as one fmaf; relu(v) = v < 0 ? 0 : v; the max is over the conv pixels of the 3 x 3 window that lie inside the
+ * conv map (a position outside it takes no part) and keeps a NaN as torch's max_pool2d does; padding of the image is real zeros that
+ * form no address.  The non-finite outputs are exactly those whose windows hold a non-finite input.  Sizes: Hc = (Hi - 1) / 2 + 1,
+ * Hp = (Hc - 1) / 2 + 1 in integer division, the same for W.
+ *
+ * hg_load_resnet_stem: a slot of its own beside the stages.  Pointers as for hg_load_resnet_stages.  Synchronous.  HG_ERR_INVALID with
+ * a message, nothing launched and the slot keeping what it held for: a convolution other than 7 x 7, stride (2, 2), padding (3, 3),
+ * dilation 1, groups 1, no bias, 3 -> 64 channels; a pool other than kernel 3, stride 2, padding 1, dilation 1, ceil_mode 0; an eps
+ * outside [0, 1]; a null pointer; and, after the weights were read, a weight that is not finite or rounds beyond fp16's range. */
+typedef struct {
+    hg_resnet_conv conv1;
+    hg_resnet_norm bn1;
+    int32_t pool_kernel, pool_stride, pool_padding, pool_dilation, pool_ceil_mode;
+} hg_resnet_stem_weights;
+int hg_load_resnet_stem(hg_ctx*, const hg_resnet_stem_weights*);
+/* hg_resnet_stem_out_shape: pure host, no context.  The pooled size of an Hi x Wi image.  HG_ERR_INVALID for Hi or Wi < 1. */
+int hg_resnet_stem_out_shape(int Hi, int Wi, int32_t* Hp, int32_t* Wp);
+/* hg_resnet_stem: the stem's map of a batch of images.
+ *   x      DEVICE fp32 [B, 3, Hi, Wi] through element strides x_stride = (image, channel, row); the column stride is 1.  Any Wi, any
+ *          row stride, any 4-byte aligned base: read where it lies with 64-bit offsets, and nothing beyond its last element is read.
+ *   out    fp32 [B, 64, Hp, Wp] through out_stride = (image, channel) in elements, token stride 1: what hg_resnet_stages takes as x.
+ * Asynchronous on `stream`; no host wait.  Workspace (grow-only, the context's): 6 B Hp Wp 64 bytes, the NHWC fp32 + fp16 pair the
+ * kernel writes.  HG_ERR_NOT_LOADED before a load; HG_ERR_INVALID with a message and nothing launched for B outside 1 .. 64, Hi or Wi
+ * outside 1 .. 4096 (a pooled map of at most 1024 a side), a null or misaligned x, a null out. */
+typedef struct {
+    const float* x;
+    int64_t x_stride[3];                   /* elements: image, channel, row */
+    int32_t B, Hi, Wi;
+    float* out;
+    int64_t out_stride[2];                 /* elements: image, channel */
+} hg_resnet_stem_args;
+int hg_resnet_stem(hg_ctx*, const hg_resnet_stem_args* args, void* stream);
+/* hg_resnet_body: the stem and blocks 0 .. last_block of the loaded stages from the images, as hg_resnet_stem followed by
+ * hg_resnet_stages would compute them, bit for bit - but the stem kernel writes straight into the stages' workspace pair: there is no
+ * NCHW stem map and no layout pass between the two.  x as hg_resnet_stem's; out, trace as hg_resnet_stages' (trace: last_block + 1
+ * pointers).  Workspace: hg_resnet_stages' rule with the stem's B Hp Wp 64 as block 0's input.  HG_ERR_NOT_LOADED if either slot is
+ * empty; HG_ERR_INVALID if the stem's cout is not block 0's cin, and for what either call refuses. */
+typedef struct {
+    const float* x;
+    int64_t x_stride[3];
+    int32_t B, Hi, Wi;
+    int32_t last_block;
+    float* out;
+    int64_t out_stride[2];
+    float* const* trace;
+} hg_resnet_body_args;
+int hg_resnet_body(hg_ctx*, const hg_resnet_body_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -844,6 +900,7 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_DETR_ROWS 105 /* row kernels of hg_detr_decoder (entries, post-norms, tails): M = rows, N = d_model, K = slices summed */
 #define HG_PROF_DETR_NECK 106 /* hg_detr_neck's launch(es): M = rows (B * H * W), N = slices of cin, K = cin */
 #define HG_PROF_RESNET_CONV 107 /* one convolution launch of hg_resnet_stages / hg_test_resnet_conv: M = output pixels (B * Ho * Wo), N = cout, K = k * k * cin */
+#define HG_PROF_RESNET_STEM 108 /* the stem launch of hg_resnet_stem / hg_resnet_body / hg_test_resnet_stem: M = pooled pixels (B * Hp * Wp), N = 64, K = 147 */
 #define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
@@ -1086,6 +1143,21 @@ typedef struct {
     int32_t B, H, W, cin, cout, k, stride, epi, tile;
 } hg_test_resnet_conv_args;
 int hg_test_resnet_conv(hg_ctx*, const hg_test_resnet_conv_args* args, void* stream);
+
+/* Test hook for the stem (hoigen_amd/csrc/hg_resnet_stem.hip): ONE launch from fp32 device tensors, the loader's packing included.
+ * x [B, 3, Hi, Wi] contiguous NCHW, read where the caller put it (any 4-byte aligned address; the caller makes the allocation exactly
+ * its size); w [64, 3, 7, 7]; scale, bias [64].  out32 / out16 [B Hp Wp, 64] fp32 NHWC (the fp16 output comes back as fp32).  There is
+ * one tile shape, so no selector.  Synchronous.  HG_ERR_INVALID where the launcher refuses. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* scale;
+    const float* bias;
+    float* out32;
+    float* out16;
+    int32_t B, Hi, Wi;
+} hg_test_resnet_stem_args;
+int hg_test_resnet_stem(hg_ctx*, const hg_test_resnet_stem_args* args, void* stream);
 
 #ifdef __cplusplus
 }
