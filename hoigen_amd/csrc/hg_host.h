@@ -1,5 +1,6 @@
-// What the host files of the C ABI share (hg_api.hip, hg_load.hip, hg_tower.hip, hg_heads.hip, hg_test_hooks.hip): the context and the
-// weight structs, error reporting, the grow-only workspace, the profiler scope and the GEMM / attention wrappers.  Host code only.
+// What the host files of the C ABI share (hg_api.hip, hg_load.hip, hg_tower.hip, hg_heads.hip, hg_detector_views.hip, hg_detr.hip,
+// hg_detr_dec.hip, hg_detr_ends.hip, hg_resnet.hip, hg_test_hooks.hip): the context and the weight structs, error reporting, the
+// grow-only workspace, the weight helpers of the loaders, the profiler scope and the GEMM / attention wrappers.  Host code only.
 //
 // Device data layout:
 //   residual stream x   fp32 [M, D]      M = n_seq * L rows (token-major, sequence-contiguous)
@@ -271,7 +272,7 @@ struct hg_ctx {
                                      // 1 the two GEMMs, 2 the split kernel or HG_ERR_INVALID
     int opt_detr_ffn_max_m = 1000;   // ... rows (B * Q) up to which 0 picks the split kernel: it wins by 25 - 31 us a layer from 100 to 950 rows; at 2 888 rows
                                      // by 7 us, which is the spread of repeated runs (profiles/detr_decoder.txt)
-    int opt_detr_neck_split = 0;     // slices of Cin of hg_detr_neck's projection: 0 the rule of detr_neck_default_split (hg_detr.hip), 1 no split, n that many
+    int opt_detr_neck_split = 0;     // slices of Cin of hg_detr_neck's projection: 0 the rule of detr_neck_default_split (hg_detr_ends.hip), 1 no split, n that many
     int opt_mlp_pair_fault = 0;      // fault injection for the tests: that launch goes out one workgroup short, so that a hand-off wait meets its bound
     int n_cu = 256;
     // sticky device->host flag (host-mapped): a hand-off wait inside the MLP pair kernel gave up (a workgroup of its grid never became
@@ -370,6 +371,55 @@ inline void free_all(std::vector<void*>& v) {
 }
 
 inline size_t rup(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// ---- weights into device memory: what every loader shares (synchronous; load time only) ------------------------------------------------
+inline int dev_alloc(hg_ctx* c, std::vector<void*>& owned, size_t bytes, void** out) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    if (e != hipSuccess) return fail(c, HG_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    owned.push_back(p);
+    *out = p;
+    return HG_OK;
+}
+
+template <typename T>
+inline int dev_alloc_n(hg_ctx* c, std::vector<void*>& owned, size_t n, T** out) {      // n elements
+    void* p;
+    int rc = dev_alloc(c, owned, n * sizeof(T), &p);
+    if (!rc) *out = (T*)p;
+    return rc;
+}
+
+// n elements of t from element `off` on, as fp16 / fp32, into dst: a copy where the dtype matches, the conversion kernel where it is the
+// other one.  The message is `who` ("" or "hg_load_x: ") and the tensor's `name` as the caller formatted it.
+inline int cvt_f16(hg_ctx* c, const hg_tensor& t, size_t off, size_t n, half_t* dst, const char* who, const char* name) {
+    if (!t.ptr) return fail(c, HG_ERR_INVALID, "%smissing tensor %s", who, name);
+    if (t.dtype == HG_F16) HG_HIP(hipMemcpy(dst, (const half_t*)t.ptr + off, n * 2, hipMemcpyDeviceToDevice));
+    else if (t.dtype == HG_F32) HG_HIP(launch_f32_to_f16((const float*)t.ptr + off, dst, n, 0));
+    else return fail(c, HG_ERR_INVALID, "%sbad dtype for %s", who, name);
+    return HG_OK;
+}
+
+inline int cvt_f32(hg_ctx* c, const hg_tensor& t, size_t off, size_t n, float* dst, const char* who, const char* name) {
+    if (!t.ptr) return fail(c, HG_ERR_INVALID, "%smissing tensor %s", who, name);
+    if (t.dtype == HG_F32) HG_HIP(hipMemcpy(dst, (const float*)t.ptr + off, n * 4, hipMemcpyDeviceToDevice));
+    else if (t.dtype == HG_F16) HG_HIP(launch_f16_to_f32((const half_t*)t.ptr + off, dst, n, 0));
+    else return fail(c, HG_ERR_INVALID, "%sbad dtype for %s", who, name);
+    return HG_OK;
+}
+
+// ... into memory of their own, which `owned` keeps
+inline int as_f16(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, size_t n, half_t** out, const char* name, const char* who = "",
+                  size_t off = 0) {
+    int rc = dev_alloc_n(c, owned, n, out);
+    return rc ? rc : cvt_f16(c, t, off, n, *out, who, name);
+}
+
+inline int as_f32(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, size_t n, float** out, const char* name, const char* who = "",
+                  size_t off = 0) {
+    int rc = dev_alloc_n(c, owned, n, out);
+    return rc ? rc : cvt_f32(c, t, off, n, *out, who, name);
+}
 
 // hipEvent pair around one launch when its kind is being profiled
 struct ProfScope {

@@ -4,40 +4,7 @@
 
 namespace {
 
-// ---- weight conversion helpers (synchronous; load time only) ------------------------------------
-int dev_alloc(hg_ctx* c, std::vector<void*>& owned, size_t bytes, void** out) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(c, HG_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    owned.push_back(p);
-    *out = p;
-    return HG_OK;
-}
-
-int as_f16(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, size_t n, half_t** out, const char* name) {
-    if (!t.ptr) return fail(c, HG_ERR_INVALID, "missing tensor %s", name);
-    void* p;
-    int rc = dev_alloc(c, owned, n * 2, &p);
-    if (rc) return rc;
-    if (t.dtype == HG_F16) HG_HIP(hipMemcpy(p, t.ptr, n * 2, hipMemcpyDeviceToDevice));
-    else if (t.dtype == HG_F32) HG_HIP(launch_f32_to_f16((const float*)t.ptr, (half_t*)p, n, 0));
-    else return fail(c, HG_ERR_INVALID, "bad dtype for %s", name);
-    *out = (half_t*)p;
-    return HG_OK;
-}
-
-int as_f32(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, size_t n, float** out, const char* name) {
-    if (!t.ptr) return fail(c, HG_ERR_INVALID, "missing tensor %s", name);
-    void* p;
-    int rc = dev_alloc(c, owned, n * 4, &p);
-    if (rc) return rc;
-    if (t.dtype == HG_F32) HG_HIP(hipMemcpy(p, t.ptr, n * 4, hipMemcpyDeviceToDevice));
-    else if (t.dtype == HG_F16) HG_HIP(launch_f16_to_f32((const half_t*)t.ptr, (float*)p, n, 0));
-    else return fail(c, HG_ERR_INVALID, "bad dtype for %s", name);
-    *out = (float*)p;
-    return HG_OK;
-}
-
+// ---- weight conversion helpers beyond hg_host.h's dev_alloc / as_f16 / as_f32 (synchronous; load time only) -------------------------------
 // [rows, cols] -> fp16 [cols, rows]
 int as_f16_T(hg_ctx* c, std::vector<void*>& owned, const hg_tensor& t, int rows, int cols, half_t** out,
              const char* name) {

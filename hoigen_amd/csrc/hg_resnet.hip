@@ -68,24 +68,15 @@ int check_blocks(hg_ctx* c, const hg_resnet_weights* w) {
     return HG_OK;
 }
 
-int resnet_alloc(hg_ctx* c, std::vector<void*>& owned, size_t bytes, void** out) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(c, HG_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    owned.push_back(p);
-    *out = p;
-    return HG_OK;
-}
-
 // one convolution and its norm: the packed fp16 weight, and scale / bias made in double and rounded to fp32 (backbone.py:45-55)
 int load_conv(hg_ctx* c, std::vector<void*>& owned, const hg_resnet_conv& v, const hg_resnet_norm& n, int* flag, ResnetConvW& d) {
     d.cin = v.cin; d.cout = v.cout; d.R = v.kh; d.stride = v.stride_h;
     const size_t nw = (size_t)v.cout * v.cin * v.kh * v.kh;
     const bool stem = v.kh == 7;      // hg_load_resnet_stem: hg_resnet_stem.hip's fragment order
     void *pw, *ps, *pb;
-    int rc = resnet_alloc(c, owned, stem ? RESNET_STEM_W_HALFS * 2 : nw * 2, &pw);
-    if (!rc) rc = resnet_alloc(c, owned, (size_t)v.cout * 4, &ps);
-    if (!rc) rc = resnet_alloc(c, owned, (size_t)v.cout * 4, &pb);
+    int rc = dev_alloc(c, owned, stem ? RESNET_STEM_W_HALFS * 2 : nw * 2, &pw);
+    if (!rc) rc = dev_alloc(c, owned, (size_t)v.cout * 4, &ps);
+    if (!rc) rc = dev_alloc(c, owned, (size_t)v.cout * 4, &pb);
     if (rc) return rc;
     if (stem) HG_HIP(launch_resnet_stem_pack(v.weight, (half_t*)pw, flag, 0));
     else HG_HIP(launch_resnet_pack(v.weight, (half_t*)pw, v.cout, v.cin, v.kh, flag, 0));
@@ -244,7 +235,7 @@ int hg_load_resnet_stages(hg_ctx* c, const hg_resnet_weights* w) {
     ResnetStages n;
     n.blocks.resize(w->n_blocks);
     void* flags = nullptr;
-    rc = resnet_alloc(c, n.owned, (size_t)w->n_blocks * 4 * sizeof(int), &flags);
+    rc = dev_alloc(c, n.owned, (size_t)w->n_blocks * 4 * sizeof(int), &flags);
     if (!rc) {
         hipError_t e = hipMemset(flags, 0, (size_t)w->n_blocks * 4 * sizeof(int));
         if (e != hipSuccess) rc = fail(c, HG_ERR_HIP, "hg_load_resnet_stages: hipMemset failed: %s", hipGetErrorString(e));
@@ -325,7 +316,7 @@ int hg_load_resnet_stem(hg_ctx* c, const hg_resnet_stem_weights* w) {
     HG_HIP(hipDeviceSynchronize());      // a call in flight may still read the weights this load replaces
     ResnetStem n;
     void* flag = nullptr;
-    rc = resnet_alloc(c, n.owned, 16, &flag);
+    rc = dev_alloc(c, n.owned, 16, &flag);
     if (!rc) {
         hipError_t e = hipMemset(flag, 0, 16);
         if (e != hipSuccess) rc = fail(c, HG_ERR_HIP, "hg_load_resnet_stem: hipMemset failed: %s", hipGetErrorString(e));

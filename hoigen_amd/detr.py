@@ -7,10 +7,10 @@ hg_detr_decoder).
 
 is the whole integration; the two halves can be swapped on their own as well.  ``DetectionHeads`` is what follows the
 transformer in the detector (upt_tip_cache_model_free_finetune_distill3.py:1598-1605): ``class_embed``, ``bbox_embed`` with its sigmoid
-and ``PostProcess`` in one launch (hg_detr_heads.hip: hg_load_detr_heads, hg_detr_heads).  ``DetectorNeck`` is what precedes it
-(upt...:1594-1597): ``input_proj``, ``PositionEmbeddingSine`` and the mask on the feature grid in one call (hg_detr_neck.hip:
-hg_load_detr_neck, hg_detr_neck), whose batch-first outputs ``Transformer.forward_tokens`` takes; ``Detector`` is lines 1594-1605 as one
-object.  Inference only; tensors must live on a HIP device.
+and ``PostProcess`` in one launch (the kernel hg_detr_heads.hip under hg_load_detr_heads, hg_detr_heads).  ``DetectorNeck`` is what
+precedes it (upt...:1594-1597): ``input_proj``, ``PositionEmbeddingSine`` and the mask on the feature grid in one call (the kernel
+hg_detr_neck.hip under hg_load_detr_neck, hg_detr_neck), whose batch-first outputs ``Transformer.forward_tokens`` takes; the host code
+of both is hg_detr_ends.hip.  ``Detector`` is lines 1594-1605 as one object.  Inference only; tensors must live on a HIP device.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .model import LayerNorm, Linear, MultiheadAttention, _Ctx, _inference_only, _require_cuda, _sig, _stream_ptr
+from .model import LayerNorm, Linear, MultiheadAttention, _inference_only, _NativeModule, _require_cuda, _sig, _stream_ptr
 from .resnet import NativeBody, ResNetStages, ResNetStem  # noqa: F401  (the body's native stem and stages: hoigen_amd/resnet.py)
 
 MAX_TOKENS = _lib.HG_DETR_ATTN_MAX_L
@@ -43,7 +43,46 @@ def _is_relu(fn) -> bool:
     return fn is torch.nn.functional.relu or isinstance(fn, nn.ReLU) or getattr(fn, "__name__", "") == "relu"
 
 
-class TransformerEncoder(nn.Module):
+def _f32_rows(t: torch.Tensor) -> torch.Tensor:
+    """fp32 with a channel stride of 1: a permuted view of a batch-first buffer passes as it is, the [S, B, C] view of a [B, C, H, W]
+    map (flatten(2).permute(2, 0, 1)) is copied"""
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.stride(-1) == 1 else t.to(torch.float32).contiguous()
+
+
+def _from_stack(cls, stack: nn.Module, what: str, layer_lines: str, *extra):
+    """``TransformerEncoder.from_module`` / ``TransformerDecoder.from_module``: the layers of ``stack`` (the reference's ``what``) must be
+    post-norm (transformer.py:``layer_lines``) ReLU layers with the state-dict keys of ``cls``; ``extra`` follows the four sizes into ``cls``."""
+    who = f"hoigen_amd: {cls.__name__}.from_module:"
+    layers = list(stack.layers)
+    if not layers:
+        raise RuntimeError(f"{who} the {what} has no layers")
+    for i, l in enumerate(layers):
+        if getattr(l, "normalize_before", False):
+            raise RuntimeError(f"{who} layers.{i} is pre-norm (normalize_before); only the post-norm layer (transformer.py:{layer_lines}) "
+                               "is implemented")
+        act = getattr(l, "activation", torch.nn.functional.relu)
+        if not _is_relu(act):
+            raise RuntimeError(f"{who} layers.{i} uses activation {act!r}; only ReLU is implemented")
+    w = layers[0].self_attn.in_proj_weight
+    m = cls(int(w.shape[1]), int(layers[0].self_attn.num_heads), len(layers), int(layers[0].linear1.weight.shape[0]), *extra)
+    missing, unexpected = m.load_state_dict(stack.state_dict(), strict=False)
+    if missing or unexpected:
+        raise RuntimeError(f"{who} state-dict keys differ (missing {missing}, unexpected {unexpected})")
+    m.to(device=w.device, dtype=w.dtype)
+    m.train(stack.training)
+    return m
+
+
+def _layer_tensors(l: nn.Module) -> list:
+    """The twelve tensors an encoder layer and a decoder layer both hold, in the order of hg_detr_layer_weights"""
+    t = _lib.tensor
+    return [t(l.self_attn.in_proj_weight), t(l.self_attn.in_proj_bias), t(l.self_attn.out_proj.weight), t(l.self_attn.out_proj.bias),
+            t(l.linear1.weight), t(l.linear1.bias), t(l.linear2.weight), t(l.linear2.bias), t(l.norm1.weight), t(l.norm1.bias),
+            t(l.norm2.weight), t(l.norm2.bias)]
+
+
+class TransformerEncoder(_NativeModule):
     """detr/models/transformer.py:62-83.  ``forward(src, mask=None, src_key_padding_mask=None, pos=None)`` on ``[S, B, C]`` tensors
     returns ``[S, B, C]`` fp32.  Post-norm ReLU layers without a final norm - what the detector builds (transformer.py:26-29 with
     normalize_before = False); anything else is refused."""
@@ -53,8 +92,6 @@ class TransformerEncoder(nn.Module):
         self.d_model, self.nhead, self.num_layers, self.dim_feedforward = d_model, nhead, num_layers, dim_feedforward
         self.layers = nn.ModuleList([TransformerEncoderLayer(d_model, nhead, dim_feedforward) for _ in range(num_layers)])
         self.norm = None
-        self._ctx = _Ctx()
-        self._sig = None
 
     @classmethod
     def from_module(cls, encoder: nn.Module) -> "TransformerEncoder":
@@ -63,48 +100,12 @@ class TransformerEncoder(nn.Module):
         if getattr(encoder, "norm", None) is not None:
             raise RuntimeError("hoigen_amd: TransformerEncoder.from_module: a final norm (the pre-norm encoder, transformer.py:28) is not "
                                "implemented; the detector's encoder is post-norm and has none")
-        layers = list(encoder.layers)
-        if not layers:
-            raise RuntimeError("hoigen_amd: TransformerEncoder.from_module: the encoder has no layers")
-        for i, l in enumerate(layers):
-            if getattr(l, "normalize_before", False):
-                raise RuntimeError(f"hoigen_amd: TransformerEncoder.from_module: layers.{i} is pre-norm (normalize_before); only the post-norm "
-                                   "layer (transformer.py:149-162) is implemented")
-            act = getattr(l, "activation", torch.nn.functional.relu)
-            if not _is_relu(act):
-                raise RuntimeError(f"hoigen_amd: TransformerEncoder.from_module: layers.{i} uses activation {act!r}; only ReLU is implemented")
-        w = layers[0].self_attn.in_proj_weight
-        d_model, nhead, d_ff = int(w.shape[1]), int(layers[0].self_attn.num_heads), int(layers[0].linear1.weight.shape[0])
-        m = cls(d_model, nhead, len(layers), d_ff)
-        missing, unexpected = m.load_state_dict(encoder.state_dict(), strict=False)
-        if missing or unexpected:
-            raise RuntimeError(f"hoigen_amd: TransformerEncoder.from_module: state-dict keys differ (missing {missing}, unexpected {unexpected})")
-        m.to(device=w.device, dtype=w.dtype)
-        m.train(encoder.training)
-        return m
+        return _from_stack(cls, encoder, "encoder", "149-162")
 
-    def set_option(self, key: str, value: int) -> None:
-        """Behaviour option of this module's native context (include/hoigen_amd.h), e.g. ``detr_attn_chunk``."""
-        self._ctx.set_option(key, value)
-
-    def get_option(self, key: str):
-        return self._ctx.get_option(key)
-
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, _sig(self.parameters()))
-        if sig != self._sig:
-            t = _lib.tensor
-            arr = (_lib.hg_detr_layer_weights * self.num_layers)()
-            for i, l in enumerate(self.layers):
-                arr[i] = _lib.hg_detr_layer_weights(
-                    t(l.self_attn.in_proj_weight), t(l.self_attn.in_proj_bias), t(l.self_attn.out_proj.weight), t(l.self_attn.out_proj.bias),
-                    t(l.linear1.weight), t(l.linear1.bias), t(l.linear2.weight), t(l.linear2.bias), t(l.norm1.weight), t(l.norm1.bias),
-                    t(l.norm2.weight), t(l.norm2.bias))
-            w = _lib.hg_detr_encoder_weights(self.d_model, self.nhead, self.dim_feedforward, self.num_layers, 0, 0, arr)
-            self._ctx.check(_lib.lib().hg_load_detr_encoder(h, C.byref(w)), "hg_load_detr_encoder")
-            self._sig = sig
-        return h
+    def _load_native(self, h: int) -> None:
+        arr = (_lib.hg_detr_layer_weights * self.num_layers)(*[_lib.hg_detr_layer_weights(*_layer_tensors(l)) for l in self.layers])
+        w = _lib.hg_detr_encoder_weights(self.d_model, self.nhead, self.dim_feedforward, self.num_layers, 0, 0, arr)
+        self._ctx.check(_lib.lib().hg_load_detr_encoder(h, C.byref(w)), "hg_load_detr_encoder")
 
     def _run(self, src, mask, src_key_padding_mask, pos, want_trace: bool, out: Optional[torch.Tensor] = None, trace=None):
         if mask is not None:
@@ -117,16 +118,11 @@ class TransformerEncoder(nn.Module):
             raise RuntimeError(f"hoigen_amd: TransformerEncoder: src must be [S, B, {self.d_model}] (got {tuple(src.shape)})")
         S, B, D = src.shape
         h = self._load(src.device)
-
-        def f32(t):      # fp32 with a channel stride of 1: the [S, B, C] view of a [B, C, H, W] map (flatten(2).permute(2, 0, 1)) is copied
-            t = t.detach()
-            return t if t.dtype == torch.float32 and t.stride(2) == 1 else t.to(torch.float32).contiguous()
-
-        x = f32(src)
+        x = _f32_rows(src)
         p = None
         if pos is not None:
             _require_cuda(pos, "TransformerEncoder pos")
-            p = f32(pos).expand(S, B, D)
+            p = _f32_rows(pos).expand(S, B, D)
         kpm = None
         if src_key_padding_mask is not None:
             _require_cuda(src_key_padding_mask, "TransformerEncoder src_key_padding_mask")
@@ -179,7 +175,7 @@ class TransformerDecoderLayer(nn.Module):
         self.norm3 = LayerNorm(d_model)
 
 
-class TransformerDecoder(nn.Module):
+class TransformerDecoder(_NativeModule):
     """detr/models/transformer.py:86-124.  ``forward(tgt, memory, ..., memory_key_padding_mask, pos, query_pos)`` on ``[Q, B, C]`` /
     ``[S, B, C]`` tensors returns ``[L, Q, B, C]`` fp32 with ``return_intermediate`` and ``[1, Q, B, C]`` without.  Post-norm ReLU layers
     with the final norm - what the detector builds (transformer.py:31-35); anything else is refused."""
@@ -191,8 +187,6 @@ class TransformerDecoder(nn.Module):
         self.layers = nn.ModuleList([TransformerDecoderLayer(d_model, nhead, dim_feedforward) for _ in range(num_layers)])
         self.norm = LayerNorm(d_model)
         self.return_intermediate = bool(return_intermediate)
-        self._ctx = _Ctx()
-        self._sig = None
 
     @classmethod
     def from_module(cls, decoder: nn.Module) -> "TransformerDecoder":
@@ -201,51 +195,17 @@ class TransformerDecoder(nn.Module):
         if getattr(decoder, "norm", None) is None:
             raise RuntimeError("hoigen_amd: TransformerDecoder.from_module: the decoder has no final norm (norm is None); the detector's "
                                "decoder has one (transformer.py:33) and only that form is implemented")
-        layers = list(decoder.layers)
-        if not layers:
-            raise RuntimeError("hoigen_amd: TransformerDecoder.from_module: the decoder has no layers")
-        for i, l in enumerate(layers):
-            if getattr(l, "normalize_before", False):
-                raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: layers.{i} is pre-norm (normalize_before); only the post-norm "
-                                   "layer (transformer.py:212-233) is implemented")
-            act = getattr(l, "activation", torch.nn.functional.relu)
-            if not _is_relu(act):
-                raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: layers.{i} uses activation {act!r}; only ReLU is implemented")
-        w = layers[0].self_attn.in_proj_weight
-        d_model, nhead, d_ff = int(w.shape[1]), int(layers[0].self_attn.num_heads), int(layers[0].linear1.weight.shape[0])
-        m = cls(d_model, nhead, len(layers), d_ff, bool(getattr(decoder, "return_intermediate", False)))
-        missing, unexpected = m.load_state_dict(decoder.state_dict(), strict=False)
-        if missing or unexpected:
-            raise RuntimeError(f"hoigen_amd: TransformerDecoder.from_module: state-dict keys differ (missing {missing}, unexpected {unexpected})")
-        m.to(device=w.device, dtype=w.dtype)
-        m.train(decoder.training)
-        return m
+        return _from_stack(cls, decoder, "decoder", "212-233", bool(getattr(decoder, "return_intermediate", False)))
 
-    def set_option(self, key: str, value: int) -> None:
-        """Behaviour option of this module's native context (include/hoigen_amd.h), e.g. ``detr_ffn``, ``detr_attn_chunk``."""
-        self._ctx.set_option(key, value)
-
-    def get_option(self, key: str):
-        return self._ctx.get_option(key)
-
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, _sig(self.parameters()))
-        if sig != self._sig:
-            t = _lib.tensor
-            arr = (_lib.hg_detr_dec_layer_weights * self.num_layers)()
-            for i, l in enumerate(self.layers):
-                arr[i] = _lib.hg_detr_dec_layer_weights(
-                    t(l.self_attn.in_proj_weight), t(l.self_attn.in_proj_bias), t(l.self_attn.out_proj.weight), t(l.self_attn.out_proj.bias),
-                    t(l.linear1.weight), t(l.linear1.bias), t(l.linear2.weight), t(l.linear2.bias), t(l.norm1.weight), t(l.norm1.bias),
-                    t(l.norm2.weight), t(l.norm2.bias), t(l.multihead_attn.in_proj_weight), t(l.multihead_attn.in_proj_bias),
-                    t(l.multihead_attn.out_proj.weight), t(l.multihead_attn.out_proj.bias), t(l.norm3.weight), t(l.norm3.bias))
-            norm = self.norm
-            w = _lib.hg_detr_decoder_weights(self.d_model, self.nhead, self.dim_feedforward, self.num_layers, 0, 0,
-                                             t(norm.weight if norm is not None else None), t(norm.bias if norm is not None else None), arr)
-            self._ctx.check(_lib.lib().hg_load_detr_decoder(h, C.byref(w)), "hg_load_detr_decoder")
-            self._sig = sig
-        return h
+    def _load_native(self, h: int) -> None:
+        t = _lib.tensor
+        arr = (_lib.hg_detr_dec_layer_weights * self.num_layers)(*[_lib.hg_detr_dec_layer_weights(
+            *_layer_tensors(l), t(l.multihead_attn.in_proj_weight), t(l.multihead_attn.in_proj_bias), t(l.multihead_attn.out_proj.weight),
+            t(l.multihead_attn.out_proj.bias), t(l.norm3.weight), t(l.norm3.bias)) for l in self.layers])
+        norm = self.norm
+        w = _lib.hg_detr_decoder_weights(self.d_model, self.nhead, self.dim_feedforward, self.num_layers, 0, 0,
+                                         t(norm.weight if norm is not None else None), t(norm.bias if norm is not None else None), arr)
+        self._ctx.check(_lib.lib().hg_load_detr_decoder(h, C.byref(w)), "hg_load_detr_decoder")
 
     def _run(self, tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask, memory_key_padding_mask, pos, query_pos, want_trace: bool,
              out: Optional[torch.Tensor] = None):
@@ -259,17 +219,12 @@ class TransformerDecoder(nn.Module):
             raise RuntimeError(f"hoigen_amd: TransformerDecoder: memory must be [S, B, {D}] (got {tuple(memory.shape)})")
         S, B, _ = memory.shape
         dev = memory.device
-
-        def f32(t):      # fp32 with a channel stride of 1 (a permuted view of a batch-first buffer passes as it is)
-            t = t.detach()
-            return t if t.dtype == torch.float32 and t.stride(-1) == 1 else t.to(torch.float32).contiguous()
-
         if query_pos is None:
             if tgt is None:
                 raise RuntimeError("hoigen_amd: TransformerDecoder: tgt and query_pos are both None: the number of queries is unknown")
             query_pos = torch.zeros(tgt.shape[0], D, device=dev)
         _require_cuda(query_pos, "TransformerDecoder query_pos")
-        qp = f32(query_pos)
+        qp = _f32_rows(query_pos)
         if qp.dim() not in (2, 3) or qp.shape[-1] != D or (qp.dim() == 3 and qp.shape[1] != B):
             raise RuntimeError(f"hoigen_amd: TransformerDecoder: query_pos must be [Q, {D}] or [Q, B = {B}, {D}] (got {tuple(qp.shape)})")
         Q = int(qp.shape[0])
@@ -282,16 +237,16 @@ class TransformerDecoder(nn.Module):
             _require_cuda(tgt, "TransformerDecoder tgt")
             if tuple(tgt.shape) != (Q, B, D):
                 raise RuntimeError(f"hoigen_amd: TransformerDecoder: tgt must be [Q, B, C] = [{Q}, {B}, {D}] (got {tuple(tgt.shape)})")
-            tg = f32(tgt)
+            tg = _f32_rows(tgt)
             a.tgt = tg.data_ptr()
             a.tgt_stride[:] = [tg.stride(1), tg.stride(0), 1]
-        mem = f32(memory)
+        mem = _f32_rows(memory)
         a.memory = mem.data_ptr()
         a.memory_stride[:] = [mem.stride(1), mem.stride(0), 1]
         p = None
         if pos is not None:
             _require_cuda(pos, "TransformerDecoder pos")
-            p = f32(pos).expand(S, B, D)
+            p = _f32_rows(pos).expand(S, B, D)
             a.pos = p.data_ptr()
             a.pos_stride[:] = [p.stride(1), p.stride(0), 1]
         kpm = None
@@ -369,13 +324,18 @@ class Transformer(nn.Module):
         if src.dim() != 4 or src.shape[1] != self.d_model or pos_embed.shape != src.shape:
             raise RuntimeError(f"hoigen_amd: Transformer: src and pos_embed must be [B, {self.d_model}, H, W] (got {tuple(src.shape)}, "
                                f"{tuple(pos_embed.shape)})")
-        B, Cc, H, W = src.shape
-        S = H * W
-        src_s = src.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous().permute(1, 0, 2)          # [S, B, C] views of
-        pos_s = pos_embed.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous().permute(1, 0, 2)    # [B, S, C] buffers
-        kpm = mask.flatten(1) if mask is not None else None
+        H, W = src.shape[2:]
+        src_b = src.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous()      # [B, S, C] buffers
+        pos_b = pos_embed.detach().to(torch.float32).flatten(2).transpose(1, 2).contiguous()
+        return self._run_tokens(src_b, mask.flatten(1) if mask is not None else None, query_embed, pos_b, H, W)
+
+    def _run_tokens(self, src, kpm, query_embed, pos, H: int, W: int):
+        """Encoder and decoder on batch-first ``src`` / ``pos`` ``[B, S, C]`` fp32 with channel stride 1 and ``kpm [B, S]``: both read
+        them as [S, B, C] views through strides.  Returns ``(hs [L, B, Q, C], memory [B, C, H, W])``."""
+        B, S, Cc = src.shape
         mem = torch.empty(B, S, Cc, device=src.device, dtype=torch.float32)
-        self.encoder._run(src_s, None, kpm, pos_s, False, mem.permute(1, 0, 2))
+        pos_s = pos.permute(1, 0, 2)
+        self.encoder._run(src.permute(1, 0, 2), None, kpm, pos_s, False, mem.permute(1, 0, 2))
         L = self.decoder.num_layers if self.decoder.return_intermediate else 1
         hs = torch.empty(L, B, query_embed.shape[0], Cc, device=src.device, dtype=torch.float32)
         self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
@@ -392,15 +352,7 @@ class Transformer(nn.Module):
         if src.dim() != 3 or src.shape[2] != self.d_model or pos.shape != src.shape or src.shape[1] != H * W:
             raise RuntimeError(f"hoigen_amd: Transformer.forward_tokens: src and pos must be [B, S = H W = {H * W}, {self.d_model}] "
                                f"(got {tuple(src.shape)}, {tuple(pos.shape)})")
-        B, S, Cc = src.shape
-        kpm = mask.reshape(B, S) if mask is not None else None
-        mem = torch.empty(B, S, Cc, device=src.device, dtype=torch.float32)
-        pos_s = pos.permute(1, 0, 2)
-        self.encoder._run(src.permute(1, 0, 2), None, kpm, pos_s, False, mem.permute(1, 0, 2))
-        L = self.decoder.num_layers if self.decoder.return_intermediate else 1
-        hs = torch.empty(L, B, query_embed.shape[0], Cc, device=src.device, dtype=torch.float32)
-        self.decoder._run(None, mem.permute(1, 0, 2), None, None, None, kpm, pos_s, query_embed, False, hs.permute(0, 2, 1, 3))
-        return hs, mem.permute(0, 2, 1).view(B, Cc, H, W)
+        return self._run_tokens(src, mask.reshape(src.shape[:2]) if mask is not None else None, query_embed, pos, H, W)
 
 
 class BoxMLP(nn.Module):
@@ -412,10 +364,10 @@ class BoxMLP(nn.Module):
         self.layers = nn.ModuleList([Linear(d_model, d_model), Linear(d_model, d_model), Linear(d_model, 4)])
 
 
-class DetectionHeads(nn.Module):
+class DetectionHeads(_NativeModule):
     """The statements between the detector's transformer and the region proposals
     (upt_tip_cache_model_free_finetune_distill3.py:1598-1605) in one native launch (hoigen_amd/csrc/hg_detr_heads.hip: hg_load_detr_heads,
-    hg_detr_heads): ``class_embed(hs)``, ``bbox_embed(hs).sigmoid()``, the V-COCO column selection ``[..., reserve_indices]`` and
+    hg_detr_heads; the host code is hg_detr_ends.hip): ``class_embed(hs)``, ``bbox_embed(hs).sigmoid()``, the V-COCO column selection ``[..., reserve_indices]`` and
     ``PostProcess`` (detr/models/detr.py:258-290).
 
         heads = DetectionHeads.from_modules(self.detector.class_embed, self.detector.bbox_embed, reserve_indices)
@@ -431,8 +383,6 @@ class DetectionHeads(nn.Module):
         self.class_embed = Linear(d_model, num_logits)
         self.bbox_embed = BoxMLP(d_model)
         self.reserve_indices = None if reserve_indices is None else [int(i) for i in reserve_indices]
-        self._ctx = _Ctx()
-        self._sig = None
 
     @property
     def n_out(self) -> int:
@@ -466,20 +416,18 @@ class DetectionHeads(nn.Module):
         m.train(class_embed.training)
         return m
 
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, _sig(self.parameters()), tuple(self.reserve_indices or ()))
-        if sig != self._sig:
-            t = lambda p: _lib.tensor(p.detach().contiguous())
-            ls = self.bbox_embed.layers
-            rows = self.reserve_indices
-            arr = (C.c_int32 * len(rows))(*rows) if rows is not None else None
-            w = _lib.hg_detr_heads_weights(t(self.class_embed.weight), t(self.class_embed.bias), t(ls[0].weight), t(ls[0].bias), t(ls[1].weight),
-                                           t(ls[1].bias), t(ls[2].weight), t(ls[2].bias), self.d_model, self.num_logits, arr,
-                                           len(rows) if rows is not None else 0)
-            self._ctx.check(_lib.lib().hg_load_detr_heads(h, C.byref(w)), "hg_load_detr_heads")
-            self._sig = sig
-        return h
+    def _sig_terms(self) -> tuple:
+        return (_sig(self.parameters()), tuple(self.reserve_indices or ()))
+
+    def _load_native(self, h: int) -> None:
+        t = lambda p: _lib.tensor(p.detach().contiguous())
+        ls = self.bbox_embed.layers
+        rows = self.reserve_indices
+        arr = (C.c_int32 * len(rows))(*rows) if rows is not None else None
+        w = _lib.hg_detr_heads_weights(t(self.class_embed.weight), t(self.class_embed.bias), t(ls[0].weight), t(ls[0].bias), t(ls[1].weight),
+                                       t(ls[1].bias), t(ls[2].weight), t(ls[2].bias), self.d_model, self.num_logits, arr,
+                                       len(rows) if rows is not None else 0)
+        self._ctx.check(_lib.lib().hg_load_detr_heads(h, C.byref(w)), "hg_load_detr_heads")
 
     def _run(self, hs, target_sizes, want_all: bool):
         _require_cuda(hs, "DetectionHeads hs")
@@ -537,7 +485,7 @@ class DetectionHeads(nn.Module):
         return results
 
 
-class DetectorNeck(nn.Module):
+class DetectorNeck(_NativeModule):
     """What stands between the detector's ResNet body and its transformer (upt_tip_cache_model_free_finetune_distill3.py:1594-1597) in
     one native call (hoigen_amd/csrc/hg_detr_neck.hip: hg_load_detr_neck, hg_detr_neck): the padding mask on the feature grid
     (detr/models/backbone.py:78), ``PositionEmbeddingSine`` (detr/models/position_encoding.py:28-48), ``input_proj``
@@ -559,8 +507,6 @@ class DetectorNeck(nn.Module):
         self.temperature, self.normalize = float(temperature), bool(normalize)
         self.scale = 2 * math.pi if scale is None else float(scale)
         self.input_proj = nn.Conv2d(self.in_channels, self.d_model, kernel_size=1)      # a parameter holder: never called
-        self._ctx = _Ctx()
-        self._sig = None
 
     @classmethod
     def from_modules(cls, input_proj: nn.Module, position_embedding: nn.Module) -> "DetectorNeck":
@@ -593,23 +539,14 @@ class DetectorNeck(nn.Module):
         m.train(input_proj.training)
         return m
 
-    def set_option(self, key: str, value: int) -> None:
-        """Behaviour option of this module's native context (include/hoigen_amd.h), e.g. ``detr_neck_split``."""
-        self._ctx.set_option(key, value)
+    def _sig_terms(self) -> tuple:
+        return (_sig(self.parameters()), self.num_pos_feats, self.temperature, self.normalize, self.scale)
 
-    def get_option(self, key: str):
-        return self._ctx.get_option(key)
-
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, _sig(self.parameters()), self.num_pos_feats, self.temperature, self.normalize, self.scale)
-        if sig != self._sig:
-            t = lambda p: _lib.tensor(p.detach().contiguous())
-            w = _lib.hg_detr_neck_weights(t(self.input_proj.weight), t(self.input_proj.bias), self.in_channels, self.d_model,
-                                          self.num_pos_feats, self.temperature, int(self.normalize), self.scale)
-            self._ctx.check(_lib.lib().hg_load_detr_neck(h, C.byref(w)), "hg_load_detr_neck")
-            self._sig = sig
-        return h
+    def _load_native(self, h: int) -> None:
+        t = lambda p: _lib.tensor(p.detach().contiguous())
+        w = _lib.hg_detr_neck_weights(t(self.input_proj.weight), t(self.input_proj.bias), self.in_channels, self.d_model,
+                                      self.num_pos_feats, self.temperature, int(self.normalize), self.scale)
+        self._ctx.check(_lib.lib().hg_load_detr_neck(h, C.byref(w)), "hg_load_detr_neck")
 
     def _run(self, features, image_mask, want_pos: bool = True, want_mask: bool = True, out=None):
         _require_cuda(features, "DetectorNeck features")

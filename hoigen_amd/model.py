@@ -150,6 +150,37 @@ def _sig(params) -> tuple:
     return tuple((p.data_ptr(), p._version, p.dtype) for p in params)
 
 
+class _NativeModule(nn.Module):
+    """A façade module whose weights live in one slot of a native context: ``_ctx`` (modules share a context by assigning it), ``_sig``
+    (what the slot was last loaded from), the context's options, and ``_load``.  A subclass gives ``_load_native(h)`` - build the
+    descriptor and call its ``hg_load_*`` on handle ``h`` - and, where a reload depends on more than its parameters, ``_sig_terms()``."""
+
+    def __init__(self):
+        super().__init__()
+        self._ctx = _Ctx()
+        self._sig = None
+
+    def set_option(self, key: str, value: int) -> None:
+        """Behaviour option of this module's native context (include/hoigen_amd.h: hg_set_option), e.g. ``detr_attn_chunk``, ``detr_ffn``,
+        ``detr_neck_split``."""
+        self._ctx.set_option(key, value)
+
+    def get_option(self, key: str):
+        return self._ctx.get_option(key)
+
+    def _sig_terms(self) -> tuple:
+        return (_sig(self.parameters()),)
+
+    def _load(self, device: torch.device) -> int:
+        """The context's handle on ``device``, with this module's weights loaded into it as they are now."""
+        h = self._ctx.get(device)
+        sig = (h,) + self._sig_terms()
+        if sig != self._sig:
+            self._load_native(h)
+            self._sig = sig
+        return h
+
+
 # ---------------------------------------------------------------------------------------------
 # parameter holders (names = the reference's attribute names)
 # ---------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .model import _Ctx, _inference_only, _require_cuda, _stream_ptr
+from .model import _inference_only, _NativeModule, _require_cuda, _stream_ptr
 
 LEVELS = ("layer1", "layer2", "layer3", "layer4")
 _CONVS = (("conv1", "bn1"), ("conv2", "bn2"), ("conv3", "bn3"))
@@ -135,7 +135,7 @@ def _read_norm(name: str, norm: nn.Module, channels: int, who: str = "ResNetStag
     return m
 
 
-class ResNetStages(nn.Module):
+class ResNetStages(_NativeModule):
     """``layer1`` .. ``layer4`` (or a range of them) of a bottleneck ResNet in one native call.  ``forward(x)`` takes the stem's
     ``[B, 64, H, W]`` map and returns the last level's map - ``[B, 2048, H / 8, W / 8]`` for ResNet-50's four levels (each stride-2 level
     gives ``(H - 1) // 2 + 1``) - as fp32 NCHW; ``forward_trace`` also returns every block's output.  Arithmetic: fp16 operands, fp32
@@ -146,9 +146,6 @@ class ResNetStages(nn.Module):
         super().__init__()
         self.level_names: List[str] = []
         self.level_ends: List[int] = []      # index of each level's last block
-        self._ctx = _Ctx()
-        self._sig = None
-        self._keep = None
 
     @classmethod
     def from_module(cls, body: nn.Module, levels: Tuple[int, int] = (1, 4)) -> "ResNetStages":
@@ -266,20 +263,12 @@ class ResNetStages(nn.Module):
             raise RuntimeError(f"hoigen_amd: hg_resnet_out_shape({first_block}, {last}, {H}, {W}) failed ({rc})")
         return c.value, h.value, ww.value
 
-    def set_option(self, key: str, value: int) -> None:
-        self._ctx.set_option(key, value)
+    def _sig_terms(self) -> tuple:
+        return (tuple((t.data_ptr(), t._version) for t in self.buffers()), tuple(b.bn1.eps for b in self.blocks()))
 
-    def get_option(self, key: str):
-        return self._ctx.get_option(key)
-
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, tuple((t.data_ptr(), t._version) for t in self.buffers()), tuple(b.bn1.eps for b in self.blocks()))
-        if sig != self._sig:
-            w, keep = self._descriptors(True)
-            self._ctx.check(_lib.lib().hg_load_resnet_stages(h, C.byref(w)), "hg_load_resnet_stages")
-            self._sig = sig
-        return h
+    def _load_native(self, h: int) -> None:
+        w, keep = self._descriptors(True)
+        self._ctx.check(_lib.lib().hg_load_resnet_stages(h, C.byref(w)), "hg_load_resnet_stages")
 
     def _run(self, x: torch.Tensor, first_block: int = 0, last_block: Optional[int] = None, out: Optional[torch.Tensor] = None,
              want_trace: bool = False):
@@ -354,7 +343,7 @@ def _images(x: torch.Tensor, what: str) -> torch.Tensor:
     return x
 
 
-class ResNetStem(nn.Module):
+class ResNetStem(_NativeModule):
     """``conv1`` (7 x 7 / 2, 3 -> 64), ``bn1``, ReLU and the 3 x 3 / 2 max-pool of a ResNet in one native launch
     (hoigen_amd/csrc/hg_resnet_stem.hip).  ``forward(images)`` takes ``[B, 3, Hi, Wi]`` and returns the stem's map, fp32
     ``[B, 64, Hp, Wp]``: what ``ResNetStages`` takes.  Arithmetic: image and weight rounded once to fp16, fp32 accumulation in a fixed
@@ -363,8 +352,6 @@ class ResNetStem(nn.Module):
     def __init__(self):
         super().__init__()
         self.pool = (3, 2, 1, 1, 0)      # kernel, stride, padding, dilation, ceil_mode
-        self._ctx = _Ctx()
-        self._sig = None
 
     @classmethod
     def from_module(cls, body: nn.Module) -> "ResNetStem":
@@ -427,20 +414,12 @@ class ResNetStem(nn.Module):
             raise RuntimeError(f"hoigen_amd: hg_resnet_stem_out_shape({Hi}, {Wi}) failed ({rc})")
         return 64, h.value, w.value
 
-    def set_option(self, key: str, value: int) -> None:
-        self._ctx.set_option(key, value)
+    def _sig_terms(self) -> tuple:
+        return (tuple((t.data_ptr(), t._version) for t in self.buffers()), self.bn1.eps)
 
-    def get_option(self, key: str):
-        return self._ctx.get_option(key)
-
-    def _load(self, device: torch.device) -> int:
-        h = self._ctx.get(device)
-        sig = (h, tuple((t.data_ptr(), t._version) for t in self.buffers()), self.bn1.eps)
-        if sig != self._sig:
-            w, keep = self._weights(True)
-            self._ctx.check(_lib.lib().hg_load_resnet_stem(h, C.byref(w)), "hg_load_resnet_stem")
-            self._sig = sig
-        return h
+    def _load_native(self, h: int) -> None:
+        w, keep = self._weights(True)
+        self._ctx.check(_lib.lib().hg_load_resnet_stem(h, C.byref(w)), "hg_load_resnet_stem")
 
     @_inference_only
     @torch.no_grad()
