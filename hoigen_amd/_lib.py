@@ -85,7 +85,8 @@ class hg_cache_weights(C.Structure):
 
 
 HG_HOI_MAX_BRANCH = 6
-HG_HOI_SRC = {"human": 0, "object": 1, "union": 2, "human_object": 3, "global": 4}
+HG_HOI_SRC = {"human": 0, "object": 1, "union": 2, "human_object": 3, "global": 4, "image": 5}
+HG_HOI_MAX_K_IMG = 4096
 
 
 class hg_hoi_branch(C.Structure):
@@ -100,6 +101,10 @@ class hg_hoi_head_args(C.Structure):
                 ("num_classes", C.c_int32), ("score_pow", C.c_float)] + \
                [(n, C.c_void_p) for n in ("pair_h", "pair_o", "objects", "union_boxes", "pooled_single", "pooled_union", "feats",
                                           "branch_logits", "logits", "prior", "scores_out")]
+
+
+class hg_hoi_image_args(C.Structure):
+    _fields_ = [("feat_image", C.c_void_p), ("K_img", C.c_int32), ("image_logits", C.c_void_p)]
 
 
 HG_MAX_PRIOR_SLOTS = 4
@@ -267,6 +272,11 @@ class hg_resnet_body_args(C.Structure):
                 ("last_block", C.c_int32), ("out", C.c_void_p), ("out_stride", C.c_int64 * 2), ("trace", C.POINTER(C.c_void_p))]
 
 
+class hg_resnet_features_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64 * 3), ("B", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("pooled", C.c_void_p), ("features", C.c_void_p), ("map_out", C.c_void_p), ("map_stride", C.c_int64 * 2)]
+
+
 class hg_test_resnet_stem_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x", "w", "scale", "bias", "out32", "out16")] + [(n, C.c_int32) for n in ("B", "Hi", "Wi")]
 
@@ -297,6 +307,9 @@ HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
 HG_PROF_RESNET_CONV = 107
 HG_PROF_RESNET_STEM = 108
+HG_PROF_RESNET_POOL = 109
+# threads of hg_resnet_pool.hip's workgroup: a thread's channels lie this far apart (hoigen_amd/csrc/hg_kernels.h)
+HG_RESNET_POOL_THREADS = 256
 # pooled pixels of a work item of hg_resnet_stem.hip (hoigen_amd/csrc/hg_kernels.h), and the largest image side of hg_resnet_stem
 HG_RESNET_STEM_TILE, HG_RESNET_STEM_MAX_SIDE = (4, 8), 4 * HG_RESNET_MAX_SIDE
 
@@ -329,6 +342,7 @@ SIGNATURES = {
     "hg_load_cache": (_I, [_P, _I, _P]),
     "hg_cache_logits": (_I, [_P, _I, _P, _I, _P, _P]),
     "hg_hoi_head": (_I, [_P, C.POINTER(hg_hoi_head_args), _P]),
+    "hg_hoi_head_image": (_I, [_P, C.POINTER(hg_hoi_head_args), C.POINTER(hg_hoi_image_args), _P]),
     "hg_load_priors": (_I, [_P, _I, C.POINTER(hg_prior_weights)]),
     "hg_region_priors": (_I, [_P, C.POINTER(hg_region_priors_args), _P]),
     "hg_hoi_detections": (_I, [_P, C.POINTER(hg_hoi_detections_args), _P]),
@@ -352,6 +366,7 @@ SIGNATURES = {
     "hg_resnet_stem_out_shape": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hg_resnet_stem": (_I, [_P, C.POINTER(hg_resnet_stem_args), _P]),
     "hg_resnet_body": (_I, [_P, C.POINTER(hg_resnet_body_args), _P]),
+    "hg_resnet_features": (_I, [_P, C.POINTER(hg_resnet_features_args), _P]),
     "hg_workspace_bytes": (_I, [_P, C.POINTER(C.c_uint64)]),
     "hg_set_option": (_I, [_P, C.c_char_p, _I]),
     "hg_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -371,6 +386,7 @@ SIGNATURES = {
     "hg_test_detr_rows": (_I, [_P, _I, C.POINTER(hg_test_detr_rows_args), _P]),
     "hg_test_resnet_conv": (_I, [_P, C.POINTER(hg_test_resnet_conv_args), _P]),
     "hg_test_resnet_stem": (_I, [_P, C.POINTER(hg_test_resnet_stem_args), _P]),
+    "hg_test_resnet_pool": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "hg_profile_begin": (_I, [_P, _I, _I]),
     "hg_profile_end": (_I, [_P, _P, _I, C.POINTER(C.c_int32)]),
 }

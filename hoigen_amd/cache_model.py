@@ -110,6 +110,26 @@ def build_clip_cache_model(features: torch.Tensor, verbs, num_classes: int, num_
     ``torch.manual_seed(s)`` set by the caller the result equals the reference's for the same inputs.  Pure index /
     copy work on the host side of the device tensors; no kernels involved.
     """
+    return _build_cache_model(features, verbs, num_classes, num_shot)
+
+
+@torch.no_grad()
+def build_dino_cache_model(features: torch.Tensor, verbs, num_classes: int, num_shot: int):
+    """The part of ``utils.build_dino_cache_model`` (the reference's utils.py:113-148) that follows the network.
+
+    ``features [n, D]``: the RAW pooled rows ``dino_model(images)`` returns for the n training images in loader order
+    (``ResNetFeatures.forward``; the reference does not normalise them before this point, :111) - only the selected keys are normalised,
+    at the end (:147).  ``verbs`` as for ``build_clip_cache_model``.  Returns ``(keys [D, S], values [S, num_classes])``.
+
+    From here on it is the same arithmetic as ``build_clip_cache_model`` and the same draws from torch's global generator in the same
+    order, so the two share one body.  The one difference in the reference's text: a class without samples draws ``torch.randn(2048)``
+    (:137, resnet50's width) where the CLIP builder draws the features' own width - the same draw for ``D == 2048``, and for any other
+    ``D`` the reference's ``torch.stack`` cannot run, so this draws ``D`` values.
+    """
+    return _build_cache_model(features, verbs, num_classes, num_shot)
+
+
+def _build_cache_model(features: torch.Tensor, verbs, num_classes: int, num_shot: int):
     n, D = features.shape
     dev = features.device
     cache_keys = [[] for _ in range(num_classes)]

@@ -75,9 +75,15 @@ int hg_cache_logits(hg_ctx* c, int slot, const float* feats, int R, float* out, 
 }
 
 // ---- interaction head (hg_hoi_head.hip) --------------------------------------------------------------------------------------------
-int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
+int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) { return hg_hoi_head_image(c, a, nullptr, stream); }
+
+// ... with the rows of its per-image branches (HG_HOI_SRC_IMAGE); im == nullptr: none
+int hg_hoi_head_image(hg_ctx* c, const hg_hoi_head_args* a, const hg_hoi_image_args* im, void* stream) {
     if (!c) return HG_ERR_INVALID;
     if (!a) return fail(c, HG_ERR_INVALID, "hg_hoi_head: no arguments");
+    const float* feat_image = im ? im->feat_image : nullptr;
+    const int K_img = im ? im->K_img : 0;
+    float* image_logits = im ? im->image_logits : nullptr;
     if (a->B < 0 || a->B > HOI_MAX_IMAGES) return fail(c, HG_ERR_INVALID, "hg_hoi_head: %d images (at most %d a call)", a->B, HOI_MAX_IMAGES);
     if (a->B == 0) return HG_OK;
     if (!a->box_off || !a->n_human) return fail(c, HG_ERR_INVALID, "hg_hoi_head: box_off / n_human missing");
@@ -105,20 +111,26 @@ int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
     const int C = a->C, NC = a->num_classes, nb = a->n_branch, Pt = hb.Pt;
     if (!a->feat_local || !a->boxes) return fail(c, HG_ERR_INVALID, "hg_hoi_head: feat_local / boxes missing");
     bool global = false;
+    int n_img = 0;
     if (nb > 0) {
         if (C % 64) return fail(c, HG_ERR_INVALID, "hg_hoi_head: C = %d is not a multiple of 64 (the branch GEMMs' K)", C);
         if (NC <= 0 || !a->logits) return fail(c, HG_ERR_INVALID, "hg_hoi_head: num_classes / logits missing");
         for (int i = 0; i < nb; ++i) {
             const hg_hoi_branch& br = a->branch[i];
-            if (br.source < HG_HOI_SRC_HUMAN || br.source > HG_HOI_SRC_GLOBAL)
+            if (br.source < HG_HOI_SRC_HUMAN || br.source > HG_HOI_SRC_IMAGE)
                 return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d has source %d", i, br.source);
+            const bool image = br.source == HG_HOI_SRC_IMAGE;
+            if (image && !feat_image) return fail(c, HG_ERR_INVALID, "hg_hoi_head: an image branch without feat_image");
+            if (image && (K_img <= 0 || K_img % 64 || K_img > HOI_MAX_K_IMG))
+                return fail(c, HG_ERR_INVALID, "hg_hoi_head: K_img = %d (a multiple of 64 from 64 to %d)", K_img, HOI_MAX_K_IMG);
             if (br.slot < 0 || br.slot >= HG_MAX_CACHE_SLOTS || !c->cache[br.slot].loaded)
                 return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d: cache slot %d not loaded", i, br.slot);
             const Cache& m = c->cache[br.slot];
-            const int K = br.source == HG_HOI_SRC_HUMAN_OBJECT ? 2 * C : C, Nout = m.has_labels ? m.C : m.S;
+            const int K = image ? K_img : br.source == HG_HOI_SRC_HUMAN_OBJECT ? 2 * C : C, Nout = m.has_labels ? m.C : m.S;
             if (m.K != K || Nout != NC)
                 return fail(c, HG_ERR_INVALID, "hg_hoi_head: branch %d: slot %d maps %d -> %d, the branch needs %d -> %d", i, br.slot, m.K, Nout, K, NC);
             if (br.source == HG_HOI_SRC_GLOBAL) global = true;
+            n_img += image;
         }
         if (global && !a->feat_global) return fail(c, HG_ERR_INVALID, "hg_hoi_head: a global branch without feat_global");
     }
@@ -134,6 +146,8 @@ int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
     if (!rc && !(a->pooled_single && (a->pooled_union || !Pt))) rc = ensure(c, c->hoi_pool, (size_t)(hb.N + Pt) * C * 4);
     if (!rc && nb > 0 && Pt > 0) rc = ensure(c, c->hoi_a16, Rp * C * 2 * (global ? 4 : 3));
     if (!rc && nb > 0 && Pt > 0 && !a->branch_logits) rc = ensure(c, c->hoi_br, (size_t)nb * Pt * NC * 4);
+    if (!rc && n_img > 0 && Pt > 0) rc = ensure(c, c->hoi_img16, (size_t)256 * K_img * 2);
+    if (!rc && n_img > 0 && Pt > 0 && !image_logits) rc = ensure(c, c->hoi_img, (size_t)n_img * a->B * NC * 4);
     if (rc) return rc;
     float* tab = (float*)c->hoi_tab.p;
     float* ps = a->pooled_single ? a->pooled_single : (float*)c->hoi_pool.p;
@@ -148,9 +162,27 @@ int hg_hoi_head(hg_ctx* c, const hg_hoi_head_args* a, void* stream) {
     HoiEpilogue e{};
     e.n = nb;
     float* br_out = a->branch_logits ? a->branch_logits : (float*)c->hoi_br.p;
-    for (int i = 0; i < nb; ++i) {
+    // The image branches' operand: the B rows of feat_image as fp16 in a 256-row buffer of their own (HOI_MAX_IMAGES <= 256: one tile
+    // of rows), the rows behind them zeroed on every call - the GEMMs read whole 256-row tiles of A.  One row per IMAGE, not per pair.
+    half_t* img16 = n_img > 0 ? (half_t*)c->hoi_img16.p : nullptr;
+    float* img_out = n_img > 0 ? (image_logits ? image_logits : (float*)c->hoi_img.p) : nullptr;
+    if (n_img > 0) {
+        HG_HIP(launch_f32_to_f16(feat_image, img16, (size_t)a->B * K_img, s));
+        HG_HIP(hipMemsetAsync(img16 + (size_t)a->B * K_img, 0, (size_t)(256 - a->B) * K_img * 2, s));
+    }
+    for (int i = 0, i_img = 0; i < nb; ++i) {
         const hg_hoi_branch& br = a->branch[i];
         Cache& m = c->cache[br.slot];
+        if (br.source == HG_HOI_SRC_IMAGE) {
+            float* rows = img_out + (size_t)i_img++ * a->B * NC;
+            rc = cache_logits_rows(c, m, img16, K_img, a->B, rows, s);
+            if (rc) return rc;
+            e.branch[i] = rows;
+            e.scale[i] = br.scale;
+            e.per_image[i] = 1;
+            e.slab[i] = a->branch_logits ? br_out + (size_t)i * Pt * NC : nullptr;
+            continue;
+        }
         const half_t* A = br.source == HG_HOI_SRC_UNION ? u16 : br.source == HG_HOI_SRC_GLOBAL ? g16 : ho16 + (br.source == HG_HOI_SRC_OBJECT ? C : 0);
         const int lda = br.source == HG_HOI_SRC_UNION || br.source == HG_HOI_SRC_GLOBAL ? C : 2 * C;
         float* out = br_out + (size_t)i * Pt * NC;

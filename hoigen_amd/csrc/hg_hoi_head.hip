@@ -9,7 +9,7 @@
 //                          staged in LDS, over the RoI's support only
 //   3. hoi_feats_kernel    human | object | union (| global) rows L2-normalised: the fp16 A operands of the branch GEMMs and,
 //                          optionally, the fp32 rows
-//   4. hoi_epilogue_kernel logits = sum_b scale_b branch_b (left to right), priors, sigmoid, scores
+//   4. hoi_epilogue_kernel logits = sum_b scale_b branch_b (left to right; a per-image branch read at the pair's image), priors, sigmoid, scores
 //
 // RoI table, HOI_TAB = 72 words per RoI:  0..31 wy   32..63 wx   64 gy (float; NaN = refused)  65 ylo  66 yhi   67 gx  68 xlo  69 xhi
 //
@@ -201,7 +201,8 @@ __global__ __launch_bounds__(256) void hoi_feats_kernel(HoiBatch hb, const float
 }
 
 // One workgroup per pair.  logits = branch_0 * scale_0 + branch_1 * scale_1 + .., every product rounded, summed left to right
-// (upt...:1195-1196); prior[0] = scores[x]^p and prior[1] = scores[y]^p on the columns obj2target[labels[y]] sets (:806-833; p == 1
+// (upt...:1195-1196, and :1205-1207 with the DINO row); a per-image branch (HG_HOI_SRC_IMAGE) holds one row per image and is read at row
+// b(p) instead of row p - the reference's dino_logits[i] broadcast over the image's pairs (:1184-1207); prior[0] = scores[x]^p and prior[1] = scores[y]^p on the columns obj2target[labels[y]] sets (:806-833; p == 1
 // leaves the score as it is, as torch's pow does; any other p goes through double); score = sigmoid(logits) * (prior[0] * prior[1]) (:1417-1423).
 __global__ __launch_bounds__(128) void hoi_epilogue_kernel(HoiBatch hb, HoiEpilogue e, const float* __restrict__ scores,
                                                            const int32_t* __restrict__ labels, const uint8_t* __restrict__ obj2target,
@@ -233,7 +234,9 @@ __global__ __launch_bounds__(128) void hoi_epilogue_kernel(HoiBatch hb, HoiEpilo
         const size_t at = (size_t)p * NC + k;
         float acc = 0.f;
         for (int i = 0; i < e.n; ++i) {
-            const float t = e.branch[i][at] * e.scale[i];
+            const float v = e.per_image[i] ? e.branch[i][(size_t)b * NC + k] : e.branch[i][at];
+            if (e.per_image[i] && e.slab[i]) e.slab[i][at] = v;
+            const float t = v * e.scale[i];
             acc = i == 0 ? t : acc + t;
         }
         if (logits) logits[at] = acc;

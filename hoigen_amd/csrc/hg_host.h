@@ -219,6 +219,7 @@ struct hg_ctx {
     Buf xlo;             // low half of the residual stream while it is held as centre + hi + lo (GemmArgs::hl)
     Buf pair_ready;      // hg_mlp_pair.hip: ready counters [blocks][256-row panels], zeroed at the start of every tower pass
     Buf hoi_tab, hoi_pool, hoi_a16, hoi_br;      // hg_hoi_head: RoI table; pooled means; fp16 operand rows HO | U | G; branch logits
+    Buf hoi_img16, hoi_img;                      // hg_hoi_head's image branches: the 256-row fp16 operand of feat_image; their [n, B, NC] logits
     Buf props;           // hg_region_priors: keep, boxes, scores, labels of the selected instances where the caller does not ask for them
     Buf det;             // hg_hoi_detections: row counts, workgroup sums, and the entry arrays the association reads where the caller does not ask for them
     Buf prebatch;        // hg_preprocess_batch: per-crop headers and weight tables, sized from n and n_px alone
@@ -300,7 +301,7 @@ namespace hg_host {
     {&(c)->x, &(c)->h, &(c)->qkv, &(c)->att, &(c)->fc, &(c)->head16, &(c)->tok32, &(c)->small, &(c)->i32, &(c)->ad32, &(c)->ad16,    \
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
-     &(c)->hoi_br, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws, &(c)->resnet_ws, \
+     &(c)->hoi_br, &(c)->hoi_img16, &(c)->hoi_img, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws, &(c)->resnet_ws, \
      &(c)->resnet_stem_ws}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {

@@ -267,6 +267,15 @@ hipError_t launch_resnet_entry(const float* x, long long sb, long long sc, long 
 // x fp32 NHWC [B, S, C] -> out fp32 [B, C, S] through element strides (image, channel), token stride 1
 hipError_t launch_resnet_exit(const float* x, int B, int C, int S, float* out, long long sb, long long sc, hipStream_t s);
 
+// ---- global average pool + L2 normalisation behind the last block (hg_resnet_pool.hip): x fp32 NHWC [B, HW, C] -> pooled [B, C] = the
+// mean over the HW positions (one fp32 accumulator per (image, channel), positions added in ascending order, one division by (float)HW)
+// and features [B, C] = pooled / ||pooled||_2 (sum of squares, sqrtf, reciprocal, one multiply); either output nullable, not both.
+// One workgroup of RESNET_POOL_THREADS threads per image, a thread's channels RESNET_POOL_THREADS apart.  C % 64 == 0, C <= RESNET_MAX_C,
+// 1 <= HW <= RESNET_MAX_SIDE^2, B <= RESNET_MAX_B; outside resnet_pool_ok: hipErrorInvalidValue and nothing launched.
+static constexpr int RESNET_POOL_THREADS = 256;
+bool resnet_pool_ok(const float* x, int B, int HW, int C, const float* pooled, const float* features);
+hipError_t launch_resnet_pool(const float* x, int B, int HW, int C, float* pooled, float* features, hipStream_t s);
+
 // ---- ResNet stem (hg_resnet_stem.hip): maxpool3x3/2,pad1(relu(fmaf(conv7x7/2,pad3(x, w), scale, bias))) in one launch, 3 -> 64 channels.
 // x fp32 [B, 3, Hi, Wi] through element strides sb, sc, sr (image, channel, row), column stride 1, 4-byte aligned; w fp16 in fragment
 // order (launch_resnet_stem_pack from torch's fp32 [64, 3, 7, 7]); scale, bias fp32 [64]; out32 fp32 / out16 fp16 NHWC [B, Hp, Wp, 64],
@@ -475,6 +484,7 @@ static constexpr int HOI_MAX_SIDE = 32;         // H, W of the local map at most
 static constexpr int HOI_MAX_C = 1024;
 static constexpr int HOI_MAX_P = 32;          // bins per side: P * P stays an int far below 2^24, a set-up thread walks at most P * HOI_MAX_GRID samples
 static constexpr int HOI_MAX_BRANCH = 6;
+static constexpr int HOI_MAX_K_IMG = 4096;      // width of feat_image at most (HG_HOI_SRC_IMAGE)
 static constexpr int HOI_MAX_GRID = 65536;      // samples per bin and axis beyond which a RoI is refused (its pooled row is NaN)
 static constexpr int HOI_TAB = 72;              // words per RoI of the table hoi_setup_kernel writes (layout: hg_hoi_head.hip)
 static constexpr size_t HOI_LDS_MAX = 160 * 1024;
@@ -484,8 +494,10 @@ struct HoiBatch {      // host-built, by value: boxes of image b are rows box_of
 };
 struct HoiEpilogue {
     int n;
-    const float* branch[HOI_MAX_BRANCH];      // [Pt, NC] each
+    const float* branch[HOI_MAX_BRANCH];      // [Pt, NC] each; a per-image branch: [B, NC], pair p reads the row of its image b(p)
     float scale[HOI_MAX_BRANCH];
+    unsigned char per_image[HOI_MAX_BRANCH];  // 1: HG_HOI_SRC_IMAGE, computed once per image (hg_heads.hip)
+    float* slab[HOI_MAX_BRANCH];              // nullable, per-image branches only: [Pt, NC] that receives the rows as the pairs read them
 };
 int hoi_pool_chunk(int H, int W);             // channels per LDS chunk: 64 while 64 x (H W | 1) floats fit HOI_LDS_MAX (24 x 24 does), else 32
 hipError_t launch_hoi_setup(const HoiBatch& hb, const float* boxes, const int32_t* labels, float scale, int P, int H, int W,

@@ -1,7 +1,8 @@
 // The bottleneck stages of a ResNet on the HIP path (torchvision's Bottleneck under the reference's FrozenBatchNorm2d,
 // detr/models/backbone.py:19-55, :83-93): the weight loader, the output-shape rule and the block runner; and the stem in front of them
-// (conv1, bn1, ReLU, max-pool): its loader, shape rule, hg_resnet_stem and hg_resnet_body.  Host code only; the kernels are in
-// hg_resnet_conv.hip and hg_resnet_stem.hip.
+// (conv1, bn1, ReLU, max-pool): its loader, shape rule, hg_resnet_stem and hg_resnet_body; and hg_resnet_features, the whole network
+// with the global average pool and the L2 normalisation behind the last block (the DINO backbone).  Host code only; the kernels are in
+// hg_resnet_conv.hip, hg_resnet_stem.hip and hg_resnet_pool.hip.
 #include "hg_host.h"
 
 namespace {
@@ -136,9 +137,10 @@ int resnet_workspace(hg_ctx* c, int B_, Hw in, int first, int last, ResnetWs& w)
 }
 
 // blocks first .. last on the NHWC pair in w.x32[0] / w.x16[0] (B x in.H x in.W x cin of `first`): every block is torchvision's
-// Bottleneck.forward.  The one block loop of hg_resnet_stages and hg_resnet_body (`who` names the caller in a message).
+// Bottleneck.forward.  The one block loop of hg_resnet_stages, hg_resnet_body and hg_resnet_features (`who` names the caller in a
+// message).  `out` nullable: no exit launch.  `last_nhwc` / `last_hw` nullable: the fp32 NHWC stream behind block `last` and its size.
 int resnet_run_blocks(hg_ctx* c, const char* who, int B, Hw cur, int first, int last, const ResnetWs& w, float* out, const int64_t* out_stride,
-                      float* const* trace, hipStream_t s) {
+                      float* const* trace, hipStream_t s, const float** last_nhwc = nullptr, Hw* last_hw = nullptr) {
     const ResnetStages& r = c->resnet;
     auto conv = [&](const ResnetConvW& cw, const half_t* x, Hw in, Hw o, int epi, const float* identity, float* o32, half_t* o16) -> int {
         ResnetConvArgs k{};
@@ -171,7 +173,9 @@ int resnet_run_blocks(hg_ctx* c, const char* who, int B, Hw cur, int first, int 
         float* tr = trace ? trace[i - first] : nullptr;
         if (tr) HG_HIP(launch_resnet_exit(w.x32[p], B, b.c3.cout, cur.H * cur.W, tr, (long long)b.c3.cout * cur.H * cur.W, (long long)cur.H * cur.W, s));
     }
-    HG_HIP(launch_resnet_exit(w.x32[p], B, r.blocks[last].c3.cout, cur.H * cur.W, out, out_stride[0], out_stride[1], s));
+    if (out) HG_HIP(launch_resnet_exit(w.x32[p], B, r.blocks[last].c3.cout, cur.H * cur.W, out, out_stride[0], out_stride[1], s));
+    if (last_nhwc) *last_nhwc = w.x32[p];
+    if (last_hw) *last_hw = cur;
     return HG_OK;
 }
 
@@ -386,6 +390,38 @@ int hg_resnet_body(hg_ctx* c, const hg_resnet_body_args* a, void* stream) {
     if ((rc = resnet_workspace(c, a->B, p, 0, last, w))) return rc;
     if ((rc = launch_stem(c, "hg_resnet_body", a->x, a->x_stride, a->B, a->Hi, a->Wi, w.x32[0], w.x16[0], s))) return rc;
     return resnet_run_blocks(c, "hg_resnet_body", a->B, p, 0, last, w, a->out, a->out_stride, a->trace, s);
+}
+
+// The DINO backbone of upt_tip_cache_model_free_finetune_distill3.py:1617-1618 from the images: the stem, every loaded block, then the
+// pool + normalise kernel on the NHWC stream the last block left in the workspace (hg_resnet_pool.hip)
+int hg_resnet_features(hg_ctx* c, const hg_resnet_features_args* a, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    const ResnetStages& r = c->resnet;
+    if (!c->resnet_stem.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_resnet_features: no stem loaded (hg_load_resnet_stem)");
+    if (!r.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_resnet_features: no stages loaded (hg_load_resnet_stages)");
+    if (!a || !a->x) return fail(c, HG_ERR_INVALID, "hg_resnet_features: x is required");
+    if (!a->pooled && !a->features && !a->map_out) return fail(c, HG_ERR_INVALID, "hg_resnet_features: one of pooled, features and map_out is required");
+    if (c->resnet_stem.conv.cout != r.blocks[0].c1.cin)
+        return fail(c, HG_ERR_INVALID, "hg_resnet_features: the stem gives %d channels, blocks[0] takes %d", c->resnet_stem.conv.cout, r.blocks[0].c1.cin);
+    Hw p;
+    int rc = check_stem_shape(c, "hg_resnet_features", a->B, a->Hi, a->Wi, p);
+    if (rc) return rc;
+    const int last = (int)r.blocks.size() - 1;
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    ResnetWs w;
+    if ((rc = resnet_workspace(c, a->B, p, 0, last, w))) return rc;
+    if ((rc = launch_stem(c, "hg_resnet_features", a->x, a->x_stride, a->B, a->Hi, a->Wi, w.x32[0], w.x16[0], s))) return rc;
+    const float* nhwc = nullptr;
+    Hw o{};
+    if ((rc = resnet_run_blocks(c, "hg_resnet_features", a->B, p, 0, last, w, a->map_out, a->map_stride, nullptr, s, &nhwc, &o))) return rc;
+    if (!a->pooled && !a->features) return HG_OK;
+    const int C = r.blocks[last].c3.cout;
+    ProfScope ps(c, s, HG_PROF_RESNET_POOL, a->B, C, o.H * o.W);
+    hipError_t he = launch_resnet_pool(nhwc, a->B, o.H * o.W, C, a->pooled, a->features, s);
+    ps.finish();
+    if (he != hipSuccess) return fail(c, HG_ERR_HIP, "hg_resnet_features: pool launch failed: %s", hipGetErrorString(he));
+    return HG_OK;
 }
 
 }  // extern "C"

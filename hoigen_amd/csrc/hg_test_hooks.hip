@@ -636,4 +636,24 @@ int hg_test_resnet_stem(hg_ctx* c, const hg_test_resnet_stem_args* x, void* stre
     return HG_OK;
 }
 
+// ONE launch of the pool + normalise kernel (hg_resnet_pool.hip) on the caller's NHWC map (include/hoigen_amd.h;
+// tests/test_gpu_resnet_features.py)
+int hg_test_resnet_pool(hg_ctx* c, const float* x_nhwc, int B, int HW, int C, float* pooled, float* features, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!resnet_pool_ok(x_nhwc, B, HW, C, pooled, features))
+        return fail(c, HG_ERR_INVALID, "hg_test_resnet_pool: x and one of pooled / features are required; B 1 .. %d, C a multiple of 64 up to %d, HW 1 .. %d^2",
+                    RESNET_MAX_B, RESNET_MAX_C, RESNET_MAX_SIDE);
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    hipError_t e;
+    {
+        ProfScope ps(c, s, HG_PROF_RESNET_POOL, B, C, HW);
+        e = launch_resnet_pool(x_nhwc, B, HW, C, pooled, features, s);
+    }
+    hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_resnet_pool: %s", hipGetErrorString(e));
+    return HG_OK;
+}
+
 }  // extern "C"

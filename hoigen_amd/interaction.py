@@ -2,16 +2,24 @@
 
 Counterpart of ``UPT.compute_roi_embeddings`` + ``compute_prior_scores`` + ``postprocessing``
 (upt_tip_cache_model_free_finetune_distill3.py:959-1268, :806-833, :1408-1427) in eval mode with ``individual_norm = True``,
-``logits_type = 'HO+U+T'``, no DINO branch, no ``use_weight_pred``, generated features not appended (the ``eval_ar`` / ``cache`` path):
+``logits_type = 'HO+U+T'``, no ``use_weight_pred``, generated features not appended (the ``eval_ar`` / ``cache`` path):
 
     head = HOIHead([("human", cache_H, s_H), ("object", cache_O, s_O), ("union", cache_U, s_U), ("union", text, s_T)],
                    object_class_to_target_class, human_idx, num_classes)
     logits, prior, bh, bo, objects = head(feat_global, feat_local, image_sizes, region_props)
     detections = head.postprocess(boxes, bh, bo, logits, prior, objects, image_sizes)
 
+The DINO branch (:1111-1115, :1184-1207; on by default in the reference, main_tip_finetune.py:393) is a sixth branch of source ``"image"``:
+one row of cache-model logits per IMAGE, computed once and added to every pair of the image in its place of the list, so
+``[H, O, U, text, global, image]`` is the sum of :1205-1207 term for term:
+
+    dino = CacheLogits(dino_cache.T, dino_cache_bias, dino_cache_values, dino_sample_len)
+    head = HOIHead([..., ("global", cache_G, s_G), ("image", dino, dino_cache_logit)], ...)
+    out = head(feat_global, feat_local, image_sizes, region_props, feat_image=dino_model.normalized(images))      # ResNetFeatures
+
 ``region_props`` may be the list ``hoigen_amd.proposals.DetectorFrontEnd`` returned (NMS / ``prepare_region_proposals``, ``get_prior`` /
 ``priors_downproj`` in one call of their own): its dicts carry the human counts, and no label leaves the device here.  Out of scope,
-plain torch in the caller as before: the training-time appended features and losses.  Inference only; CPU tensors and gradient callers raise ``RuntimeError`` (there is no
+plain torch in the caller as before: the training-time appended features (``gen_to_dino``, :1122-1127, among them) and losses.  Inference only; CPU tensors and gradient callers raise ``RuntimeError`` (there is no
 CPU fallback).
 """
 from typing import List, Optional, Sequence, Tuple
@@ -94,7 +102,8 @@ class HOIHead:
 
     ``branches``: at most 6 entries ``(source, CacheLogits, scale)`` with ``source`` one of ``"human"``, ``"object"``, ``"union"``,
     ``"human_object"`` (the ``[P, 2C]`` concatenation, :1166) and ``"global"`` (``feat_global[b]`` normalised, repeated over the
-    image's pairs, :1132-1138); the logits are ``sum_b scale_b * branch_b`` in list order (:1195-1196).  ``hyper_lambda`` is the power
+    image's pairs, :1132-1138) and ``"image"`` (a ``CacheLogits`` of any ``K % 64 == 0`` up to 4096 on the rows of ``feat_image [B, K]``
+    as they are - the caller normalises - computed once per image and read by each of its pairs, :1111-1115, :1184-1207); the logits are ``sum_b scale_b * branch_b`` in list order (:1195-1196).  ``hyper_lambda`` is the power
     of the detection scores in the priors (:814; pass 1.0 for the training-time value)."""
 
     def __init__(self, branches, obj2target, human_idx: int, num_classes: int, hyper_lambda: float = 2.8, pool: int = 7):
@@ -118,8 +127,15 @@ class HOIHead:
             raise RuntimeError("hoigen_amd: HOIHead runs only on a HIP device (there is no CPU fallback)")
 
     def __call__(self, feat_global: Optional[torch.Tensor], feat_local: torch.Tensor, image_sizes: torch.Tensor,
-                 region_props: List[dict]) -> Tuple[list, list, list, list, list]:
-        self._check([feat_global, feat_local] + [p[k] for p in region_props for k in ("boxes", "scores")])
+                 region_props: List[dict], feat_image: Optional[torch.Tensor] = None) -> Tuple[list, list, list, list, list]:
+        """``feat_image [B, K]``: the rows of the ``"image"`` branches (``ResNetFeatures.normalized``); needed by such a branch,
+        ignored without one."""
+        has_image = any(src == "image" for src, _, _ in self.branches)
+        if has_image and feat_image is None:
+            raise RuntimeError("hoigen_amd: HOIHead has an \"image\" branch: pass feat_image [B, K] (ResNetFeatures.normalized(images))")
+        if not has_image:
+            feat_image = None
+        self._check([feat_global, feat_local, feat_image] + [p[k] for p in region_props for k in ("boxes", "scores")])
         if not region_props:
             return [], [], [], [], []
         if feat_local.dim() != 4 or feat_local.shape[0] != len(region_props):
@@ -145,6 +161,11 @@ class HOIHead:
             self.obj2target = self.obj2target.to(dev)
         fl = feat_local.detach().float().contiguous()
         fg = feat_global.detach().float().contiguous() if feat_global is not None else None
+        fi = None
+        if feat_image is not None:
+            if feat_image.dim() != 2 or feat_image.shape[0] != B:
+                raise ValueError(f"feat_image must be [{B}, K] (got {tuple(feat_image.shape)})")
+            fi = feat_image.detach().float().contiguous()
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         pair_h, pair_o, objects = torch.empty(Pt, **i32), torch.empty(Pt, **i32), torch.empty(Pt, **i32)
@@ -166,7 +187,11 @@ class HOIHead:
         a.pair_h, a.pair_o, a.objects = pair_h.data_ptr(), pair_o.data_ptr(), objects.data_ptr()
         a.logits, a.prior, a.scores_out = logits.data_ptr(), prior.data_ptr(), dense.data_ptr()
         with torch.cuda.device(idx):
-            rc = _lib.lib().hg_hoi_head(_lib.ctx(idx), _lib.C.byref(a), torch.cuda.current_stream().cuda_stream)
+            if fi is None:
+                rc = _lib.lib().hg_hoi_head(_lib.ctx(idx), _lib.C.byref(a), torch.cuda.current_stream().cuda_stream)
+            else:
+                im = _lib.hg_hoi_image_args(fi.data_ptr(), int(fi.shape[1]), None)
+                rc = _lib.lib().hg_hoi_head_image(_lib.ctx(idx), _lib.C.byref(a), _lib.C.byref(im), torch.cuda.current_stream().cuda_stream)
         _lib.check(idx, rc, "hg_hoi_head")
         out = split_outputs(pair_off, logits, prior, pair_h, pair_o, objects, label_dtype)
         for b, lg in enumerate(out[0]):      # the dense scores travel with the logits they belong to: postprocess keeps no state

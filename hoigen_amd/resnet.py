@@ -8,7 +8,9 @@ as the DINO backbone on the 224-pixel crops (upt_tip_cache_model_free_finetune_d
 
 The stem (``conv1`` 7 x 7, ``bn1``, ReLU, max-pool) stays torch by default; ``ResNetStem.from_module(body)`` is its one native launch
 (hoigen_amd/csrc/hg_resnet_stem.hip) and ``NativeBody.from_module(body, native_stem=True)`` runs stem and stages as one call
-(hg_resnet_body).  torchvision is not imported: the source module is read by its attribute
+(hg_resnet_body).  ``ResNetFeatures.from_module(net)`` is the whole network as the reference's DINO backbone runs it - stem, stages,
+global average pool, ``fc = Identity`` - with the L2 normalisation of :1618 behind it, in one call (hg_resnet_features; the pool and the
+norm are one launch, hoigen_amd/csrc/hg_resnet_pool.hip).  torchvision is not imported: the source module is read by its attribute
 names.  Inference only; tensors must live on a HIP device.
 """
 from __future__ import annotations
@@ -509,3 +511,96 @@ class NativeBody(nn.Module):
         if self.native_stem is not None:
             return {"0": self._run_body(images)[0]}
         return {"0": self.stages._run(self.stem(images))[0]}
+
+
+class ResNetFeatures(nn.Module):
+    """A torchvision-style bottleneck ResNet with ``fc = nn.Identity()`` - the reference's ``dino_model`` (main_tip_finetune.py:404-408,
+    upt_tip_cache_model_free_finetune_distill3.py:1616-1618) - in one native call (hg_resnet_features): the stem, ``layer1`` ..
+    ``layer4``, then ONE launch that pools the last block's NHWC stream where it lies and L2-normalises the rows.
+
+        self.dino_model = ResNetFeatures.from_module(dino_model)      # forward(images) -> [B, 2048], as before
+        dino_feat = self.dino_model.normalized(images)                # :1617-1618 in one call
+
+    ``pooled``: per (image, channel) one fp32 accumulator over the positions in ascending order and one division; ``features``: sum of
+    squares, ``sqrtf``, one reciprocal, one multiply (a zero row is NaN, as ``0 / 0`` is).  Stem and stages share one native context of
+    this object's own, so a detector's ResNet and this one coexist."""
+
+    def __init__(self, stem: ResNetStem, stages: ResNetStages):
+        super().__init__()
+        self.stem = stem
+        self.stages = stages
+        stem._ctx = stages._ctx
+
+    @classmethod
+    def from_module(cls, net: nn.Module) -> "ResNetFeatures":
+        """``net``: attributes ``conv1, bn1, relu, maxpool, layer1 .. layer4`` as ``ResNetStem`` / ``ResNetStages`` read them; ``avgpool``
+        an adaptive average pool to 1 x 1 (or absent); ``fc`` an ``nn.Identity`` (or absent).  Anything else is refused here, without a
+        device."""
+        head = "hoigen_amd: ResNetFeatures.from_module: "
+        fc = getattr(net, "fc", None)
+        if fc is not None and not isinstance(fc, nn.Identity):
+            what = f"a Linear {fc.in_features} -> {fc.out_features}" if isinstance(fc, nn.Linear) else type(fc).__name__
+            raise RuntimeError(head + f"fc is {what}; only nn.Identity (or no fc) is implemented: the reference replaces it "
+                               "(main_tip_finetune.py:406), and a classifier behind the pool is the caller's")
+        pool = getattr(net, "avgpool", None)
+        if pool is not None:
+            size = getattr(pool, "output_size", None)
+            if not isinstance(pool, nn.AdaptiveAvgPool2d) or size not in (1, (1, 1), [1, 1]):
+                raise RuntimeError(head + f"avgpool is {pool!r}; only nn.AdaptiveAvgPool2d to 1 x 1 (or no avgpool) is implemented")
+        stages = ResNetStages.from_module(net)
+        stem = ResNetStem.from_module(net)
+        if len(stages.level_names) != 4:
+            raise RuntimeError(head + "layer1 .. layer4 are needed")
+        m = cls(stem, stages)
+        m.train(getattr(net, "training", False))
+        return m
+
+    @property
+    def num_channels(self) -> int:
+        return self.stages.blocks()[-1].conv3.desc.cout
+
+    def _run(self, images: torch.Tensor, want_pooled: bool, want_features: bool, want_map: bool):
+        st, sg = self.stem, self.stages
+        x = _images(images, "ResNetFeatures images")
+        B, _, Hi, Wi = (int(v) for v in x.shape)
+        if sg._ctx is not st._ctx:
+            raise RuntimeError("hoigen_amd: ResNetFeatures: the stem and the stages must share one native context")
+        h = sg._load(x.device)
+        st._load(x.device)
+        _, Hp, Wp = st.out_shape(Hi, Wi)
+        Co, Ho, Wo = sg.out_shape(Hp, Wp)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        pooled = torch.empty(B, Co, **f32) if want_pooled else None
+        features = torch.empty(B, Co, **f32) if want_features else None
+        fmap = torch.empty(B, Co, Ho, Wo, **f32) if want_map else None
+        a = _lib.hg_resnet_features_args()
+        a.x, a.B, a.Hi, a.Wi = x.data_ptr(), B, Hi, Wi
+        a.x_stride[:] = [x.stride(0), x.stride(1), x.stride(2)]
+        a.pooled = pooled.data_ptr() if want_pooled else None
+        a.features = features.data_ptr() if want_features else None
+        if want_map:
+            a.map_out = fmap.data_ptr()
+            a.map_stride[:] = [fmap.stride(0), fmap.stride(1)]
+        st._ctx.check(_lib.lib().hg_resnet_features(h, C.byref(a), _stream_ptr(x.device)), "hg_resnet_features")
+        return pooled, features, fmap
+
+    @_inference_only
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        """``images [B, 3, Hi, Wi]`` -> ``pooled [B, C]``: what ``dino_model(images)`` returns (:1617)."""
+        return self._run(images, True, False, False)[0]
+
+    @_inference_only
+    @torch.no_grad()
+    def normalized(self, images: torch.Tensor) -> torch.Tensor:
+        """``pooled / pooled.norm(dim=-1, keepdim=True)`` (:1617-1618): what ``HOIHead`` takes as ``feat_image``."""
+        return self._run(images, False, True, False)[1]
+
+    @_inference_only
+    @torch.no_grad()
+    def forward_all(self, images: torch.Tensor, pooled: bool = True, features: bool = True, map: bool = True):
+        """``(pooled [B, C], features [B, C], map [B, C, Ho, Wo])`` of one call; an output switched off comes back as ``None`` (at least
+        one must be on).  ``map`` is ``NativeBody(native_stem=True)``'s, bit for bit."""
+        if not (pooled or features or map):
+            raise RuntimeError("hoigen_amd: ResNetFeatures.forward_all: at least one of pooled, features and map")
+        return self._run(images, bool(pooled), bool(features), bool(map))

@@ -221,7 +221,7 @@ int hg_load_cache(hg_ctx*, int slot, const hg_cache_weights* w);
 int hg_cache_logits(hg_ctx*, int slot, const float* feats, int R, float* out, void* stream);
 
 /* The interaction head for a batch of images in one call: UPT.compute_roi_embeddings in eval mode with individual_norm = True,
- * logits_type = 'HO+U+T', no DINO branch, no use_weight_pred, generated features not appended
+ * logits_type = 'HO+U+T', the DINO branch as a per-image source (below), no use_weight_pred, generated features not appended
  * (upt_tip_cache_model_free_finetune_distill3.py:959-1268), compute_prior_scores (:806-833) and the score of postprocessing
  * (:1408-1427).  Image b has the boxes box_off[b] .. box_off[b + 1] - 1, HUMANS FIRST (the caller applies the permutation of
  * :988-996), n_human[b] of them humans.  Its pairs are all (x, y) with x < n_human[b], y != x, row-major (:1007-1012):
@@ -242,6 +242,13 @@ int hg_cache_logits(hg_ctx*, int slot, const float* feats, int R, float* out, vo
  * A zero-area box pools to 0 and its normalised row is NaN, as in the reference; so are the rows of every pair that contains it.
  * feat_local fp32 [B, C, H, W] (hg_encode_image_prior's out_local), feat_global fp32 [B, C] (nullable without a global branch),
  * boxes [N, 4] (x1, y1, x2, y2, image pixels), scores [N], labels int32 [N]: device.  box_off [B + 1], n_human [B]: HOST.
+ * The DINO branch (:1111-1115, :1184-1207) is a branch of source HG_HOI_SRC_IMAGE, through hg_hoi_head_image (below): branch i = hg_cache_logits(branch[i].slot) on the B
+ * rows of feat_image [B, K_img] TAKEN AS THEY ARE (the caller normalises: hg_resnet_features' `features`), converted to fp16 once and
+ * computed ONCE PER IMAGE - for all B images whenever Pt > 0 - on a zero-padded 256-row operand of its own whose padding rows are
+ * rewritten on every call; pair p reads row b(p).  The sum stays scale_0 * branch_0 + scale_1 * branch_1 + .. in list order, so
+ * [H, O, U, text, global, image] is :1205-1207 term for term.  image_logits (nullable) receives [n image branches, B, num_classes] in
+ * list order; in branch_logits an image branch's [Pt, num_classes] slab holds the broadcast rows.  HG_ERR_INVALID for an image source
+ * without feat_image, K_img <= 0, K_img % 64 != 0 or K_img > 4096, a slot whose K != K_img or whose width is not num_classes.
  * Limits: B <= 64, H, W <= 32, C <= 1024, P <= 32, n_branch <= 6; with branches C % 64 == 0, every slot loaded (hg_load_cache) with K = C
  * (2C for human|object) and output width num_classes.  n_branch == 0 pools only (any C; logits may be NULL, prior may be asked for, scores_out may not: HG_ERR_INVALID).  Every output but
  * logits may be NULL.  Asynchronous on `stream`. */
@@ -251,6 +258,7 @@ int hg_cache_logits(hg_ctx*, int slot, const float* feats, int R, float* out, vo
 #define HG_HOI_SRC_UNION 2
 #define HG_HOI_SRC_HUMAN_OBJECT 3
 #define HG_HOI_SRC_GLOBAL 4
+#define HG_HOI_SRC_IMAGE 5 /* a row per IMAGE from feat_image, computed once per image and added to every pair of it (the DINO branch) */
 typedef struct {
     int32_t source, slot;
     float scale;
@@ -270,6 +278,16 @@ typedef struct {
     float *union_boxes, *pooled_single, *pooled_union, *feats, *branch_logits, *logits, *prior, *scores_out;
 } hg_hoi_head_args;
 int hg_hoi_head(hg_ctx*, const hg_hoi_head_args* args, void* stream);
+/* hg_hoi_head_image: hg_hoi_head with the rows of the HG_HOI_SRC_IMAGE branches.  hg_hoi_head_args keeps its layout, so the three
+ * values travel in a struct of their own; `image` NULL is hg_hoi_head itself (which is this call with NULL: the same launches as before the source existed - the
+ * epilogue kernel's by-value argument struct grew by the per-branch flags - and an image branch in its list is refused for want of
+ * feat_image). */
+typedef struct {
+    const float* feat_image;               /* fp32 [B, K_img], device */
+    int32_t K_img;
+    float* image_logits;                   /* nullable: [n image branches, B, num_classes] */
+} hg_hoi_image_args;
+int hg_hoi_head_image(hg_ctx*, const hg_hoi_head_args* args, const hg_hoi_image_args* image, void* stream);
 
 /* Region proposals and instance priors for a batch of images in one call: what UPT.forward does between DETR's PostProcess and the
  * encoders (upt_tip_cache_model_free_finetune_distill3.py:1543-1660).
@@ -782,6 +800,28 @@ typedef struct {
     float* const* trace;
 } hg_resnet_body_args;
 int hg_resnet_body(hg_ctx*, const hg_resnet_body_args* args, void* stream);
+/* hg_resnet_features: the network as the reference's DINO backbone runs it (torchvision's resnet50 with fc = Identity on the 224 x 224
+ * view, upt_tip_cache_model_free_finetune_distill3.py:1617-1618): the stem, EVERY loaded block, then one launch that pools and
+ * normalises the last block's fp32 NHWC stream where it lies in the workspace (hoigen_amd/csrc/hg_resnet_pool.hip) - no NCHW map is
+ * written unless map_out asks for it.  x as hg_resnet_body's.  Outputs, each nullable, at least one required:
+ *   pooled    fp32 [B, C] contiguous: avgpool + flatten.  Per (image, channel) one fp32 accumulator, the Ho Wo positions added in
+ *             ascending order, then one IEEE division by (float)(Ho Wo).
+ *   features  fp32 [B, C] contiguous: pooled / pooled.norm(dim=-1, keepdim=True) - the sum of squares in a fixed order, sqrtf, one
+ *             reciprocal, one multiply per element.  An all-zero row is NaN, as the reference's 0 / 0 is.
+ *   map_out   fp32 [B, C, Ho, Wo] through map_stride = (image, channel) in elements, token stride 1: hg_resnet_body's out, bit for bit.
+ * A non-finite image makes its own rows non-finite and no other image's.  Workspace: hg_resnet_body's.  Asynchronous on `stream`.
+ * HG_ERR_NOT_LOADED if either slot is empty; HG_ERR_INVALID with a message and nothing launched for what hg_resnet_body refuses and
+ * for a call without an output. */
+typedef struct {
+    const float* x;
+    int64_t x_stride[3];                   /* elements: image, channel, row */
+    int32_t B, Hi, Wi;
+    float* pooled;
+    float* features;
+    float* map_out;
+    int64_t map_stride[2];                 /* elements: image, channel */
+} hg_resnet_features_args;
+int hg_resnet_features(hg_ctx*, const hg_resnet_features_args* args, void* stream);
 /* vae_loss forward value (main_coop_vae.py:300-303) -> loss[1] fp32. */
 int hg_vae_loss(hg_ctx*, const float* recon, const float* x, const float* mean, const float* logvar,
                 int R, int D, float* loss, void* stream);
@@ -901,6 +941,7 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_DETR_NECK 106 /* hg_detr_neck's launch(es): M = rows (B * H * W), N = slices of cin, K = cin */
 #define HG_PROF_RESNET_CONV 107 /* one convolution launch of hg_resnet_stages / hg_test_resnet_conv: M = output pixels (B * Ho * Wo), N = cout, K = k * k * cin */
 #define HG_PROF_RESNET_STEM 108 /* the stem launch of hg_resnet_stem / hg_resnet_body / hg_test_resnet_stem: M = pooled pixels (B * Hp * Wp), N = 64, K = 147 */
+#define HG_PROF_RESNET_POOL 109 /* the pool + normalise launch of hg_resnet_features / hg_test_resnet_pool: M = images, N = channels, K = positions (Ho * Wo) */
 #define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
@@ -1158,6 +1199,11 @@ typedef struct {
     int32_t B, Hi, Wi;
 } hg_test_resnet_stem_args;
 int hg_test_resnet_stem(hg_ctx*, const hg_test_resnet_stem_args* args, void* stream);
+
+/* Test hook for the pool + normalise kernel (hoigen_amd/csrc/hg_resnet_pool.hip): ONE launch on the caller's fp32 NHWC map x_nhwc
+ * [B, HW, C], read where it lies.  pooled, features fp32 [B, C], either nullable, not both.  C a multiple of 64 up to 2048, HW from 1
+ * to 1024^2, B from 1 to 64.  Synchronous.  HG_ERR_INVALID where the launcher refuses, and nothing launched. */
+int hg_test_resnet_pool(hg_ctx*, const float* x_nhwc, int B, int HW, int C, float* pooled, float* features, void* stream);
 
 #ifdef __cplusplus
 }
