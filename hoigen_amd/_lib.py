@@ -303,11 +303,15 @@ class hg_test_detr_rows_args(C.Structure):
     _fields_ = [("p", C.c_void_p * 12), ("s", C.c_int64 * 4), ("i", C.c_int32 * 4)]
 
 
+# the text tower's backward (hoigen_amd/csrc/hg_kernels.h): tokens per prompt at most; prompts per chunk of grad_ctx's first stage
+HG_TEXT_GRAD_MAX_L, HG_PROMPTS_BWD_CHUNK = 80, 64
+
 HG_PROF_OFF, HG_PROF_ALL, HG_PROF_ATTENTION, HG_PROF_QKV_ATTN = -1, -2, 100, 101
 HG_PROF_DETR_FFN, HG_PROF_DETR_ROWS, HG_PROF_DETR_NECK = 104, 105, 106
 HG_PROF_RESNET_CONV = 107
 HG_PROF_RESNET_STEM = 108
 HG_PROF_RESNET_POOL = 109
+HG_PROF_TEXT_ATTN_BWD, HG_PROF_TEXT_GRAD_ROWS = 110, 111      # hg_text_backward_embeds: the attention backward; its row and elementwise launches
 # threads of hg_resnet_pool.hip's workgroup: a thread's channels lie this far apart (hoigen_amd/csrc/hg_kernels.h)
 HG_RESNET_POOL_THREADS = 256
 # pooled pixels of a work item of hg_resnet_stem.hip (hoigen_amd/csrc/hg_kernels.h), and the largest image side of hg_resnet_stem
@@ -331,11 +335,14 @@ SIGNATURES = {
     "hg_encode_image_trace": (_I, [_P, _P, _I, _P, _P, _P]),
     "hg_encode_text_ids": (_I, [_P, _P, _I, _I, _P, _I, _P]),
     "hg_encode_text_embeds": (_I, [_P, _P, _P, _I, _I, _P, _I, _P]),
+    "hg_encode_text_embeds_save": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P]),
+    "hg_text_backward_embeds": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "hg_token_embedding": (_I, [_P, _P, _I, _P, _P]),
     "hg_vae_forward": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "hg_generator": (_I, [_P, _I, _P, _I, _P, _P]),
     "hg_mlp_net": (_I, [_P, _I, _P, _I, _P, _P]),
     "hg_assemble_prompts": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "hg_assemble_prompts_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "hg_l2_normalize": (_I, [_P, _P, _I, _I, _P, _P]),
     "hg_vae_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "hg_roi_align": (_I, [_P, _P, _I, _I, _I, _P, _I, C.c_float, _I, _P, _P, _P]),
@@ -383,6 +390,7 @@ SIGNATURES = {
     "hg_test_text_stream": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "hg_test_adapter": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "hg_test_elem": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
+    "hg_test_text_grad": (_I, [_P, _I, C.POINTER(hg_test_elem_args), _P]),
     "hg_test_detr_rows": (_I, [_P, _I, C.POINTER(hg_test_detr_rows_args), _P]),
     "hg_test_resnet_conv": (_I, [_P, C.POINTER(hg_test_resnet_conv_args), _P]),
     "hg_test_resnet_stem": (_I, [_P, C.POINTER(hg_test_resnet_stem_args), _P]),

@@ -5,7 +5,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wall -Wno-unused-function -ffp-contract=fast ${HG_EXTRA_FLAGS}"   # HG_EXTRA_FLAGS=-DHG_STAMPS: diagnostic build with s_memtime stamps
 OBJS=""
-for f in hg_gemm hg_gemm_ring hg_gemm_ring2 hg_mlp_pair hg_mlp_pair256 hg_mlp_pair256p hg_gemm_duo hg_attn hg_attn_long hg_detr_attn hg_detr_rows hg_detr hg_detr_ffn hg_detr_dec hg_detr_ends hg_detr_heads hg_detr_neck hg_resnet_conv hg_resnet_stem hg_resnet_pool hg_resnet hg_qkv_attn hg_qkv_attn_text hg_vae_fused hg_elem hg_adapter hg_adapter_long hg_preproc hg_preproc_batch hg_detector_views hg_hoi_head hg_region_props hg_detections hg_api hg_load hg_tower hg_heads hg_test_hooks; do
+for f in hg_gemm hg_gemm_ring hg_gemm_ring2 hg_mlp_pair hg_mlp_pair256 hg_mlp_pair256p hg_gemm_duo hg_attn hg_attn_long hg_detr_attn hg_detr_rows hg_detr hg_detr_ffn hg_detr_dec hg_detr_ends hg_detr_heads hg_detr_neck hg_resnet_conv hg_resnet_stem hg_resnet_pool hg_resnet hg_qkv_attn hg_qkv_attn_text hg_text_grad hg_vae_fused hg_elem hg_adapter hg_adapter_long hg_preproc hg_preproc_batch hg_detector_views hg_hoi_head hg_region_props hg_detections hg_api hg_load hg_tower hg_text_bwd hg_heads hg_test_hooks; do
   # an object is rebuilt when its source, any header or include file here, or the C header is newer
   if [ ! -f $f.o ] || [ -n "$(find $f.hip *.h *.inc ../../include/hoigen_amd.h -newer $f.o)" ]; then
     rm -f $f.o

@@ -106,6 +106,7 @@ void hg_destroy(hg_ctx* c) {
     free_all(c->vit.owned);
     free_all(c->vit.owned_adapters);
     free_all(c->text.owned);
+    free_all(c->text.owned_grad);
     for (auto& v : c->vae) free_all(v.owned);
     for (auto& m : c->mlp) free_all(m.owned);
     for (auto& m : c->cache) free_all(m.owned);
@@ -289,6 +290,19 @@ int hg_assemble_prompts(hg_ctx* c, const float* prefix, const float* suffix, con
         return fail(c, HG_ERR_INVALID, "bad arguments to assemble_prompts");
     HG_ON_DEVICE(c);
     HG_HIP(launch_assemble_prompts(prefix, suffix, ctx, bias, target, R, C, L, n_ctx, D, prompts, (hipStream_t)stream));
+    return HG_OK;
+}
+
+int hg_assemble_prompts_backward(hg_ctx* c, const float* grad_prompts, int R, int L, int n_ctx, int D, float* grad_ctx, float* grad_bias,
+                                 void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (R == 0) return HG_OK;
+    if (!grad_prompts || (!grad_ctx && !grad_bias) || R < 0 || n_ctx < 1 || n_ctx >= L || D < 1)
+        return fail(c, HG_ERR_INVALID, "bad arguments to assemble_prompts_backward");
+    HG_ON_DEVICE(c);
+    const size_t n_part = ((size_t)R + PROMPTS_BWD_CHUNK - 1) / PROMPTS_BWD_CHUNK;
+    if (int rc = ensure(c, c->pgrad, n_part * n_ctx * D * 4)) return rc;
+    HG_HIP(launch_prompts_bwd(grad_prompts, R, L, n_ctx, D, (float*)c->pgrad.p, grad_ctx, grad_bias, (hipStream_t)stream));
     return HG_OK;
 }
 

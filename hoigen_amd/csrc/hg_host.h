@@ -102,6 +102,13 @@ struct Text {
     half_t* w_projT = nullptr;
     std::vector<BlockW> blocks;
     std::vector<void*> owned;
+    // the input gradient of the tower (hg_text_bwd.hip): the linears once more, transposed, so that dX = dY W runs on the GEMM kernels
+    // as they are - built by ensure_text_grad on the first backward call, dropped with the weights by hg_load_text
+    struct GradW { half_t *wT_qkv, *wT_out, *wT_fc, *wT_proj; };      // [D, 3D], [D, D], [D, 4D], [4D, D]
+    std::vector<GradW> grad;
+    half_t* g_proj = nullptr;      // text_projection as the state dict holds it: [D, E]
+    float* g_zero = nullptr;       // [4D] zeros: the backward GEMMs' bias
+    std::vector<void*> owned_grad;
 };
 
 struct Vae {
@@ -227,6 +234,8 @@ struct hg_ctx {
     Buf detr_dec_ws;     // hg_detr_decoder: memory's fp16 copies and every layer's cross-attention K and V, the decoder stream and its fp16 operands, the split FFN's partial sums
     Buf detr_neck_ws;    // hg_detr_neck: the fp32 partial sums of a split over Cin
     Buf resnet_ws;       // hg_resnet_stages / hg_resnet_body: the fp32 stream in and out, its fp16 copies, the downsample's output, conv1's and conv2's outputs
+    Buf tgrad;           // hg_text_backward_embeds: the fp32 gradient stream, its fp16 copy, and the fp16 / fp32 gradients of a block's activations
+    Buf pgrad;           // hg_assemble_prompts_backward: the per-chunk partial sums of grad_ctx
     Buf resnet_stem_ws;  // hg_resnet_stem: the NHWC fp32 + fp16 pair the kernel writes, ahead of the NCHW copy the caller gets
     Buf dviews;          // hg_detector_views: the CLIP leg's boxes, the weight tables, and the resized images where the caller does not ask for them
     int max_chunk_img = 256;
@@ -302,7 +311,7 @@ namespace hg_host {
      &(c)->adkv, &(c)->mr, &(c)->mu, &(c)->muc, &(c)->stats, &(c)->pre, &(c)->pretab, &(c)->cx, &(c)->ca, &(c)->ch, &(c)->cf,        \
      &(c)->cq, &(c)->xlo, &(c)->zpark, &(c)->att2, &(c)->hg, &(c)->pair_ready, &(c)->hoi_tab, &(c)->hoi_pool, &(c)->hoi_a16,    \
      &(c)->hoi_br, &(c)->hoi_img16, &(c)->hoi_img, &(c)->props, &(c)->det, &(c)->prebatch, &(c)->dviews, &(c)->detr_ws, &(c)->detr_dec_ws, &(c)->detr_neck_ws, &(c)->resnet_ws, \
-     &(c)->resnet_stem_ws}
+     &(c)->resnet_stem_ws, &(c)->tgrad, &(c)->pgrad}
 
 inline int fail(hg_ctx* c, int code, const char* fmt, ...) {
     char tmp[512];
@@ -461,4 +470,10 @@ inline GemmArgs gemm_args(const half_t* A, int lda, const half_t* W, const float
 
 // hg_load.hip: the text tower's in_proj operands in the fused kernel's fragment order, packed on the first call that needs them
 int ensure_text_packs(hg_ctx* c, std::vector<void*>& owned, std::vector<BlockW>& blocks, int D, bool gamma);
+// hg_text_bwd.hip: the transposed weights of the text tower's input gradient, built on first use
+int ensure_text_grad(hg_ctx* c);
+// ... one block of that backward: g [M, D] fp32 (in place: the gradient of the block's output -> of its input) from the block's saved
+// input x_in [M, D]; the block is recomputed into the tower workspace, the gradients live in c->tgrad (text_grad_ws)
+int text_grad_ws(hg_ctx* c, int M, int R);
+int text_block_backward(hg_ctx* c, int block, const float* x_in, float* g, int n_seq, int L, hipStream_t s);
 }  // namespace hg_host

@@ -571,6 +571,28 @@ hipError_t launch_det_assoc(const DetBatch& db, const float* boxes, const float*
                             float min_iou, int cap, int Gt, const int32_t* det_off, const DetEntries& e, float* det_label, int32_t* det_gt,
                             float* det_max_iou, float* gt_out, int32_t* status, hipStream_t s);
 
+// ---- backward of the frozen text tower (hg_text_grad.hip): the gradient with respect to the prompts, no weight gradients ----------------
+// causal attention backward, head dim 64, 1 <= L <= TEXT_GRAD_MAX_L: qkv fp16 [n_seq * L, 3 * heads * 64] (q | k | v column blocks), dout
+// fp16 [n_seq * L, heads * 64] -> dqkv fp16 [n_seq * L, 3 * heads * 64] (dq | dk | dv); exactly those rows are written
+static constexpr int TEXT_GRAD_MAX_L = 80;
+size_t text_attn_bwd_lds(int L);      // dynamic LDS bytes of a workgroup
+hipError_t launch_text_attn_bwd(const half_t* qkv, const half_t* dout, half_t* dqkv, int n_seq, int L, int heads, hipStream_t s);
+// g[row] += LayerNorm_backward(x[r], gamma, dy[r]) for r < M (x, dy dense [M, D] fp32; eps 1e-5, statistics recomputed from x);
+// row = r, or r * rows_per_seq + sel[r] (clamped) with sel.  D % 4 == 0, D <= 1024
+hipError_t launch_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* g, int M, int D, const int32_t* sel,
+                                int rows_per_seq, hipStream_t s);
+// du = fp16(df * quickgelu'(u)), n % 8 == 0, 16-byte aligned; du may be df
+hipError_t launch_qgelu_bwd(const half_t* df, const half_t* u, half_t* du, size_t n, hipStream_t s);
+// go16 [R, E] = fp16(s_r * go), sinv[r] = 1 / s_r with s_r = 2^-floor(log2(max_e |go[r][e]|)) (1 for a zero row)
+hipError_t launch_grad_scale(const float* go, half_t* go16, float* sinv, int R, int E, hipStream_t s);
+// out [R, L, D] = g [R, Leff, D] * sinv[r], zeros at positions >= Leff
+hipError_t launch_grad_unscale(const float* g, const float* sinv, float* out, int R, int L, int Leff, int D, hipStream_t s);
+// g [R, L, D] -> grad_bias [R, D] = sum_j g[r][1 + j], grad_ctx [n_ctx, D] = sum_r g[r][1 + j] through partial
+// [ceil(R / PROMPTS_BWD_CHUNK)][n_ctx][D] (rows of a chunk ascending, then chunks ascending); either output nullable
+static constexpr int PROMPTS_BWD_CHUNK = 64;
+hipError_t launch_prompts_bwd(const float* g, int R, int L, int n_ctx, int D, float* partial, float* grad_ctx, float* grad_bias,
+                              hipStream_t s);
+
 // ---- adapter (variant C) --------------------------------------------------------------------
 // tokens per image at most: the decoder keeps K and V of NKMAX = 224 keys on chip (hg_adapter.hip); a longer tower loads without adapters only
 static constexpr int ADAPTER_MAX_L = 224;

@@ -447,6 +447,7 @@ int hg_load_text(hg_ctx* c, const hg_text_weights* w) {
     HG_ON_DEVICE(c);
     Text& t = c->text;
     free_all(t.owned);
+    free_all(t.owned_grad);
     t = Text{};
     const int D = w->width;
     if (D <= 0 || D % 128 || w->heads * 64 != D)

@@ -530,6 +530,41 @@ int hg_test_elem(hg_ctx* c, int op, const hg_test_elem_args* x, void* stream) {
     return HG_OK;
 }
 
+// One launcher of hg_text_grad.hip with the caller's own device buffers, or one block of the text tower's backward
+// (include/hoigen_amd.h has the table of operands; tests/test_gpu_text_grad_kernels.py).
+int hg_test_text_grad(hg_ctx* c, int op, const hg_test_elem_args* x, void* stream) {
+    if (!c) return HG_ERR_INVALID;
+    if (!x) return fail(c, HG_ERR_INVALID, "hg_test_text_grad: args are required");
+    hipStream_t s = (hipStream_t)stream;
+    HG_ON_DEVICE(c);
+    void* const* p = x->p;
+    const int32_t* i = x->i;
+    auto F = [&](int k) { return (float*)p[k]; };
+    auto H = [&](int k) { return (half_t*)p[k]; };
+    hipError_t e;
+    switch (op) {
+        case 0: e = launch_text_attn_bwd(H(0), H(1), H(2), i[0], i[1], i[2], s); break;
+        case 1: e = launch_layernorm_bwd(F(0), F(1), F(2), F(3), i[0], i[1], (const int32_t*)p[4], i[2], s); break;
+        case 2: e = launch_qgelu_bwd(H(0), H(1), H(2), (size_t)x->n, s); break;
+        case 3: e = launch_grad_scale(F(0), H(1), F(2), i[0], i[1], s); break;
+        case 4: e = launch_grad_unscale(F(0), F(1), F(2), i[0], i[1], i[2], i[3], s); break;
+        case 5: e = launch_prompts_bwd(F(0), i[0], i[1], i[2], i[3], F(1), F(2), F(3), s); break;
+        case 6: {
+            if (!c->text.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_text has not been called");
+            if (i[0] < 0 || i[0] >= (int)c->text.blocks.size() || i[1] < 1 || i[2] < 1 || i[2] > TEXT_GRAD_MAX_L || !p[0] || !p[1] ||
+                (long long)i[1] * i[2] > c->text_rows_budget)
+                return fail(c, HG_ERR_INVALID, "hg_test_text_grad: block, n_seq >= 1, 1 <= L <= %d, x_in and g are needed", TEXT_GRAD_MAX_L);
+            if (int rc = ensure_text_grad(c)) return rc;
+            if (int rc = text_grad_ws(c, i[1] * i[2], 0)) return rc;
+            return text_block_backward(c, i[0], F(0), F(1), i[1], i[2], s);
+        }
+        default: return fail(c, HG_ERR_INVALID, "hg_test_text_grad: op must be 0 .. 6");
+    }
+    if (e == hipErrorInvalidValue) return fail(c, HG_ERR_INVALID, "hg_test_text_grad: op %d refused by its launcher: %s", op, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, HG_ERR_HIP, "hg_test_text_grad: op %d failed: %s", op, hipGetErrorString(e));
+    return HG_OK;
+}
+
 // One launcher of hg_detr_rows.hip with the caller's own device buffers (include/hoigen_amd.h has the table of operands;
 // tests/test_gpu_detr_rows.py, tests/test_gpu_detr_wiring.py).
 int hg_test_detr_rows(hg_ctx* c, int op, const hg_test_detr_rows_args* x, void* stream) {

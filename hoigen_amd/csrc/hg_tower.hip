@@ -61,6 +61,7 @@ struct TowerCall {
     int n_seq = 0, L = 0, D = 0, heads = 0;
     bool causal = false; hipStream_t s = nullptr;
     float* trace = nullptr; int trace_stride = 0; bool trace_all = false;
+    bool trace_entries_only = false;      // no entry behind the last block: the trace holds the stream as it ENTERS every block (hg_encode_text_embeds_save)
     const AdapterCall* ac = nullptr;
     bool ln_fold = false;        // LayerNorm folded into the GEMMs where the shapes allow (ln_fuse_ok)
     bool gamma_act = false;      // ... with the LayerNorm weight in the ACTIVATION copy (text tower, text_ln_fold = 1)
@@ -533,11 +534,12 @@ int run_blocks(hg_ctx* c, const std::vector<BlockW>& blocks, const TowerCall& t)
         int rc = HG_OK;
         if (b.adapter) rc = run_adapter(c, *b.adapter, t.n_seq, t.L, D, *t.ac, s, p.fuse, b.fold != nullptr, p.hilo_c ? p.att_o + D : nullptr, true);
         if (!rc) rc = launch_in_proj_attention(c, t, p, blocks[i], b);
-        if (!rc && b.row0) return launch_row0_block(c, t, p, blocks[i], t.trace ? t.trace + (i + 1) * (size_t)t.trace_stride : nullptr);
+        const bool tr = t.trace && !(t.trace_entries_only && i + 1 == blocks.size());
+        if (!rc && b.row0) return launch_row0_block(c, t, p, blocks[i], tr ? t.trace + (i + 1) * (size_t)t.trace_stride : nullptr);
         if (!rc) rc = launch_out_proj(c, t, p, blocks[i], b);
         if (!rc) rc = launch_mlp(c, t, p, blocks, i);
         if (rc) return rc;
-        if (t.trace) HG_HIP(launch_trace_copy(t, p, (int)i + 1, b.x_hilo));
+        if (tr) HG_HIP(launch_trace_copy(t, p, (int)i + 1, b.x_hilo));
     }
     return HG_OK;
 }
@@ -661,7 +663,9 @@ int text_chunk_prompts(const hg_ctx* c, int n_prompts, int Leff) {
 }
 
 // `trace` (hg_test_text_stream): every row of the stream, [layers + 1][Tc * Leff][D]
-int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out, hipStream_t s, float* trace = nullptr) {
+// `saved` (hg_encode_text_embeds_save): the stream as it enters every block, [layers][Tc * Leff][D], and behind it the last block's output
+// on the EOT rows, [Tc][D] - what the backward recomputes the blocks from.  The same launches otherwise
+int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out, hipStream_t s, float* trace = nullptr, float* saved = nullptr) {
     Text& t = c->text;
     const int D = t.D, E = t.E;
     // option text_ln_fold: 1 (default) folds the LayerNorms with gamma riding in the ACTIVATION copy (6.2e-4 against the reference's
@@ -674,12 +678,15 @@ int text_tail(hg_ctx* c, int Tc, int Leff, const int32_t* eot, float* out, hipSt
     }
     TowerCall call;
     call.n_seq = Tc; call.L = Leff; call.D = D; call.heads = t.heads; call.causal = true; call.s = s;
-    call.trace = trace; call.trace_stride = Tc * Leff * D; call.trace_all = trace != nullptr;
+    call.trace = saved ? saved : trace; call.trace_stride = Tc * Leff * D; call.trace_all = call.trace != nullptr;
+    call.trace_entries_only = saved != nullptr;
     call.ln_fold = c->opt_text_ln_fold != 0; call.gamma_act = c->opt_text_ln_fold == 1;
     call.sel = eot; call.row0_out = &rows;
     int rc = run_blocks(c, t.blocks, call);
     if (rc) return rc;
     half_t* h16 = (half_t*)c->head16.p;
+    if (saved) HG_HIP(launch_copy_rows(rows ? rows : (const float*)c->x.p, saved + t.blocks.size() * (size_t)Tc * Leff * D, Tc, rows ? 1 : Leff, D, s,
+                                       rows ? nullptr : eot));
     // ln_final, select the EOT row, @ text_projection (clipnet/model.py:346-350); LN is row-wise so
     // selecting before normalising is identical
     if (rows) HG_HIP(launch_layernorm_f16(rows, t.lnf_w, t.lnf_b, h16, Tc, D, nullptr, 0, 1, s));
@@ -842,8 +849,8 @@ int hg_test_text_stream(hg_ctx* c, const int32_t* ids, int T, int L, int trunc, 
     return encode_text_ids_impl(c, ids, T, L, out, trunc, trace, stream);
 }
 
-int hg_encode_text_embeds(hg_ctx* c, const float* prompts, const int32_t* eot_idx, int R, int L, float* out,
-                          int trunc, void* stream) {
+static int encode_text_embeds_impl(hg_ctx* c, const float* prompts, const int32_t* eot_idx, int R, int L, float* out, int trunc,
+                                   float* saved, void* stream) {
     if (!c) return HG_ERR_INVALID;
     Text& t = c->text;
     if (!t.loaded) return fail(c, HG_ERR_NOT_LOADED, "hg_load_text has not been called");
@@ -856,6 +863,9 @@ int hg_encode_text_embeds(hg_ctx* c, const float* prompts, const int32_t* eot_id
     const int Leff = (trunc > 0 && trunc < L) ? trunc : L;
     if (Leff < L && c->eot_flag_dev) HG_HIP(hipMemsetAsync(c->eot_flag_dev, 0, 4, s));
     const int chunk = text_chunk_prompts(c, R, Leff);
+    if (saved && chunk < R)
+        return fail(c, HG_ERR_INVALID, "hg_encode_text_embeds_save: %d prompts of %d tokens are more than one pass of the text tower (a row budget of "
+                                       "%d rows: at most %d prompts of this length)", R, Leff, c->text_rows_budget, chunk);
     for (int r0 = 0; r0 < R; r0 += chunk) {
         const int Rc = (R - r0 < chunk) ? R - r0 : chunk;
         int rc = ensure_tower_ws(c, Rc * Leff, t.D);
@@ -869,11 +879,21 @@ int hg_encode_text_embeds(hg_ctx* c, const float* prompts, const int32_t* eot_id
             HG_HIP(launch_clamp_eot(eot, Rc, Leff, (int32_t*)c->i32.p, c->eot_flag, s, c->eot_flag_dev));
             eot = (const int32_t*)c->i32.p;
         }
-        rc = text_tail(c, Rc, Leff, eot, out + (size_t)r0 * t.E, s);
+        rc = text_tail(c, Rc, Leff, eot, out + (size_t)r0 * t.E, s, nullptr, saved);
         if (rc) return rc;
     }
     if (Leff < L) HG_HIP(launch_poison_if_flag(out, (size_t)R * t.E, c->eot_flag_dev, s));
     return HG_OK;
+}
+
+int hg_encode_text_embeds(hg_ctx* c, const float* prompts, const int32_t* eot_idx, int R, int L, float* out,
+                          int trunc, void* stream) {
+    return encode_text_embeds_impl(c, prompts, eot_idx, R, L, out, trunc, nullptr, stream);
+}
+int hg_encode_text_embeds_save(hg_ctx* c, const float* prompts, const int32_t* eot_idx, int R, int L, float* out, int trunc,
+                               float* saved, void* stream) {
+    if (c && !saved) return fail(c, HG_ERR_INVALID, "hg_encode_text_embeds_save: saved == NULL");
+    return encode_text_embeds_impl(c, prompts, eot_idx, R, L, out, trunc, saved, stream);
 }
 
 int hg_token_embedding(hg_ctx* c, const int32_t* ids, int n, float* out, void* stream) {

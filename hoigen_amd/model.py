@@ -48,13 +48,17 @@ def _tensors_in(obj):
             yield from _tensors_in(o)
 
 
-def _inference_only(fn):
+def _inference_only(fn=None, *, name=None):
     """The HIP path records no autograd graph.  The reference back-propagates through two of these entry points
     (VAE training through the frozen text tower, main_coop_vae.py:465-471; adapter / prompt fine-tuning,
     main_tip_finetune.py:955-1031).  A caller that asks for gradients - grad mode on and either an input that
     requires grad, or a module in ``train()`` mode that owns trainable parameters (where the reference would also apply
     the adapters' dropout, CLIP_models_adapter_prior2.py:51-72) - gets an error instead of silently frozen
     parameters.  ``eval()`` modules and ``torch.no_grad()`` callers (every inference call site of the reference) pass."""
+
+    if fn is None:      # @_inference_only(name="forward"): the method's name in the message
+        return functools.partial(_inference_only, name=name)
+    shown = name or fn.__name__
 
     @functools.wraps(fn)
     def wrapper(self, *args, **kwargs):
@@ -67,7 +71,7 @@ def _inference_only(fn):
                 what = "a module in train() mode with trainable parameters"
             if what is not None:
                 raise RuntimeError(
-                    f"hoigen_amd: {type(self).__name__}.{fn.__name__} was called with {what} while grad mode is on. "
+                    f"hoigen_amd: {type(self).__name__}.{shown} was called with {what} while grad mode is on. "
                     "The HIP path is inference-only: it records no autograd graph and applies no train-mode dropout, so "
                     "parameters would silently receive no gradients.  Call it under torch.no_grad() / in eval() mode, or "
                     "use the reference's PyTorch modules for training (INTEGRATION.md, 'Training entry points').")
@@ -700,6 +704,13 @@ class CLIP(nn.Module):
     @torch.no_grad()
     def encode_text_embeds(self, prompts: torch.Tensor, tokenized_prompts: torch.Tensor) -> torch.Tensor:
         """TextEncoder.forward(prompts, tokenized_prompts) (main_coop_vae.py:54-63) -> fp32 [R,E]."""
+        return self._encode_text_embeds(prompts, tokenized_prompts)[0]
+
+    @torch.no_grad()
+    def _encode_text_embeds(self, prompts: torch.Tensor, tokenized_prompts: torch.Tensor, save: bool = False):
+        """The one native text call on embedded prompts -> (out fp32 [R,E], saved, eot int32 [R], trunc).  ``save``: the call is
+        hg_encode_text_embeds_save and ``saved`` holds the stream entering every block and the last block's EOT rows (what
+        hg_text_backward_embeds recomputes the blocks from: vae.TextEncoder(differentiable=True)); else ``saved`` is None."""
         _require_cuda(prompts, "prompts")
         dev = prompts.device
         h = self._sync_text(dev)
@@ -711,11 +722,24 @@ class CLIP(nn.Module):
         eot32 = eot.to(device=dev, dtype=torch.int32).contiguous()
         pf = prompts.detach().to(torch.float32).contiguous()
         out = torch.empty(R, self.text_projection.shape[1], device=dev, dtype=torch.float32)
-        rc = _lib.lib().hg_encode_text_embeds(h, pf.data_ptr(), eot32.data_ptr(), R, L, out.data_ptr(), trunc, _stream_ptr(dev))
+        saved = None
+        with torch.cuda.device(dev):
+            if save:
+                leff = trunc if 0 < trunc < L else L
+                if leff > _lib.HG_TEXT_GRAD_MAX_L:
+                    raise RuntimeError(f"hoigen_amd: the differentiable text tower serves at most {_lib.HG_TEXT_GRAD_MAX_L} tokens per "
+                                       f"prompt (got {leff})")
+                saved = torch.empty(self.transformer.layers * R * leff + R, D, device=dev, dtype=torch.float32)
+                what = "hg_encode_text_embeds_save"
+                rc = _lib.lib().hg_encode_text_embeds_save(h, pf.data_ptr(), eot32.data_ptr(), R, L, out.data_ptr(), trunc,
+                                                           saved.data_ptr(), _stream_ptr(dev))
+            else:
+                what = "hg_encode_text_embeds"
+                rc = _lib.lib().hg_encode_text_embeds(h, pf.data_ptr(), eot32.data_ptr(), R, L, out.data_ptr(), trunc, _stream_ptr(dev))
         if rc:
             self._trunc_memo = (None, 0, 0, 0)
-        self._ctx.check(rc, "hg_encode_text_embeds")
-        return out
+        self._ctx.check(rc, what)
+        return out, saved, eot32, trunc
 
     def forward(self, image, text):
         """clipnet/model.py:354-368."""

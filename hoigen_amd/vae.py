@@ -5,7 +5,9 @@ Reference: /root/reference/main_coop_vae.py — ``TextEncoder`` :45-63, ``Prompt
 :66-258, ``Encoder`` :261-279, ``Generator`` :282-296, ``vae_loss`` :300-303; ``mlp_net``
 /root/reference/finetune_ship.py:302-314 (twin main_tip_finetune.py:313-324).
 
-Inference only (no autograd through the kernels); tensors must live on a HIP device.
+Inference only (no autograd through the kernels) with one exception: ``TextEncoder`` and the prompt learners take
+``differentiable=True`` and then give the gradients the VAE training loop needs (main_coop_vae.py:452-468: ``ctx`` of the prompt learner
+and whatever produced ``bias``, through the frozen text tower).  Tensors must live on a HIP device.
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import clip as _clip
@@ -335,10 +338,45 @@ def vae_loss(recon_x, x, mean, log_var, target=None) -> torch.Tensor:
     return loss[0]
 
 
-class TextEncoder(nn.Module):
-    """main_coop_vae.py:45-63 — shares the CLIP model's text tower (no copies)."""
+class _TextEncoderGrad(torch.autograd.Function):
+    """TextEncoder.forward with the gradient with respect to ``prompts`` (hg_encode_text_embeds_save / hg_text_backward_embeds).  The
+    frozen tower gets no weight gradients."""
 
-    def __init__(self, clip_model: CLIP):
+    @staticmethod
+    def forward(ctx, prompts, tokenized_prompts, clip_model):
+        # the saved stream is kept here, not in the context's workspace, which every other call (encode_image, the VAE, another text
+        # call) overwrites between this forward and its backward
+        out, saved, eot32, trunc = clip_model._encode_text_embeds(prompts, tokenized_prompts, save=True)
+        ctx.save_for_backward(saved, eot32)
+        ctx.clip_model, ctx.shape, ctx.trunc, ctx.in_dtype, ctx.sig = clip_model, tuple(prompts.shape), trunc, prompts.dtype, clip_model._text_sig
+        return out
+
+    @staticmethod
+    @once_differentiable      # the HIP backward records no graph: a double backward is an error, not a silent zero
+    def backward(ctx, grad_out):
+        saved, eot32 = ctx.saved_tensors
+        m, (R, L, D) = ctx.clip_model, ctx.shape
+        dev = saved.device
+        if m._text_sig != ctx.sig or _sig(m._text_params()) != ctx.sig:
+            raise RuntimeError("hoigen_amd: the text tower's weights changed between the forward and the backward of TextEncoder")
+        h = m._sync_text(dev)
+        go = grad_out.detach().to(torch.float32).contiguous()
+        gp = torch.empty(R, L, D, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            m._ctx.check(_lib.lib().hg_text_backward_embeds(h, saved.data_ptr(), eot32.data_ptr(), go.data_ptr(), R, L, ctx.trunc,
+                                                            gp.data_ptr(), _stream_ptr(dev)), "hg_text_backward_embeds")
+        return gp.to(ctx.in_dtype), None, None
+
+
+class TextEncoder(nn.Module):
+    """main_coop_vae.py:45-63 — shares the CLIP model's text tower (no copies).
+
+    ``differentiable=True``: a call with grad mode on and ``prompts.requires_grad`` returns text features that back-propagate to
+    ``prompts`` through the frozen tower (the VAE training loop, main_coop_vae.py:452-468).  The tower itself must be frozen: no weight
+    gradients are computed.  At most 80 executed tokens per prompt and one pass of the tower (256 prompts of 77 tokens are one pass).
+    Every other call is the inference call; the default (``False``) refuses gradient callers as before."""
+
+    def __init__(self, clip_model: CLIP, differentiable: bool = False):
         super().__init__()
         object.__setattr__(self, "_clip", clip_model)
         self.transformer = clip_model.transformer
@@ -346,21 +384,67 @@ class TextEncoder(nn.Module):
         self.ln_final = clip_model.ln_final
         self.text_projection = clip_model.text_projection
         self.dtype = clip_model.dtype
+        self.differentiable = bool(differentiable)
 
-    @_inference_only
     def forward(self, prompts: torch.Tensor, tokenized_prompts: torch.Tensor) -> torch.Tensor:
+        if self.differentiable and torch.is_grad_enabled() and prompts.requires_grad:
+            trainable = [n for n, p in self._clip.named_parameters()
+                         if p.requires_grad and not n.startswith("visual.") and n != "logit_scale"]
+            if trainable:
+                raise RuntimeError(
+                    f"hoigen_amd: TextEncoder(differentiable=True) needs a frozen text tower, but {len(trainable)} of its parameters "
+                    f"require grad (first: {trainable[0]}).  This path computes the gradient with respect to the prompts only, no weight "
+                    "gradients: freeze CLIP as main_coop_vae.py:316-318 does (requires_grad_(False))")
+            return _TextEncoderGrad.apply(prompts, tokenized_prompts, self._clip)
+        return self._inference(prompts, tokenized_prompts)
+
+    @_inference_only(name="forward")
+    def _inference(self, prompts, tokenized_prompts):
         return self._clip.encode_text_embeds(prompts, tokenized_prompts)
+
+
+class _AssemblePromptsGrad(torch.autograd.Function):
+    """PromptLearner_*.forward with the gradients of ``ctx`` and ``bias`` (hg_assemble_prompts / hg_assemble_prompts_backward)."""
+
+    @staticmethod
+    def forward(ctx, bias, ctx_param, learner, target):
+        out = learner._assemble(bias, target, None, None)
+        ctx.learner, ctx.dtypes = learner, (bias.dtype, ctx_param.dtype)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_prompts):
+        pl = ctx.learner
+        g = grad_prompts.detach().to(torch.float32).contiguous()
+        R, L, D = g.shape
+        dev = g.device
+        g_ctx = torch.empty(pl.n_ctx, D, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        g_bias = torch.empty(R, D, device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        if g_ctx is None and g_bias is None:
+            return None, None, None, None
+        h = _util_ctx.get(dev)
+        with torch.cuda.device(dev):
+            _util_ctx.check(_lib.lib().hg_assemble_prompts_backward(
+                h, g.data_ptr(), R, L, pl.n_ctx, D, g_ctx.data_ptr() if g_ctx is not None else None,
+                g_bias.data_ptr() if g_bias is not None else None, _stream_ptr(dev)), "hg_assemble_prompts_backward")
+        return (g_bias.to(ctx.dtypes[0]) if g_bias is not None else None, g_ctx.to(ctx.dtypes[1]) if g_ctx is not None else None,
+                None, None)
 
 
 class _PromptLearner(nn.Module):
     """PromptLearner_{hoi,h,o} (main_coop_vae.py:66-258): learnable context ``ctx [n_ctx,D]`` shifted by
     a per-sample ``bias`` between the SOT embedding and the class-name suffix.  The three reference
-    classes differ only in ``n_ctx`` (5 / 4 / 4)."""
+    classes differ only in ``n_ctx`` (5 / 4 / 4).
+
+    ``differentiable=True``: a call with grad mode on whose ``bias`` or ``ctx`` requires grad returns prompts that back-propagate to
+    both (main_coop_vae.py:452-468 trains ``ctx``, and ``bias`` carries the generator's graph); the default refuses gradient callers."""
 
     N_CTX = 4
 
-    def __init__(self, classnames: List[str], clip_model: CLIP):
+    def __init__(self, classnames: List[str], clip_model: CLIP, differentiable: bool = False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         n_ctx = self.N_CTX
         self.dtype = clip_model.dtype
         ctx_dim = clip_model.ln_final.weight.shape[0]
@@ -394,15 +478,26 @@ class _PromptLearner(nn.Module):
         self._names_key = key
         self._f32_key = None              # fp32 operands of hg_assemble_prompts are rebuilt on the next forward
 
-    @_inference_only
-    @torch.no_grad()
     def forward(self, bias: torch.Tensor, target: torch.Tensor, out: Optional[torch.Tensor] = None,
                 tokens: Optional[int] = None) -> torch.Tensor:
         """main_coop_vae.py:119-128 -> prompts [R, L, D].
 
         Extensions for the device-resident sampling loop (hoigen_amd.generation): ``tokens`` = only the first ``tokens`` positions of
         every prompt (what a text tower truncated to max(EOT) + 1 reads: 13-16 of 77), ``out`` = a caller-owned fp32 ``[R, L, D]``
-        buffer, e.g. a slice of the batch the tower is called with (no concatenation afterwards)."""
+        buffer, e.g. a slice of the batch the tower is called with (no concatenation afterwards).  Both are inference-only."""
+        if self.differentiable and torch.is_grad_enabled() and (bias.requires_grad or self.ctx.requires_grad):
+            if out is not None or tokens is not None:
+                raise RuntimeError("hoigen_amd: the out= / tokens= extensions of the prompt learners are inference-only (call them under "
+                                   "torch.no_grad())")
+            return _AssemblePromptsGrad.apply(bias, self.ctx, self, target)
+        return self._inference(bias, target, out, tokens)
+
+    @_inference_only(name="forward")
+    def _inference(self, bias, target, out=None, tokens=None):
+        return self._assemble(bias, target, out, tokens)
+
+    @torch.no_grad()
+    def _assemble(self, bias: torch.Tensor, target: torch.Tensor, out: Optional[torch.Tensor], tokens: Optional[int]) -> torch.Tensor:
         _require_cuda(bias, "bias")
         h = _util_ctx.get(bias.device)
         bf = _f32(bias)

@@ -178,6 +178,26 @@ int hg_encode_text_ids(hg_ctx*, const int32_t* ids, int T, int L, float* out, in
  * already embedded, eot_idx [R] int32 = tokenized_prompts.argmax(-1) -> out [R,E] fp32. */
 int hg_encode_text_embeds(hg_ctx*, const float* prompts, const int32_t* eot_idx, int R, int L,
                           float* out, int trunc, void* stream);
+/* The input gradient of TextEncoder.forward: what the CoOp-VAE training loop back-propagates through the frozen tower
+ * (main_coop_vae.py:452-468 with CLIP frozen at :316-318).  No weight gradient of the tower is computed.
+ *
+ * hg_encode_text_embeds_save is hg_encode_text_embeds - the same plan, launches and bits in `out` - and additionally copies into the
+ * caller's `saved`, fp32 [layers * R * Leff + R][D], the stream as it enters every block ([layers][R * Leff][D]) and the last block's
+ * output on the EOT rows ([R][D]); Leff = trunc where 0 < trunc < L, else L.  The state lives in the caller's memory because every other
+ * entry point reuses the context's workspace between forward and backward.  One pass of the text tower at most (a budget of 65 536 rows:
+ * 256 prompts of 77 tokens are one pass); a longer call is refused with HG_ERR_INVALID.
+ *
+ * hg_text_backward_embeds: grad_out [R,E] fp32 -> grad_prompts [R,L,D] fp32 from that `saved`, the same eot_idx, L and trunc.  Each
+ * block is recomputed from its saved input and walked backwards; Leff <= 80.  Gradients that are MFMA operands are
+ * fp16, so the backward runs on grad_out scaled per prompt by the power of two that brings its largest element into [1, 2) and is
+ * unscaled at its end; nothing saturates (an overflow shows as Inf / NaN in that prompt's gradient).  Rows behind a prompt's EOT and
+ * positions >= Leff are exactly 0.  The transposed copies of the linears the backward GEMMs read (76 MB for ViT-B/16's text tower) are
+ * built on the first call - synchronously, on the null stream, so not inside a stream capture - and dropped by hg_load_text.  Workspace
+ * of the context beyond the forward's: 26 bytes x rows x D (263 MB for 256 prompts of 77 tokens at D = 512). */
+int hg_encode_text_embeds_save(hg_ctx*, const float* prompts, const int32_t* eot_idx, int R, int L, float* out, int trunc,
+                               float* saved, void* stream);
+int hg_text_backward_embeds(hg_ctx*, const float* saved, const int32_t* eot_idx, const float* grad_out, int R, int L, int trunc,
+                            float* grad_prompts, void* stream);
 /* token_embedding(ids) (clipnet/model.py:340): ids [n] int32 -> out [n,D] fp32 (exact gather). */
 int hg_token_embedding(hg_ctx*, const int32_t* ids, int n, float* out, void* stream);
 
@@ -195,6 +215,11 @@ int hg_mlp_net(hg_ctx*, int slot, const float* x, int R, float* out, void* strea
 int hg_assemble_prompts(hg_ctx*, const float* prefix, const float* suffix, const float* ctx,
                         const float* bias, const int32_t* target, int R, int C, int L, int n_ctx,
                         int D, float* prompts, void* stream);
+/* Backward of PromptLearner_*.forward (main_coop_vae.py:119-128: prompts = [prefix | ctx + bias | suffix]): grad_prompts [R,L,D] ->
+ * grad_bias [R,D] = sum_j g[r][1 + j] and grad_ctx [n_ctx,D] = sum_r g[r][1 + j]; either may be NULL.  grad_ctx is summed in two stages
+ * in a fixed order (64 prompts of a chunk in ascending order, then the chunks): no atomics, the same bits on every run. */
+int hg_assemble_prompts_backward(hg_ctx*, const float* grad_prompts, int R, int L, int n_ctx, int D, float* grad_ctx,
+                                 float* grad_bias, void* stream);
 /* x / x.norm(dim=-1, keepdim=True) (main_coop_vae.py:438,466); in == out allowed. */
 int hg_l2_normalize(hg_ctx*, const float* x, int R, int D, float* out, void* stream);
 /* RoI-align over the variant-C local feature map (SURVEY.md 8f-4;
@@ -942,6 +967,8 @@ int hg_workspace_bytes(hg_ctx*, uint64_t* bytes);
 #define HG_PROF_RESNET_CONV 107 /* one convolution launch of hg_resnet_stages / hg_test_resnet_conv: M = output pixels (B * Ho * Wo), N = cout, K = k * k * cin */
 #define HG_PROF_RESNET_STEM 108 /* the stem launch of hg_resnet_stem / hg_resnet_body / hg_test_resnet_stem: M = pooled pixels (B * Hp * Wp), N = 64, K = 147 */
 #define HG_PROF_RESNET_POOL 109 /* the pool + normalise launch of hg_resnet_features / hg_test_resnet_pool: M = images, N = channels, K = positions (Ho * Wo) */
+#define HG_PROF_TEXT_ATTN_BWD 110 /* attention backward of hg_text_backward_embeds: M = prompts, N = tokens per prompt, K = heads */
+#define HG_PROF_TEXT_GRAD_ROWS 111 /* its row and elementwise launches (LayerNorm backward, qgelu', fp16 casts, scale, copies): M = rows, N = width, K = 0 */
 #define HG_PROF_MLP_PAIR 103/* c_fc -> QuickGELU -> c_proj as one launch: M = rows, N = hidden width (4 D), K = D */
 typedef struct {
     int32_t kind; /* GEMM epilogue class or HG_PROF_ATTENTION */
@@ -1146,6 +1173,19 @@ typedef struct {
     int32_t i[6];
 } hg_test_elem_args;
 int hg_test_elem(hg_ctx*, int op, const hg_test_elem_args* args, void* stream);
+
+/* Test hook for the backward of the text tower (hoigen_amd/csrc/hg_text_grad.hip, hg_text_bwd.hip; main_coop_vae.py:452-468): ONE
+ * launcher with the caller's device buffers in the kernels' own types, or (op 6) one whole block backward on the loaded text tower.
+ *   op                     p[0 ..]                                                          i[0 ..]                       n
+ *   0  text_attn_bwd       qkv (fp16), dout (fp16), dqkv (fp16)                             n_seq, L, heads
+ *   1  layernorm_bwd       x, gamma, dy, g (in place), sel (int32, nullable)                M, D, rows_per_seq
+ *   2  qgelu_bwd           df (fp16), u (fp16), du (fp16)                                                                 elements
+ *   3  grad_scale          go, go16 (fp16), sinv                                            R, E
+ *   4  grad_unscale        g, sinv, out                                                     R, L, Leff, D
+ *   5  prompts_bwd         g, partial, grad_ctx, grad_bias                                  R, L, n_ctx, D
+ *   6  block backward      x_in [n_seq * L, D], g [n_seq * L, D] (in place)                 block, n_seq, L
+ * (pointers fp32 where no type is given) */
+int hg_test_text_grad(hg_ctx*, int op, const hg_test_elem_args* args, void* stream);
 
 /* Test hook for the row kernels of the DETR encoder and decoder (hoigen_amd/csrc/hg_detr_rows.hip): ONE launch_detr_* call with the
  * caller's device pointers, in the kernels' own types (fp32, fp16 - nothing is converted on the way), on the caller's stream.  No
